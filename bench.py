@@ -22,8 +22,11 @@ One "step" = one pass of the hot path over one resident batch:
   config 5: ControlIK continuous mode, 4096 trajectories x 1000 control steps per pass; consecutive passes overlap
     (RSIK_OPT_CONT_GOALS_RESIDENT; `steady_state.launch_forms_ms` holds the other launch forms).
 
-Prints ONE JSON line on rank 0 (the repo prompt's bench contract) carrying `roofline` (traffic measured in the run; `extras.hbm_copy`
-confirms the 8 TB/s it is priced against) and `cpu_baseline`.
+A plain run sets up, warms up, times the K steps, writes the outputs of the last timed step (`--dump-outputs DIR`) and prints ONE
+JSON line on rank 0 (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, `roofline` from the timed steps).  `--full`
+adds everything else the line can carry: at N = 1 without --config the other BASELINE configs (`other_configs`), the `steady_state`
+legs, `cpu_baseline` with its parity check, `extras` (cold HBM, `hbm_copy` confirming the 8 TB/s `roofline` is priced against, the
+sustained clock, the VALU calibration), `roofline.traffic` measured in the run with `rocprofv3 --pmc`, and at N > 1 the other gather form.
 """
 import argparse
 import json
@@ -62,6 +65,31 @@ def _quiet(fn, *a, **k):
 
     with contextlib.redirect_stdout(io.StringIO()):
         return fn(*a, **k)
+
+
+DUMP_BUDGET_BYTES = 32 << 20  # --dump-outputs: float64 bytes written at most; beyond that a fixed, seeded sample of the rows
+DUMP_SEED = 20250204
+
+
+def dump_outputs(out_dir, arrays, row_axis=0):
+    """Writes `arrays` (tensors whose `row_axis` has the same length: one row per pose, or per trajectory for config 5) as
+    out_dir/<name>.npy in float64.  If all of them together exceed DUMP_BUDGET_BYTES, the same rows of every array are written:
+    a sample drawn with a fixed seed, in ascending order, its indices in out_dir/sample_rows.npy.  Returns what was written."""
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    rows = next(iter(arrays.values())).shape[row_axis]
+    per_row = sum(8 * t.numel() // max(1, rows) for t in arrays.values())
+    keep = min(rows, max(1, DUMP_BUDGET_BYTES // max(1, per_row)))
+    idx = None
+    if keep < rows:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(rows, size=keep, replace=False))
+        np.save(os.path.join(out_dir, "sample_rows.npy"), idx.astype(np.float64))
+    for name, t in arrays.items():
+        if idx is not None:
+            t = t.index_select(row_axis, torch.as_tensor(idx, device=t.device))
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy().astype(np.float64))
+    return {"dir": out_dir, "arrays": sorted(arrays), "rows": rows, "rows_written": keep, "sampled": idx is not None}
 
 
 # One-GPU figures the driver recorded for the configs the N > 1 line runs (BENCH_r03.json, other_configs, W = 5 / K = 20): what an N-GPU
@@ -552,7 +580,17 @@ def parse_args(argv):
                          "counters committed under profiles/ are quoted instead when they belong to this build")
     ap.add_argument("--no-other-configs", action="store_true",
                     help="default run (N = 1, no --config): do not time configs 3, 4 and 5 after the headline config")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the other configs, the steady-state legs, the CPU baseline and its parity check, the extras, "
+                         "the traffic measured under rocprofv3 and (N > 1) the other gather form; the --no-* options above switch parts off "
+                         "again.  Without it a run only sets up, warms up, times the K steps, dumps its outputs and prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last of them computed as DIR/<name>.npy (float64; a fixed, seeded "
+                         "sample of the rows where the whole would exceed %d MiB, their indices in DIR/sample_rows.npy)" % (DUMP_BUDGET_BYTES >> 20))
     args = ap.parse_args(argv)
+    if not args.full:
+        args.no_other_configs = args.no_cpu_baseline = args.no_steady_state = True
+        args.no_extras = args.no_valu_calibration = args.no_live_traffic = True
     if args.graph:
         args.launch = "graph"
     if args.gather_every_step:
@@ -711,7 +749,7 @@ def main(argv=None, return_line=False):
         os.environ.update(WORLD_SIZE="1", RANK="0", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world == 1 and args.config == 0 and not args.no_other_configs and not args.rendezvous_only and not args.grouped:
-        others_argv = ["--steps", "20", "--warmup", "5", "--no-extras", "--no-valu-calibration", "--no-other-configs", "--cpu-seconds", "2"]
+        others_argv = ["--full", "--steps", "20", "--warmup", "5", "--no-extras", "--no-valu-calibration", "--no-other-configs", "--cpu-seconds", "2"]
         if args.lib:
             others_argv += ["--lib", args.lib]
         line, others, order = run_default_protocol(
@@ -1040,6 +1078,16 @@ def _run(argv):
     step_ms_events = e0.elapsed_time(e1) / args.steps
     progress(f"timed region done: {elapsed * 1e3:.1f} ms")
 
+    # ---- --dump-outputs: what the last timed step computed, before any other leg runs
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        if cfg == 5:  # [n_steps, n_traj, ...]: one row per trajectory (the set the last pass wrote: overlapping passes take two in turn)
+            dumped = dump_outputs(args.dump_outputs, last_out[0], row_axis=1)
+        elif bufs is not None:  # N > 1: the gathered arrays (rows no rank sent stay zero)
+            dumped = dump_outputs(args.dump_outputs, bufs.result())
+        else:
+            dumped = dump_outputs(args.dump_outputs, out)
+
     # ---- config 5: the same K passes again after 60 more untimed ones (the clock has settled: the driver's W = 5 protocol above is the
     # headline, this is the steady state), in the form timed above and in the other one (eager <-> one captured pass replayed)
     steady = None
@@ -1157,9 +1205,9 @@ def _run(argv):
 
     # ---- N > 1: the OTHER gather form, timed the same way (round 6: `value` is whichever form --gather names — since round 5 the
     # north star's job shape, K sharded steps + ONE all-gather, by default; rounds 1-4 timed an all-gather inside every step — and both
-    # are measured in every run, each in its own overlapped form, so that lines of different rounds can be compared like for like)
+    # are measured in every --full run, each in its own overlapped form, so that lines of different rounds can be compared like for like)
     other_form = None
-    if grouped and gather_mode != "none" and cfg != 5:
+    if grouped and gather_mode != "none" and cfg != 5 and args.full:
         o_mode = "step" if gather_mode == "final" else "final"
         o_chunks = max(1, args.chunks) if o_mode == "step" else 1
         if n % o_chunks == 0:
@@ -1424,6 +1472,8 @@ def _run(argv):
                                 if (pipelined[0] and graph is None) else "K passes back to back without overlap between passes")
         if steady is not None:
             line["steady_state"] = steady
+        if dumped is not None:
+            line["dumped_outputs"] = dumped
 
         # ---- what bounds the kernel: counters committed with this build, live clock, cold-HBM run
         build_id = hs.build_id()

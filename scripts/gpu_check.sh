@@ -11,6 +11,6 @@ rc=$?
 echo "pytest exit $rc" >> $OUT/pytest.log
 tail -6 $OUT/pytest.log
 [ $rc -eq 0 ] || exit $rc
-timeout -k 10 300 python3 bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err || exit $?
+timeout -k 10 300 python3 bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err || exit $?
 cat $OUT/bench_default.json
 timeout -k 10 120 python3 -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tee $OUT/smoke.log

@@ -12,7 +12,7 @@ cd /tmp
 # dispatches deadlocks on a replayed multi-stream graph (round 4: every --pmc pass of `--launch graph` sat until its timeout), and
 # waits on device words are not its business either)
 LAUNCH="eager --no-steady-state"; [ "$CFG" = 5 ] && LAUNCH="eager --phased-variant 1 --no-steady-state"
-python3 $R/bench.py --config $CFG > $OUT/bench.json 2> $OUT/bench.err
+python3 $R/bench.py --full --config $CFG > $OUT/bench.json 2> $OUT/bench.err
 # (config 5 under the kernel trace: the captured form, as in round 5 — the default is now the pipelined one, whose streams are tied by
 # device words and whose theta kernels wait for their prepare kernels themselves: not something to run under a tool that may serialise)
 TRACE_LAUNCH=""; [ "$CFG" = 5 ] && TRACE_LAUNCH="--launch graph"

@@ -327,3 +327,38 @@ def test_bench_defaults():
     assert bench.parse_args(["--gather-every-step"]).gather == "step" and bench.parse_args(["--graph"]).launch == "graph"
     h = bench.host_facts()
     assert h["cores_visible"] >= 1 and h["logical_cpus"] >= h["cores_visible"] and isinstance(h["cpu_model"], str) and h["cpu_model"]
+
+
+def test_bench_plain_run_and_full(monkeypatch, tmp_path):
+    """A plain bench run only times the headline; `--full` turns every other leg back on, where the --no-* options still switch parts
+    off.  `--dump-outputs`: float64 arrays, the same seeded sample of rows in every array once the budget is exceeded."""
+    import torch
+
+    import bench
+
+    a = bench.parse_args(["--steps", "5", "--warmup", "2"])
+    assert not a.full and a.steps == 5 and a.warmup == 2 and a.dump_outputs == ""
+    assert a.no_other_configs and a.no_cpu_baseline and a.no_steady_state and a.no_extras and a.no_valu_calibration and a.no_live_traffic
+    f = bench.parse_args(["--full"])
+    assert not (f.no_other_configs or f.no_cpu_baseline or f.no_steady_state or f.no_extras or f.no_valu_calibration or f.no_live_traffic)
+    assert bench.parse_args(["--full", "--no-extras"]).no_extras and bench.parse_args(["--dump-outputs", "d"]).dump_outputs == "d"
+
+    joints = torch.arange(100 * 7, dtype=torch.float64).reshape(100, 7)
+    state = torch.arange(100, dtype=torch.uint8)
+    got = bench.dump_outputs(str(tmp_path / "all"), {"joints": joints, "state": state})
+    assert got["rows_written"] == 100 and not got["sampled"] and not (tmp_path / "all" / "sample_rows.npy").exists()
+    j = np.load(tmp_path / "all" / "joints.npy")
+    assert j.dtype == np.float64 and np.array_equal(j, joints.numpy())
+    assert np.array_equal(np.load(tmp_path / "all" / "state.npy"), np.arange(100.0))
+
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 8 * 8 * 10)  # room for 10 rows of 8 float64
+    for d in ("s1", "s2"):
+        got = bench.dump_outputs(str(tmp_path / d), {"joints": joints, "state": state})
+        assert got["rows_written"] == 10 and got["sampled"]
+    idx = np.load(tmp_path / "s1" / "sample_rows.npy")
+    assert len(idx) == 10 and np.all(np.diff(idx) > 0) and np.array_equal(idx, np.load(tmp_path / "s2" / "sample_rows.npy"))
+    assert np.array_equal(np.load(tmp_path / "s1" / "joints.npy"), joints.numpy()[idx.astype(int)])
+    assert np.array_equal(np.load(tmp_path / "s1" / "state.npy"), idx)
+    traj = torch.zeros((3, 100, 7), dtype=torch.float64)  # config 5's layout: [steps, trajectories, 7], a row per trajectory
+    got = bench.dump_outputs(str(tmp_path / "t"), {"joints": traj}, row_axis=1)
+    assert got["rows"] == 100 and np.load(tmp_path / "t" / "joints.npy").shape == (3, got["rows_written"], 7)

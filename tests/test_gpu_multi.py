@@ -18,8 +18,9 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _bench(*argv, timeout=900):
+def _bench(*argv, timeout=900, full=True):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    argv = (("--full",) if full else ()) + argv  # (what these tests read beyond the headline is only measured with --full)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *argv], env=env, capture_output=True, text=True, timeout=timeout)
     assert p.returncode == 0, p.stderr[-4000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -196,6 +197,27 @@ def test_bench_settled_leg_of_configs_3_and_4():
         cb = d["cpu_baseline"]
         assert cb["cores_visible"] >= cb["threads_used"] == cb["cores"] >= 1 and isinstance(cb["cpu_model"], str) and cb["cpu_model"]
         assert str(cb["threads_used"]) in cb["threads_probed"]
+
+
+def test_bench_plain_run_dumps_the_last_step(tmp_path):
+    """A plain run (no --full) times the headline alone and prints the line's core; `--dump-outputs` writes what the last timed step
+    computed, float64, and two runs with the same arguments write the same arrays (the inputs are seeded)."""
+    lines = []
+    for d in ("a", "b"):
+        lines.append(_bench("--config", "2", "--poses", "65536", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / d),
+                            full=False))
+    line = lines[0]
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0 and line["higher_is_better"] is True
+    assert line["dtype"] == "f64" and line["unit"] == "solves/s"
+    for moved in ("cpu_baseline", "steady_state", "extras", "other_configs"):
+        assert moved not in line, moved
+    du = line["dumped_outputs"]
+    assert du["rows"] == 65536 and not du["sampled"] and du["arrays"] == ["interval", "joints", "reachable", "state"]
+    j = np.load(tmp_path / "a" / "joints.npy")
+    assert j.dtype == np.float64 and j.shape == (65536, 7) and np.isfinite(j).all()
+    assert np.array_equal(np.load(tmp_path / "a" / "reachable.npy"), np.ones(65536))
+    for name in du["arrays"]:
+        assert np.array_equal(np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy"), equal_nan=True), name
 
 
 def test_stage_timers_script():
