@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define RSIK_ABI_VERSION 7
+#define RSIK_ABI_VERSION 8
 
 /* ---- status codes ---- */
 #define RSIK_OK 0
@@ -288,6 +288,37 @@ int rsik_control_discrete(rsik_ctx *ctx, int64_t n, const double *const m12_soa[
                           int arm_uniform, int nb_search_points, double preferred_theta, int constrained_mode,
                           const double *previous_sol_host, const double *current_joints, double orbita3d_max_angle,
                           double *joints, uint8_t *reachable, uint8_t *state, uint8_t *emergency);
+
+/*
+ * Per-row previous joints: n independent callers (robots, planner seeds, arms of a fleet) in one launch, each with its own
+ * last solution.  Same arguments, checks and outputs as the entry above it, except that the launch-uniform host array is
+ * replaced by an [n,7] row-major DEVICE array, one row per pose / goal (not NULL: RSIK_E_INVALID).  With every row equal to
+ * the uniform vector (per arm for discrete) the outputs are bit for bit those of the uniform entry, except that a discrete
+ * row that falls back to previous_sol (no theta found, current_joints NULL) takes the sin / cos of its wrist joints on the
+ * device instead of from the host's libm (a few ulp; for a previous_sol whose wrist pitch lies beyond +-pi/2 — not a
+ * solution any call returns — those ulps can also decide which turn allow_multiturn picks).  "Rows that are not numbers" applies row by row: a NaN or an infinity
+ * in one row's previous vector changes only that row's outputs.
+ * There is no per-row previous_theta: discrete mode hands it to limit_theta_to_interval and get_best_discrete_theta, and
+ * neither uses it (utils.py:93-112, 334-396; the Q12 note of rsik_device.hpp).
+ *
+ * rsik_solve_rows — rsik_solve with previous_joints [n,7]: row i is get_joints' previous_joints for pose i
+ *   (symbolic_ik.py:697-699; read only at an exact shoulder / elbow singularity, :751-753, :782-784).
+ */
+int rsik_solve_rows(rsik_ctx *ctx, int64_t n, const double *const pose_soa[6], const uint8_t *arm, int arm_uniform,
+                    int theta_policy, const double *theta_in, const double *previous_joints, double *joints,
+                    double *interval, double *elbow, uint8_t *reachable, uint8_t *state);
+
+/*
+ * rsik_control_discrete_rows — rsik_control_discrete with previous_sol [n,7]: row i is ControlIK.previous_sol[name] of the
+ *   caller that owns goal i, for that row's own arm (no 2x7 split).  It is get_joints' previous_joints (control_ik.py:454-456),
+ *   the fallback joints when no theta is found and current_joints is NULL (:237-238, :457-458), and safety_checks'
+ *   reference (allow_multiturn and the +-6 pi limits, utils.py:493-505, 535-568).  Nothing is latched: a caller whose
+ *   emergency stop is set filters its rows on the host (the reference returns previous_sol without solving).
+ */
+int rsik_control_discrete_rows(rsik_ctx *ctx, int64_t n, const double *const m12_soa[12], const uint8_t *arm,
+                               int arm_uniform, int nb_search_points, double preferred_theta, int constrained_mode,
+                               const double *previous_sol, const double *current_joints, double orbita3d_max_angle,
+                               double *joints, uint8_t *reachable, uint8_t *state, uint8_t *emergency);
 
 /*
  * rsik_control_continuous_step — ControlIK.symbolic_inverse_kinematics(name, M, "continuous", ...)

@@ -24,7 +24,7 @@ def use_library(path: str) -> None:
     LIB_PATH = os.path.abspath(path)
 
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 RSIK_OK = 0
 RSIK_E_INVALID, RSIK_E_NO_DEVICE, RSIK_E_HIP, RSIK_E_NOT_SET = -1, -2, -3, -4
 
@@ -57,6 +57,9 @@ PROTOTYPES = {
     "rsik_solve": (C.c_int, [_vp, C.c_int64, C.POINTER(_vp), _vp, C.c_int, C.c_int, _vp, _dp, _vp, _vp, _vp, _vp, _vp]),
     "rsik_control_discrete": (C.c_int, [_vp, C.c_int64, C.POINTER(_vp), _vp, C.c_int, C.c_int, C.c_double, C.c_int, _dp,
                                         _vp, C.c_double, _vp, _vp, _vp, _vp]),
+    "rsik_solve_rows": (C.c_int, [_vp, C.c_int64, C.POINTER(_vp), _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rsik_control_discrete_rows": (C.c_int, [_vp, C.c_int64, C.POINTER(_vp), _vp, C.c_int, C.c_int, C.c_double, C.c_int, _vp,
+                                             _vp, C.c_double, _vp, _vp, _vp, _vp]),
     "rsik_control_continuous_step": (C.c_int, [_vp, C.c_int64, C.POINTER(_vp), C.POINTER(_vp), _vp, C.c_int, _vp, C.c_double, _dp,
                                                C.c_int, C.c_double, _vp, C.c_double, _vp, _vp, _vp, _vp]),
     "rsik_control_continuous_run": (C.c_int, [_vp, C.c_int64, C.c_int64, _vp, C.POINTER(_vp), _vp, C.c_int, C.c_int, C.c_double, _dp,

@@ -161,9 +161,12 @@ class HipSolver:
         want_elbow: bool = True,
         out: Optional[Dict[str, torch.Tensor]] = None,
         plan_only: bool = False,
+        previous_joints_rows: Optional[torch.Tensor] = None,
     ) -> Dict[str, torch.Tensor]:
         """pose_soa: [6, n] float64 (rows px,py,pz,roll,pitch,yaw).  Returns joints [n,7], interval [n,2],
         elbow [n,3], reachable [n] u8, state [n] u8 (device tensors, asynchronous on the current stream).
+        previous_joints: 7 values for every pose (rsik_solve); previous_joints_rows: [n,7], one row per pose
+        (rsik_solve_rows: n independent callers in one launch).  Not both.
         plan_only=True launches nothing and adds res["launch"], a zero-overhead re-launch callable (see plan())."""
         if pose_soa.dim() != 2 or pose_soa.shape[0] != 6:
             raise ValueError("pose_soa must have shape [6, n]")
@@ -185,7 +188,14 @@ class HipSolver:
         state = self._out_buf(out, "state", (n,), _U8)
         cols = (C.c_void_p * 6)(*[pose_soa[k].data_ptr() for k in range(6)])
         prev = None
-        if previous_joints is not None:
+        fn_name = "rsik_solve"
+        if previous_joints_rows is not None:
+            if previous_joints is not None:
+                raise ValueError("previous_joints and previous_joints_rows cannot be combined")
+            previous_joints_rows = self._dev_f64(previous_joints_rows, (n, 7), "previous_joints_rows")
+            prev = _ptr(previous_joints_rows)
+            fn_name = "rsik_solve_rows"
+        elif previous_joints is not None:
             pj = np.ascontiguousarray(previous_joints, dtype=np.float64)
             if pj.shape != (7,):
                 raise ValueError("previous_joints must have 7 entries")
@@ -194,12 +204,12 @@ class HipSolver:
                  _ptr(joints), _ptr(interval), _ptr(elbow), _ptr(reachable), _ptr(state))
         res = {"interval": interval, "reachable": reachable, "state": state}
         if plan_only:
-            res["launch"] = self.plan("rsik_solve", *cargs)
-            res["_keepalive"] = (pose_soa, arm, theta_in, cols, prev)
+            res["launch"] = self.plan(fn_name, *cargs)
+            res["_keepalive"] = (pose_soa, arm, theta_in, cols, prev, previous_joints_rows)
         else:
             with torch.cuda.device(self.device):
                 self._bind_stream()
-                self._check(self.lib.rsik_solve(self._h, *cargs))
+                self._check(getattr(self.lib, fn_name)(self._h, *cargs))
         if joints is not None:
             res["joints"] = joints
         if elbow is not None:
@@ -245,8 +255,11 @@ class HipSolver:
         orbita3d_max_angle: float = float(np.deg2rad(42.5)),
         out: Optional[Dict[str, torch.Tensor]] = None,
         plan_only: bool = False,
+        previous_sol_rows: Optional[torch.Tensor] = None,
     ) -> Dict[str, torch.Tensor]:
-        """m12_soa: [12, n] float64 (R row-major, then translation)."""
+        """m12_soa: [12, n] float64 (R row-major, then translation).  previous_sol: (2, 7), ControlIK.previous_sol of r and
+        l for the whole launch (rsik_control_discrete); previous_sol_rows: [n,7], the previous_sol of the caller that owns
+        each goal, for that row's own arm (rsik_control_discrete_rows: n independent callers in one launch).  Not both."""
         if m12_soa.dim() != 2 or m12_soa.shape[0] != 12:
             raise ValueError("m12_soa must have shape [12, n]")
         n = int(m12_soa.shape[1])
@@ -257,25 +270,31 @@ class HipSolver:
             arm = self._dev_u8(arm, n, "arm")
         if current_joints is not None:
             current_joints = self._dev_f64(current_joints, (n, 7), "current_joints")
-        ps = np.ascontiguousarray(previous_sol, dtype=np.float64)
-        if ps.shape != (2, 7):
-            raise ValueError("previous_sol must have shape (2, 7)")
+        if previous_sol_rows is not None:
+            if previous_sol is not None:
+                raise ValueError("previous_sol and previous_sol_rows cannot be combined")
+            ps = self._dev_f64(previous_sol_rows, (n, 7), "previous_sol_rows")
+            prev, fn_name = _ptr(ps), "rsik_control_discrete_rows"
+        else:
+            ps = np.ascontiguousarray(previous_sol, dtype=np.float64)
+            if ps.shape != (2, 7):
+                raise ValueError("previous_sol must have shape (2, 7)")
+            prev, fn_name = ps.ctypes.data_as(C.POINTER(C.c_double)), "rsik_control_discrete"
         joints = self._out_buf(out, "joints", (n, 7), _F64)
         reachable = self._out_buf(out, "reachable", (n,), _U8)
         state = self._out_buf(out, "state", (n,), _U8)
         emergency = self._out_buf(out, "emergency", (n,), _U8)
         cols = (C.c_void_p * 12)(*[m12_soa[k].data_ptr() for k in range(12)])
         cargs = (n, cols, _ptr(arm), int(arm_uniform), int(nb_search_points), float(preferred_theta), int(constrained_mode),
-                 ps.ctypes.data_as(C.POINTER(C.c_double)), _ptr(current_joints), float(orbita3d_max_angle), _ptr(joints),
-                 _ptr(reachable), _ptr(state), _ptr(emergency))
+                 prev, _ptr(current_joints), float(orbita3d_max_angle), _ptr(joints), _ptr(reachable), _ptr(state), _ptr(emergency))
         res = {"joints": joints, "reachable": reachable, "state": state, "emergency": emergency}
         if plan_only:
-            res["launch"] = self.plan("rsik_control_discrete", *cargs)
+            res["launch"] = self.plan(fn_name, *cargs)
             res["_keepalive"] = (m12_soa, arm, current_joints, cols, ps)
         else:
             with torch.cuda.device(self.device):
                 self._bind_stream()
-                self._check(self.lib.rsik_control_discrete(self._h, *cargs))
+                self._check(getattr(self.lib, fn_name)(self._h, *cargs))
         return res
 
     # ------------------------------------------------------------------ rsik_control_continuous_step

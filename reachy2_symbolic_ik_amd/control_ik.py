@@ -445,11 +445,16 @@ class ControlIK:
         preferred_theta: float = -4 * np.pi / 6,
         out: Optional[Dict[str, torch.Tensor]] = None,
         plan_only: bool = False,
+        previous_sol: Any = None,
     ) -> Dict[str, torch.Tensor]:
         """Discrete-mode IK for a batch of goal matrices.
 
         name: "r_arm" / "l_arm" for a single-arm batch, or a uint8 tensor/array [n] of arm ids (0 = r, 1 = l).
         M: [n,4,4] or packed SoA [12,n].  current_joints: [n,7] or None (=> previous_sol of the pose's arm).
+        previous_sol: None (=> this object's previous_sol of each pose's arm) or [n,7]: the batch is n independent callers,
+        row i the previous_sol of the caller that owns goal i, for that row's own arm (rsik_control_discrete_rows).  Such a
+        call neither reads nor writes this object's previous_sol or emergency_stop; a caller whose emergency stop is latched
+        leaves its rows out (the reference returns previous_sol without solving, control_ik.py:205-210).
         Returns device tensors joints [n,7], reachable [n], state [n], emergency [n].
         """
         if constrained_mode not in _abi.MODES:
@@ -466,8 +471,8 @@ class ControlIK:
         return self._solver.control_discrete(
             m12, arm=arm_t, arm_uniform=arm_uniform, nb_search_points=int(self.nb_search_points),
             preferred_theta=float(preferred_theta), constrained_mode=_abi.MODES[constrained_mode],
-            previous_sol=self._previous_sol_2x7(), current_joints=current_joints,
-            orbita3d_max_angle=float(self.orbita3D_max_angle), out=out, plan_only=plan_only)
+            previous_sol=self._previous_sol_2x7() if previous_sol is None else None, current_joints=current_joints,
+            orbita3d_max_angle=float(self.orbita3D_max_angle), out=out, plan_only=plan_only, previous_sol_rows=previous_sol)
 
     def run_continuous_trajectories(
         self,

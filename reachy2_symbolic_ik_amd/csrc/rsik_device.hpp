@@ -702,8 +702,11 @@ struct JointsOut {
 // FRESH = true: the state comes straight from reach() on the same pose (the fused kernels), so |wrist - elbow| is
 // the forearm length by construction; FRESH = false (stored solver state, possibly moved by an earlier projection,
 // Q1) measures it.
-template <bool FRESH, bool TIPZ = false, class Acc>
-__device__ JointsOut joints_from_theta_g(const Acc& A, Reach& r, const Goal& G, double ct, double st, const double* prev) {
+typedef const __attribute__((address_space(1))) double* GConst;  // a global-memory row (per-row previous joints)
+// Prev: the pointer type of previous_joints — the per-row entries pass a global-address-space row (GConst), which keeps
+// their instantiations apart from the launch-constant ones (sharing one changes how the uniform kernels are compiled).
+template <bool FRESH, bool TIPZ = false, class Acc, class Prev = const double*>
+__device__ JointsOut joints_from_theta_g(const Acc& A, Reach& r, const Goal& G, double ct, double st, Prev prev) {
     RSIK_MARK("joints_elbow");
     JointsOut o;
     V3 e = elbow_on_circle(r, ct, st);

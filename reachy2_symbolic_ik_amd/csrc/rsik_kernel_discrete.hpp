@@ -19,7 +19,10 @@ struct DiscreteArgs {
     double pref[2];       // preferred theta per arm slot (already mirrored for l, C:252)
     double pref_cs[2], pref_sn[2];  // its cosine / sine (host libm, once per launch)
     double lim[2][2];     // interval_limit per arm slot (C:225-250)
-    double prev_sol[2][7];
+    union {
+        double prev_sol[2][7];    // rsik_control_discrete: ControlIK.previous_sol per arm slot
+        const double* prev_rows;  // rsik_control_discrete_rows (PREV_ROWS kernels): [n,7] device, previous_sol of each goal's caller
+    };
     double prev_cs[2][3], prev_sn[2][3];  // cos / sin of previous_sol[4..6] (host libm): the wrist of a pose that falls back to it
     const double* current_joints;
     double max_angle, cos_max, sin_max;
@@ -134,7 +137,13 @@ __device__ __forceinline__ void sweep_theta_grid(const DiscreteArgs& K, uint64_t
 #define RSIK_DISC_BLOCK 256
 #endif
 constexpr int kDiscBlock = RSIK_DISC_BLOCK;  // threads per workgroup of the discrete kernel
-template <bool MIXED, bool PLANE>
+// PREV_ROWS: previous_sol is the goal's own row of K.prev_rows (rsik_control_discrete_rows) instead of the launch constants
+// K.prev_sol[slot] (+56 B per row): get_joints' previous_joints, the fallback joints and safety_checks' reference.
+struct PrevRowRegs { double v[7]; };  // PREV_ROWS: the row's previous_sol, loaded at the kernel's head
+struct NoPrevRow {};
+__device__ __forceinline__ const double* safety_prev(const PrevRowRegs& p, const double*) { return p.v; }
+__device__ __forceinline__ const double* safety_prev(const NoPrevRow&, const double* uniform) { return uniform; }
+template <bool MIXED, bool PLANE, bool PREV_ROWS = false>
 __global__ __launch_bounds__(kDiscBlock, RSIK_DISC_MIN_WAVES) RSIK_DISC_ATTR void control_discrete_kernel(const DiscreteArgs K) {
     __shared__ double lds_slab[kDiscBlock / 64][kDiscRows][64];
     const int lane = threadIdx.x & 63;
@@ -156,6 +165,13 @@ __global__ __launch_bounds__(kDiscBlock, RSIK_DISC_MIN_WAVES) RSIK_DISC_ATTR voi
 #pragma unroll
     for (int k = 0; k < 12; k++) m12[k] = K.in[k][ii];
     const bool lane_isl = MIXED ? (K.arm[ii] != 0) : false;
+    // PREV_ROWS: the row's previous_sol is issued here with the goal loads, so that its latency overlaps the whole kernel (loaded
+    // where the joint stage needs it, at the end of a one-round launch, it cost 13.6 -> 17.6 us on config 3); 14 VGPRs
+    [[maybe_unused]] std::conditional_t<PREV_ROWS, PrevRowRegs, NoPrevRow> prow;
+    if constexpr (PREV_ROWS) {
+#pragma unroll
+        for (int k = 0; k < 7; k++) prow.v[k] = K.prev_rows[ii * 7 + k];
+    }
         __shared__ SharedTables lds_tab;
     stage_tables<MIXED, (int)offsetof(DiscreteArgs, arms) + (MIXED ? 0 : (int)sizeof(ArmC)), kDiscBlock>(lds_tab, K.arms);
 #ifdef RSIK_TIMELINE_PROBE
@@ -262,6 +278,8 @@ __global__ __launch_bounds__(kDiscBlock, RSIK_DISC_MIN_WAVES) RSIK_DISC_ATTR voi
     RSIK_MARK("disc_joints");
     RSIK_DISC_PRIO(1);
     RSIK_DISC_PROBE(3);
+    // PREV_ROWS: the fallback joints and safety_checks take the row from `prow` (loaded at the head, `ii` as for current_joints:
+    // dead lanes read the last row); joints_from_theta_g reads it through the global row, only on an exact singularity.
     const double* prev = K.prev_sol[slot];
     double jv[7];
     double c4, s4, c5, s5, c6, s6;
@@ -272,13 +290,27 @@ __global__ __launch_bounds__(kDiscBlock, RSIK_DISC_MIN_WAVES) RSIK_DISC_ATTR voi
         const double* pk = &lds_slab[wave][0][0];
         G.tw = {pk[0 * 64 + lane], pk[1 * 64 + lane], pk[2 * 64 + lane]};
         G.xg = {pk[3 * 64 + lane], pk[4 * 64 + lane], pk[5 * 64 + lane]};
-        JointsOut o = joints_from_theta_g<true>(A, r, G, ct, st, prev);
+        if constexpr (PREV_ROWS) {
+            JointsOut o = joints_from_theta_g<true>(A, r, G, ct, st, (GConst)(K.prev_rows + ii * 7));
 #pragma unroll
-        for (int k = 0; k < 7; k++) jv[k] = o.j[k];
-        c4 = o.c4; s4 = o.s4; c5 = o.c5; s5 = o.s5; c6 = o.c6; s6 = o.s6;
+            for (int k = 0; k < 7; k++) jv[k] = o.j[k];
+            c4 = o.c4; s4 = o.s4; c5 = o.c5; s5 = o.s5; c6 = o.c6; s6 = o.s6;
+        } else {  // (the same three statements: see solve_kernel)
+            JointsOut o = joints_from_theta_g<true>(A, r, G, ct, st, prev);
+#pragma unroll
+            for (int k = 0; k < 7; k++) jv[k] = o.j[k];
+            c4 = o.c4; s4 = o.s4; c5 = o.c5; s5 = o.s5; c6 = o.c6; s6 = o.s6;
+        }
     } else if (K.current_joints) {  // C:457-458
 #pragma unroll
         for (int k = 0; k < 7; k++) jv[k] = K.current_joints[ii * 7 + k];
+        const double w3[3] = {jv[4], jv[5], jv[6]};
+        double sn3[3], cs3[3];
+        fast_sincos_n<3>(w3, sn3, cs3);
+        c4 = cs3[0]; s4 = sn3[0]; c5 = cs3[1]; s5 = sn3[1]; c6 = cs3[2]; s6 = sn3[2];
+    } else if constexpr (PREV_ROWS) {  // current_joints defaults to previous_sol (C:237-238): the row's own, sin / cos here
+#pragma unroll
+        for (int k = 0; k < 7; k++) jv[k] = prow.v[k];
         const double w3[3] = {jv[4], jv[5], jv[6]};
         double sn3[3], cs3[3];
         fast_sincos_n<3>(w3, sn3, cs3);
@@ -292,7 +324,7 @@ __global__ __launch_bounds__(kDiscBlock, RSIK_DISC_MIN_WAVES) RSIK_DISC_ATTR voi
     RSIK_MARK("disc_safety");
     RSIK_DISC_PROBE(6);
     RSIK_DISC_PRIO(0);
-    int em = safety_checks(A.utab, jv, c4, s4, c5, s5, c6, s6, prev, K.max_angle, K.cos_max, K.sin_max);
+    int em = safety_checks(A.utab, jv, c4, s4, c5, s5, c6, s6, safety_prev(prow, prev), K.max_angle, K.cos_max, K.sin_max);
     if (RSIK_RARE(invalid)) {  // no joints, no verdict on them (the reference has raised, C:215 / S:580)
 #pragma unroll
         for (int k = 0; k < 7; k++) jv[k] = __builtin_nan("");

@@ -15,7 +15,10 @@ struct SolveArgs {
     const uint8_t* arm;
     int theta_policy;
     const double* theta_in;
-    double prev[7];
+    union {
+        double prev[7];         // rsik_solve: get_joints' previous_joints, the same for every pose
+        const double* prev_rows;  // rsik_solve_rows (PREV_ROWS kernels): [n,7] device, one row per pose
+    };
     double* joints;
     double* interval;
     double* elbow;
@@ -245,7 +248,9 @@ __device__ __forceinline__ void flush_rows(double* __restrict__ out, int64_t wav
 // profiles/r01/timeline/: under the power-managed clock it is the executed instruction count that sets the time, not
 // how well the waves overlap.)
 // TIPZ: every arm of the launch has tip_x = tip_y = 0 (goal_from_euler_tipz: -24 fp64 operations per pose).
-template <int MIXED, bool TIPZ>
+// PREV_ROWS: previous_joints is the pose's own row of K.prev_rows (rsik_solve_rows), not the launch constant K.prev.
+// joints_from_theta_g reads it only on an exact singularity, so a pose that is not singular loads none of it.
+template <int MIXED, bool TIPZ, bool PREV_ROWS = false>
 __global__ __launch_bounds__(kBlock, RSIK_SOLVE_MIN_WAVES) void solve_kernel(const SolveArgs K) {
     __shared__ SharedTables lds_tab;
     __shared__ double lds[kBlock / 64][64 * 10];
@@ -324,11 +329,22 @@ __global__ __launch_bounds__(kBlock, RSIK_SOLVE_MIN_WAVES) void solve_kernel(con
                 }
                 fast_sincos(theta, &st, &ct);
             }
-            JointsOut o = joints_from_theta_g<true, TIPZ>(A, r, G, ct, st, (const double*)K.prev);
-            RSIK_MARK("stores");
+            // Two statements chosen at compile time: a pointer that could be either the kernarg array or a global row would
+            // turn the uniform kernels' loads into flat loads, and any shared local changes how the uniform kernels are
+            // scheduled.  tt is clamped, so dead lanes read a row in bounds.
+            if constexpr (PREV_ROWS) {
+                JointsOut o = joints_from_theta_g<true, TIPZ>(A, r, G, ct, st, (GConst)(K.prev_rows + (tile0 + tt) * 7));
+                RSIK_MARK("stores");
 #pragma unroll
-            for (int k = 0; k < 7; k++) jrow[k] = o.j[k];
-            erow[0] = o.elbow.x; erow[1] = o.elbow.y; erow[2] = o.elbow.z;
+                for (int k = 0; k < 7; k++) jrow[k] = o.j[k];
+                erow[0] = o.elbow.x; erow[1] = o.elbow.y; erow[2] = o.elbow.z;
+            } else {
+                JointsOut o = joints_from_theta_g<true, TIPZ>(A, r, G, ct, st, (const double*)K.prev);
+                RSIK_MARK("stores");
+#pragma unroll
+                for (int k = 0; k < 7; k++) jrow[k] = o.j[k];
+                erow[0] = o.elbow.x; erow[1] = o.elbow.y; erow[2] = o.elbow.z;
+            }
         } else {
             // (`opaque`: the value is made inside this branch — otherwise the compiler merges the two branches' LDS writes and
             // every wave, reachable or not, first fills ten registers pairs with NaN: 20 v_mov in the all-reachable config 2)

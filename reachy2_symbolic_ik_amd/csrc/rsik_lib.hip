@@ -257,36 +257,56 @@ static int check_arms(rsik_ctx* ctx, const uint8_t* arm, int arm_uniform, const 
     return RSIK_OK;
 }
 
-int rsik_solve(rsik_ctx* ctx, int64_t n, const double* const pose_soa[6], const uint8_t* arm, int arm_uniform,
-               int theta_policy, const double* theta_in, const double* previous_joints_host, double* joints,
-               double* interval, double* elbow, uint8_t* reachable, uint8_t* state) {
-    if (!ctx) return RSIK_E_INVALID;
-    if (n < 0) return fail(ctx, RSIK_E_INVALID, "rsik_solve: n < 0");
+extern "C++" {  // (templates: inside the extern "C" block)
+template <bool PREV_ROWS>
+static void launch_solve(bool mixed, bool mirror, bool tipz, dim3 grid, dim3 block, hipStream_t stream, const rsik::SolveArgs& K) {
+    if (mixed) {
+        if (mirror) {
+            if (tipz) hipLaunchKernelGGL((rsik::solve_kernel<2, true, PREV_ROWS>), grid, block, 0, stream, K);
+            else hipLaunchKernelGGL((rsik::solve_kernel<2, false, PREV_ROWS>), grid, block, 0, stream, K);
+        } else {
+            if (tipz) hipLaunchKernelGGL((rsik::solve_kernel<1, true, PREV_ROWS>), grid, block, 0, stream, K);
+            else hipLaunchKernelGGL((rsik::solve_kernel<1, false, PREV_ROWS>), grid, block, 0, stream, K);
+        }
+    } else {
+        if (tipz) hipLaunchKernelGGL((rsik::solve_kernel<0, true, PREV_ROWS>), grid, block, 0, stream, K);
+        else hipLaunchKernelGGL((rsik::solve_kernel<0, false, PREV_ROWS>), grid, block, 0, stream, K);
+    }
+}
+}
+
+// rsik_solve (previous_rows == NULL: previous_joints_host for every pose) and rsik_solve_rows (previous_rows: one device row per pose)
+static int solve_impl(rsik_ctx* ctx, const char* who, int64_t n, const double* const pose_soa[6], const uint8_t* arm, int arm_uniform,
+                      int theta_policy, const double* theta_in, const double* previous_joints_host, const double* previous_rows,
+                      double* joints, double* interval, double* elbow, uint8_t* reachable, uint8_t* state) {
+    const std::string w(who);
+    if (n < 0) return fail(ctx, RSIK_E_INVALID, w + ": n < 0");
     if (theta_policy < RSIK_THETA_INTERVAL0 || theta_policy > RSIK_THETA_NONE)
-        return fail(ctx, RSIK_E_INVALID, "rsik_solve: unknown theta_policy");
+        return fail(ctx, RSIK_E_INVALID, w + ": unknown theta_policy");
     if ((theta_policy == RSIK_THETA_EXPLICIT || theta_policy == RSIK_THETA_FRACTION) && !theta_in && n > 0)
-        return fail(ctx, RSIK_E_INVALID, "rsik_solve: theta_in is required for this theta_policy");
-    int rc = check_arms(ctx, arm, arm_uniform, "rsik_solve");
+        return fail(ctx, RSIK_E_INVALID, w + ": theta_in is required for this theta_policy");
+    int rc = check_arms(ctx, arm, arm_uniform, who);
     if (rc != RSIK_OK) return rc;
     if (n == 0) return RSIK_OK;
-    if (!pose_soa) return fail(ctx, RSIK_E_INVALID, "rsik_solve: pose_soa is NULL");
+    if (!pose_soa) return fail(ctx, RSIK_E_INVALID, w + ": pose_soa is NULL");
     rsik::SolveArgs K;
     K.n = n;
     for (int k = 0; k < 6; k++) {
-        if (!pose_soa[k]) return fail(ctx, RSIK_E_INVALID, "rsik_solve: a pose_soa column is NULL");
+        if (!pose_soa[k]) return fail(ctx, RSIK_E_INVALID, w + ": a pose_soa column is NULL");
         K.in[k] = pose_soa[k];
     }
     K.arm = arm;
     K.theta_policy = theta_policy;
     K.theta_in = theta_in;
-    for (int k = 0; k < 7; k++) K.prev[k] = previous_joints_host ? previous_joints_host[k] : 0.0;
+    if (previous_rows) K.prev_rows = previous_rows;  // (shares its kernarg bytes with K.prev)
+    else for (int k = 0; k < 7; k++) K.prev[k] = previous_joints_host ? previous_joints_host[k] : 0.0;
     K.joints = joints; K.interval = interval; K.elbow = elbow; K.reachable = reachable; K.state = state;
     if (arm) { K.arms[0] = ctx->arms[0]; K.arms[1] = ctx->arms[1]; }
     else { K.arms[0] = ctx->arms[arm_uniform]; K.arms[1] = ctx->arms[arm_uniform]; }
     RSIK_HIP(ctx, hipSetDevice(ctx->device));
     const int64_t tile = (int64_t)rsik::kBlock;
     const int64_t blocks = (n + tile - 1) / tile;
-    if (blocks > 0x7fffffffLL) return fail(ctx, RSIK_E_INVALID, "rsik_solve: n too large for one launch");
+    if (blocks > 0x7fffffffLL) return fail(ctx, RSIK_E_INVALID, w + ": n too large for one launch");
     dim3 grid((unsigned)blocks), block(rsik::kBlock);
     // tip offset along the goal z axis only (the default arm / the URDF): the specialised goal stage applies
     const bool tipz = K.arms[0].v[RSIK_C_TIPL] == 0.0 && K.arms[0].v[RSIK_C_TIPL + 1] == 0.0 &&
@@ -295,20 +315,27 @@ int rsik_solve(rsik_ctx* ctx, int64_t n, const double* const pose_soa[6], const 
     bool mirror = arm != nullptr && !ctx->options[RSIK_OPT_NO_MIRROR];
     for (int i = 0; mirror && i < RSIK_ARM_CONSTS_COUNT; i++)
         if (!rsik::arm_const_is_sided(i) && std::memcmp(&K.arms[0].v[i], &K.arms[1].v[i], sizeof(double)) != 0) mirror = false;
-    if (arm) {
-        if (mirror) {
-            if (tipz) hipLaunchKernelGGL((rsik::solve_kernel<2, true>), grid, block, 0, ctx->stream, K);
-            else hipLaunchKernelGGL((rsik::solve_kernel<2, false>), grid, block, 0, ctx->stream, K);
-        } else {
-            if (tipz) hipLaunchKernelGGL((rsik::solve_kernel<1, true>), grid, block, 0, ctx->stream, K);
-            else hipLaunchKernelGGL((rsik::solve_kernel<1, false>), grid, block, 0, ctx->stream, K);
-        }
-    } else {
-        if (tipz) hipLaunchKernelGGL((rsik::solve_kernel<0, true>), grid, block, 0, ctx->stream, K);
-        else hipLaunchKernelGGL((rsik::solve_kernel<0, false>), grid, block, 0, ctx->stream, K);
-    }
+    if (previous_rows) launch_solve<true>(arm != nullptr, mirror, tipz, grid, block, ctx->stream, K);
+    else launch_solve<false>(arm != nullptr, mirror, tipz, grid, block, ctx->stream, K);
     RSIK_HIP(ctx, hipGetLastError());
     return RSIK_OK;
+}
+
+int rsik_solve(rsik_ctx* ctx, int64_t n, const double* const pose_soa[6], const uint8_t* arm, int arm_uniform,
+               int theta_policy, const double* theta_in, const double* previous_joints_host, double* joints,
+               double* interval, double* elbow, uint8_t* reachable, uint8_t* state) {
+    if (!ctx) return RSIK_E_INVALID;
+    return solve_impl(ctx, "rsik_solve", n, pose_soa, arm, arm_uniform, theta_policy, theta_in, previous_joints_host, nullptr,
+                      joints, interval, elbow, reachable, state);
+}
+
+int rsik_solve_rows(rsik_ctx* ctx, int64_t n, const double* const pose_soa[6], const uint8_t* arm, int arm_uniform,
+                    int theta_policy, const double* theta_in, const double* previous_joints, double* joints,
+                    double* interval, double* elbow, uint8_t* reachable, uint8_t* state) {
+    if (!ctx) return RSIK_E_INVALID;
+    if (!previous_joints) return fail(ctx, RSIK_E_INVALID, "rsik_solve_rows: previous_joints is NULL");
+    return solve_impl(ctx, "rsik_solve_rows", n, pose_soa, arm, arm_uniform, theta_policy, theta_in, nullptr, previous_joints,
+                      joints, interval, elbow, reachable, state);
 }
 
 // Python float modulo (sign of the divisor), used for the l-arm limit wrap (C:243-250).
@@ -404,24 +431,39 @@ static bool singularity_plane_binds(const rsik::ArmC (&arms)[2]) {
     return false;
 }
 
-int rsik_control_discrete(rsik_ctx* ctx, int64_t n, const double* const m12_soa[12], const uint8_t* arm,
-                          int arm_uniform, int nb_search_points, double preferred_theta, int constrained_mode,
-                          const double* previous_sol_host, const double* current_joints, double orbita3d_max_angle,
-                          double* joints, uint8_t* reachable, uint8_t* state, uint8_t* emergency) {
-    if (!ctx) return RSIK_E_INVALID;
-    if (n < 0) return fail(ctx, RSIK_E_INVALID, "rsik_control_discrete: n < 0");
-    if (nb_search_points < 2) return fail(ctx, RSIK_E_INVALID, "rsik_control_discrete: nb_search_points must be >= 2");
+extern "C++" {  // (templates: inside the extern "C" block)
+template <bool PREV_ROWS>
+static void launch_discrete(bool mixed, bool plane_binds, dim3 grid, dim3 block, hipStream_t stream, const rsik::DiscreteArgs& K) {
+    if (mixed) {
+        if (plane_binds) hipLaunchKernelGGL((rsik::control_discrete_kernel<true, true, PREV_ROWS>), grid, block, 0, stream, K);
+        else hipLaunchKernelGGL((rsik::control_discrete_kernel<true, false, PREV_ROWS>), grid, block, 0, stream, K);
+    } else {
+        if (plane_binds) hipLaunchKernelGGL((rsik::control_discrete_kernel<false, true, PREV_ROWS>), grid, block, 0, stream, K);
+        else hipLaunchKernelGGL((rsik::control_discrete_kernel<false, false, PREV_ROWS>), grid, block, 0, stream, K);
+    }
+}
+}
+
+// rsik_control_discrete (previous_rows == NULL: previous_sol_host, 2x7, per arm) and rsik_control_discrete_rows (previous_rows:
+// one device row per goal, previous_sol_host NULL)
+static int control_discrete_impl(rsik_ctx* ctx, const char* who, int64_t n, const double* const m12_soa[12], const uint8_t* arm,
+                                 int arm_uniform, int nb_search_points, double preferred_theta, int constrained_mode,
+                                 const double* previous_sol_host, const double* previous_rows, const double* current_joints,
+                                 double orbita3d_max_angle, double* joints, uint8_t* reachable, uint8_t* state, uint8_t* emergency) {
+    const std::string w(who);
+    if (n < 0) return fail(ctx, RSIK_E_INVALID, w + ": n < 0");
+    if (nb_search_points < 2) return fail(ctx, RSIK_E_INVALID, w + ": nb_search_points must be >= 2");
     if (constrained_mode != RSIK_MODE_UNCONSTRAINED && constrained_mode != RSIK_MODE_LOW_ELBOW)
-        return fail(ctx, RSIK_E_INVALID, "rsik_control_discrete: unknown constrained_mode");
-    if (!previous_sol_host) return fail(ctx, RSIK_E_INVALID, "rsik_control_discrete: previous_sol_host is NULL");
-    int rc = check_arms(ctx, arm, arm_uniform, "rsik_control_discrete");
+        return fail(ctx, RSIK_E_INVALID, w + ": unknown constrained_mode");
+    if (!previous_sol_host && !previous_rows) return fail(ctx, RSIK_E_INVALID, w + ": previous_sol_host is NULL");
+    int rc = check_arms(ctx, arm, arm_uniform, who);
     if (rc != RSIK_OK) return rc;
     if (n == 0) return RSIK_OK;
-    if (!m12_soa || !joints) return fail(ctx, RSIK_E_INVALID, "rsik_control_discrete: m12_soa / joints is NULL");
+    if (!m12_soa || !joints) return fail(ctx, RSIK_E_INVALID, w + ": m12_soa / joints is NULL");
     rsik::DiscreteArgs K;
     K.n = n;
     for (int k = 0; k < 12; k++) {
-        if (!m12_soa[k]) return fail(ctx, RSIK_E_INVALID, "rsik_control_discrete: an m12_soa column is NULL");
+        if (!m12_soa[k]) return fail(ctx, RSIK_E_INVALID, w + ": an m12_soa column is NULL");
         K.in[k] = m12_soa[k];
     }
     K.arm = arm;
@@ -438,14 +480,17 @@ int rsik_control_discrete(rsik_ctx* ctx, int64_t n, const double* const m12_soa[
         control_limits(a, constrained_mode, preferred_theta, K.lim[slot], &K.pref[slot]);
         K.pref_cs[slot] = std::cos(K.pref[slot]);  // np.cos / np.sin of the reference (U:359-360), once per launch
         K.pref_sn[slot] = std::sin(K.pref[slot]);
-        for (int k = 0; k < 7; k++) K.prev_sol[slot][k] = previous_sol_host[7 * a + k];
-        for (int k = 0; k < 3; k++) {
-            K.prev_cs[slot][k] = std::cos(K.prev_sol[slot][4 + k]);
-            K.prev_sn[slot][k] = std::sin(K.prev_sol[slot][4 + k]);
+        if (previous_sol_host) {  // (the PREV_ROWS kernels read neither: prev_rows takes prev_sol's bytes, prev_cs / prev_sn stay unset)
+            for (int k = 0; k < 7; k++) K.prev_sol[slot][k] = previous_sol_host[7 * a + k];
+            for (int k = 0; k < 3; k++) {
+                K.prev_cs[slot][k] = std::cos(K.prev_sol[slot][4 + k]);
+                K.prev_sn[slot][k] = std::sin(K.prev_sol[slot][4 + k]);
+            }
         }
         K.arms[slot] = ctx->arms[a];
     }
     const bool plane_binds = singularity_plane_binds(K.arms);
+    if (previous_rows) K.prev_rows = previous_rows;  // (shares its kernarg bytes with K.prev_sol)
     K.current_joints = current_joints;
     K.max_angle = orbita3d_max_angle;
     K.cos_max = std::cos(orbita3d_max_angle);
@@ -453,17 +498,33 @@ int rsik_control_discrete(rsik_ctx* ctx, int64_t n, const double* const m12_soa[
     K.joints = joints; K.reachable = reachable; K.state = state; K.emergency = emergency;
     RSIK_HIP(ctx, hipSetDevice(ctx->device));
     dim3 grid, block(rsik::kDiscBlock);
-    rc = launch_dims(ctx, n, &grid, "rsik_control_discrete", rsik::kDiscBlock);
+    rc = launch_dims(ctx, n, &grid, who, rsik::kDiscBlock);
     if (rc != RSIK_OK) return rc;
-    if (arm) {
-        if (plane_binds) hipLaunchKernelGGL((rsik::control_discrete_kernel<true, true>), grid, block, 0, ctx->stream, K);
-        else hipLaunchKernelGGL((rsik::control_discrete_kernel<true, false>), grid, block, 0, ctx->stream, K);
-    } else {
-        if (plane_binds) hipLaunchKernelGGL((rsik::control_discrete_kernel<false, true>), grid, block, 0, ctx->stream, K);
-        else hipLaunchKernelGGL((rsik::control_discrete_kernel<false, false>), grid, block, 0, ctx->stream, K);
-    }
+    if (previous_rows) launch_discrete<true>(arm != nullptr, plane_binds, grid, block, ctx->stream, K);
+    else launch_discrete<false>(arm != nullptr, plane_binds, grid, block, ctx->stream, K);
     RSIK_HIP(ctx, hipGetLastError());
     return RSIK_OK;
+}
+
+int rsik_control_discrete(rsik_ctx* ctx, int64_t n, const double* const m12_soa[12], const uint8_t* arm,
+                          int arm_uniform, int nb_search_points, double preferred_theta, int constrained_mode,
+                          const double* previous_sol_host, const double* current_joints, double orbita3d_max_angle,
+                          double* joints, uint8_t* reachable, uint8_t* state, uint8_t* emergency) {
+    if (!ctx) return RSIK_E_INVALID;
+    return control_discrete_impl(ctx, "rsik_control_discrete", n, m12_soa, arm, arm_uniform, nb_search_points, preferred_theta,
+                                 constrained_mode, previous_sol_host, nullptr, current_joints, orbita3d_max_angle, joints,
+                                 reachable, state, emergency);
+}
+
+int rsik_control_discrete_rows(rsik_ctx* ctx, int64_t n, const double* const m12_soa[12], const uint8_t* arm,
+                               int arm_uniform, int nb_search_points, double preferred_theta, int constrained_mode,
+                               const double* previous_sol, const double* current_joints, double orbita3d_max_angle,
+                               double* joints, uint8_t* reachable, uint8_t* state, uint8_t* emergency) {
+    if (!ctx) return RSIK_E_INVALID;
+    if (!previous_sol) return fail(ctx, RSIK_E_INVALID, "rsik_control_discrete_rows: previous_sol is NULL");
+    return control_discrete_impl(ctx, "rsik_control_discrete_rows", n, m12_soa, arm, arm_uniform, nb_search_points,
+                                 preferred_theta, constrained_mode, nullptr, previous_sol, current_joints, orbita3d_max_angle,
+                                 joints, reachable, state, emergency);
 }
 
 // Arguments shared by the continuous-mode launches (validated once).

@@ -257,6 +257,8 @@ class SymbolicIK:
 
         poses: [n,2,3] or SoA [6,n].  theta: "interval0" (the reference's README/benchmark convention),
         "none" (reachability only), ("explicit", tensor[n]) or ("fraction", tensor[n]).
+        previous_joints: (7,) for every pose, or (n, 7): one get_joints previous_joints per pose (n independent callers in
+        one launch, rsik_solve_rows).
         Returns device tensors: joints [n,7], interval [n,2], elbow [n,3], reachable [n] u8, state [n] u8.
         """
         soa = poses_to_soa(poses, self._solver.device)
@@ -267,8 +269,10 @@ class SymbolicIK:
             policy = _THETA_POLICIES[theta[0]]
             theta_in = theta[1]
         self._upload()
+        previous_joints, rows = _split_previous_joints(previous_joints)
         return self._solver.solve(soa, arm_uniform=self.arm_id, theta_policy=policy, theta_in=theta_in,
-                                  previous_joints=previous_joints, want_elbow=want_elbow, out=out, plan_only=plan_only)
+                                  previous_joints=previous_joints, want_elbow=want_elbow, out=out, plan_only=plan_only,
+                                  previous_joints_rows=rows)
 
     def is_reachable_batch(self, poses: Any) -> Dict[str, torch.Tensor]:
         return self.solve_batch(poses, theta="none")
@@ -350,6 +354,17 @@ class SymbolicIK:
         return [STATE_STRINGS[int(k)] for k in c]
 
 
+def _split_previous_joints(previous_joints: Any):
+    """solve_batch's previous_joints: None or (7,) -> the launch-uniform vector; a 2-D (n, 7) array -> one row per pose
+    (the backend checks n and raises ValueError before anything is launched).  Returns (uniform, rows)."""
+    if previous_joints is None:
+        return None, None
+    shape = tuple(previous_joints.shape) if hasattr(previous_joints, "shape") else np.shape(previous_joints)
+    if len(shape) == 2:
+        return None, previous_joints
+    return previous_joints, None
+
+
 class DualArmIK:
     """Mixed r/l batches in one launch (BASELINE config 4): two SymbolicIK objects sharing one device context, the arm
     of every pose given by a uint8 array (0 = r_arm, 1 = l_arm)."""
@@ -375,5 +390,6 @@ class DualArmIK:
             theta_in = theta[1]
         self.r_arm._upload()
         self.l_arm._upload()
+        previous_joints, rows = _split_previous_joints(previous_joints)
         return self._solver.solve(soa, arm=arm_ids, theta_policy=policy, theta_in=theta_in, previous_joints=previous_joints,
-                                  want_elbow=want_elbow, out=out, plan_only=plan_only)
+                                  want_elbow=want_elbow, out=out, plan_only=plan_only, previous_joints_rows=rows)
