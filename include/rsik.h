@@ -471,6 +471,12 @@ int rsik_control_continuous_release(rsik_ctx *ctx);
  *                                   singularity_offset, singularity_limit_coeff, elbow_singularity_position 3, the intersection circle its
  *                                   get_elbow_position argument reads (centre 3, radius, normal 3) -> found 0/1, theta, preferred worked 0/1
  *                                   (nb_search_points outside [0, 2^20] or not a number: an empty grid)
+ * and the rate limiter of the continuous mode, which the fused kernels carry inside (`arm` is not read):
+ *   RSIK_STAGE_TEND_TO_PREFERRED_THETA  tend_to_preferred_theta :115-127: previous_theta, d_theta_max, goal_theta -> reached 0/1, theta
+ *   RSIK_STAGE_BEST_CONTINUOUS_THETA2   get_best_continuous_theta2 :220-264: the 18 operands of RSIK_STAGE_BEST_DISCRETE_THETA, d_theta_max
+ *                                   -> reachable 0/1, theta, which text (0 = nothing found: the search's own text, 1 = "theta theta_goal
+ *                                   ok et proche" appended, 2 = "theta theta_goal ok mais loin" alone), "preferred_theta worked" 0/1 of the
+ *                                   search inside
  */
 #define RSIK_STAGE_POSE_IN_REACH 0
 #define RSIK_STAGE_WRIST_POSITION 1
@@ -489,7 +495,9 @@ int rsik_control_continuous_release(rsik_ctx *ctx);
 #define RSIK_STAGE_MULTITURN_SAFETY_CHECK 14
 #define RSIK_STAGE_CONTINUITY_CHECK 15
 #define RSIK_STAGE_BEST_DISCRETE_THETA 16
-#define RSIK_STAGE_COUNT 17
+#define RSIK_STAGE_TEND_TO_PREFERRED_THETA 17
+#define RSIK_STAGE_BEST_CONTINUOUS_THETA2 18
+#define RSIK_STAGE_COUNT 19
 int rsik_stage(rsik_ctx *ctx, int op, int64_t n, int arm, const double *in, int in_stride, double *out, int out_stride);
 
 /*
@@ -504,6 +512,9 @@ int rsik_stage(rsik_ctx *ctx, int op, int64_t n, int arm, const double *in, int 
  *   call's results and the updated state with one download), 24-30 joints of the last get_joints, 31 reserved.
  */
 #define RSIK_SOLVER_STATE_STRIDE 32
+/* how a goal is laid out where an entry point takes either form (rsik_theta_from_joints, rsik_fk_residual) */
+#define RSIK_GOAL_POSE6 0
+#define RSIK_GOAL_M12 1
 
 /* SymbolicIK.is_reachable (no_limits == 0, symbolic_ik.py:121-282) or is_reachable_no_limits
  * (no_limits != 0, symbolic_ik.py:85-119).  Only the fields the reference would have assigned are
@@ -517,6 +528,45 @@ int rsik_joints_from_state(rsik_ctx *ctx, int64_t n, double *solver_state, const
                            const double *theta, const double *previous_joints, double *joints, double *elbow);
 /* SymbolicIK.get_elbow_position(theta) on stored state (symbolic_ik.py:684-695). */
 int rsik_elbow_from_state(rsik_ctx *ctx, int64_t n, const double *solver_state, const double *theta, double *elbow);
+
+/*
+ * rsik_theta_from_joints — "which theta puts this arm nearest to these joints", for n independent rows (n robots, n planner seeds,
+ * n restarted trajectories): what every caller of the reference does when it starts or restarts an arm (ControlIK.__init__
+ * control_ik.py:142-158, the continuous start-up :306-325).  Per row: SymbolicIK.is_reachable_no_limits on the goal
+ * (symbolic_ik.py:85-119), then utils.get_best_theta_to_current_joints (utils.py:267-331) with the reference's own sequence of
+ * get_joints evaluations — the preferred theta first (within 0.01 of the joints: that theta is the answer), then the ternary
+ * search over [-pi, pi] (r) / [0, 2 pi] (l), two evaluations per iteration, and one more at the mid point of the last bracket;
+ * each evaluation moves the row's solver state where the elbow projection fires, as the reference's does.  The result is the
+ * theta a timed-out rsik_control_continuous_step finds for the same current pose and joints, bit for bit.
+ *
+ *   goal_kind / goal_soa   RSIK_GOAL_POSE6: 6 device arrays of n doubles (the layout of rsik_solve); RSIK_GOAL_M12: 12 (the layout
+ *                          of rsik_control_discrete; RSIK_OPT_EULER_ROUNDTRIP applies as there) — the pose the arm is in
+ *   arm / arm_uniform      as rsik_solve
+ *   current_joints         [n,7] device, row-major: the joints each arm measured
+ *   preferred_theta_host   2 doubles (host): the preferred theta of r and of l (they differ: control_ik.py:136-140), used as given
+ *   theta                  [n]: the theta found
+ *   joints                 [n,7] or NULL: the joints of the last evaluation (utils.py:324; the preferred theta's for a shortcut row)
+ *   bracket                [n,2] or NULL: the search's final low, high (the reference's returned text carries them); NaN for a
+ *                          shortcut row
+ *   distance               [n] or NULL: the search's objective at the returned theta — the norm of the seven angle_diffs between the
+ *                          returned joints and current_joints — so that a caller can refuse a poor match
+ *   state                  [n] uint8 or NULL: RSIK_STATE_REACHABLE; RSIK_STATE_NOT_REACHABLE_NO_LIMITS where is_reachable_no_limits
+ *                          fails (outputs NaN); RSIK_STATE_INVALID_INPUT where the goal or the row's current joints hold a NaN or an
+ *                          infinity (outputs NaN, no other row is touched: "Rows that are not numbers" above)
+ * n == 0 launches nothing.  Enqueued on the context's stream; never waits for the device.
+ */
+int rsik_theta_from_joints(rsik_ctx *ctx, int64_t n, int goal_kind, const double *const *goal_soa, const uint8_t *arm,
+                           int arm_uniform, const double *current_joints, const double *preferred_theta_host, double *theta,
+                           double *joints, double *bracket, double *distance, uint8_t *state);
+/* The drop-in call shape: utils.get_best_theta_to_current_joints(get_joints, ...) with the bound get_joints of a solver object.
+ * Runs the same search on stored solver-state rows (as rsik_joints_from_state does, after rsik_reach_state) and leaves each row
+ * as the reference leaves `self` after those get_joints calls: slots 0-2 and 6-8 moved by every projection that fired, slots
+ * 16-19 and 24-30 of the last evaluation.  current_joints is [n, n_current], n_current = 7, or 14 for the list-of-both-arms form
+ * ControlIK.__init__ hands over (control_ik.py:152-158: joints 0 and 1 are compared against all seven entries of the r list and
+ * of the l list).  theta [n]; bracket [n,2] or NULL.  Works on pinned host rows like the other state entry points. */
+int rsik_theta_from_joints_state(rsik_ctx *ctx, int64_t n, double *solver_state, const uint8_t *arm, int arm_uniform,
+                                 const double *current_joints, int n_current, const double *preferred_theta_host,
+                                 double *theta, double *bracket);
 
 /* utils.get_euler_from_homogeneous_matrix for a batch (utils.py:84-90): goal matrices (m12_soa, layout as
  * rsik_control_discrete) -> pose_soa = 6 device arrays px,py,pz,roll,pitch,yaw (the input layout of rsik_solve),
@@ -534,8 +584,6 @@ int rsik_forward_kinematics(rsik_ctx *ctx, int64_t n, const double *joints, cons
 /* FK(joints) against the goal it was solved for: err[n,2] = (|position error| in m, rotation error in rad).
  * goal_soa: 6 columns (px,py,pz,roll,pitch,yaw) for RSIK_GOAL_POSE6, 12 columns (R row-major, t) for RSIK_GOAL_M12.
  * Rows whose joints are NaN (unreachable poses) give NaN. */
-#define RSIK_GOAL_POSE6 0
-#define RSIK_GOAL_M12 1
 int rsik_fk_residual(rsik_ctx *ctx, int64_t n, int goal_kind, const double *const *goal_soa, const double *joints,
                      const uint8_t *arm, int arm_uniform, double *err);
 

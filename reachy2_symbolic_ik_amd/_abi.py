@@ -73,6 +73,8 @@ PROTOTYPES = {
     "rsik_elbow_from_state": (C.c_int, [_vp, C.c_int64, _vp, _vp, _vp]),
     "rsik_forward_kinematics": (C.c_int, [_vp, C.c_int64, _vp, _vp, C.c_int, _vp, _vp]),
     "rsik_fk_residual": (C.c_int, [_vp, C.c_int64, C.c_int, C.POINTER(_vp), _vp, _vp, C.c_int, _vp]),
+    "rsik_theta_from_joints": (C.c_int, [_vp, C.c_int64, C.c_int, C.POINTER(_vp), _vp, C.c_int, _vp, _dp, _vp, _vp, _vp, _vp, _vp]),
+    "rsik_theta_from_joints_state": (C.c_int, [_vp, C.c_int64, _vp, _vp, C.c_int, _vp, C.c_int, _dp, _vp, _vp]),
     "rsik_debug_math": (C.c_int, [_vp, C.c_int, C.c_int64, _vp, _vp, _vp, _vp]),
     "rsik_comm_unique_id": (C.c_int, [_vp]),
     "rsik_comm_init_rank": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.POINTER(_vp)]),
@@ -83,9 +85,10 @@ PROTOTYPES = {
 GOAL_POSE6, GOAL_M12 = 0, 1
 (STAGE_POSE_IN_REACH, STAGE_WRIST_POSITION, STAGE_LIMITATION_CIRCLE, STAGE_INTERSECTION_CIRCLE, STAGE_CIRCLES_LINKED, STAGE_NEAREST_APPROACH,
  STAGE_CIRCLE_LINE, STAGE_ROTATION_FROM_VECTOR, STAGE_ANGLE_DIFF, STAGE_IS_VALID_ANGLE, STAGE_LIMIT_THETA_TO_INTERVAL, STAGE_IS_ELBOW_OK,
- STAGE_ALLOW_MULTITURN, STAGE_LIMIT_ORBITA3D_JOINTS, STAGE_MULTITURN_SAFETY_CHECK, STAGE_CONTINUITY_CHECK, STAGE_BEST_DISCRETE_THETA) = range(17)
+ STAGE_ALLOW_MULTITURN, STAGE_LIMIT_ORBITA3D_JOINTS, STAGE_MULTITURN_SAFETY_CHECK, STAGE_CONTINUITY_CHECK, STAGE_BEST_DISCRETE_THETA,
+ STAGE_TEND_TO_PREFERRED_THETA, STAGE_BEST_CONTINUOUS_THETA2) = range(19)
 STAGE_ROW = {0: (6, 5), 1: (6, 3), 2: (6, 7), 3: (3, 8), 4: (17, 3), 5: (12, 7), 6: (10, 7), 7: (3, 9),  # doubles in / out per row
-             8: (2, 1), 9: (3, 1), 10: (4, 2), 11: (9, 1), 12: (14, 7), 13: (4, 3), 14: (10, 8), 15: (21, 8), 16: (18, 3)}
+             8: (2, 1), 9: (3, 1), 10: (4, 2), 11: (9, 1), 12: (14, 7), 13: (4, 3), 14: (10, 8), 15: (21, 8), 16: (18, 3), 17: (3, 2), 18: (19, 4)}
 STAGE_IN_MAX, STAGE_OUT_MAX = 21, 9
 OPT_EULER_ROUNDTRIP, OPT_SWEEP_MODE, OPT_NO_TIPZ, OPT_NO_MIRROR, OPT_CONT_RUN_MODE = 0, 1, 2, 3, 4
 OPT_CONT_BLOCK_STEPS, OPT_CONT_PHASED_VARIANT, OPT_CONT_GOALS_RESIDENT = 5, 6, 7
@@ -98,6 +101,7 @@ CONT_RUN_AUTO, CONT_RUN_PHASED, CONT_RUN_STEPS = 0, 1, 2
 EMERGENCY_SHOULDER_PITCH, EMERGENCY_ELBOW_YAW, EMERGENCY_WRIST_YAW, EMERGENCY_CONTINUITY = 1, 2, 4, 8
 EULER_AUTO, EULER_ALWAYS, EULER_NEVER = 0, 1, 2
 
+STATE_REACHABLE = 0
 STATE_EMERGENCY, STATE_NOT_REACHABLE_NO_LIMITS, STATE_INVALID_INPUT = 8, 9, 10
 SOLVER_STATE_STRIDE = 32
 CONT_STATE_ROWS = 19

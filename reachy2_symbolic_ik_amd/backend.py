@@ -464,6 +464,84 @@ class HipSolver:
             self._check(self.lib.rsik_elbow_from_state(self._h, n, _ptr(solver_state), _ptr(theta), _ptr(elbow)))
         return elbow
 
+    # ------------------------------------------------------------------ rsik_theta_from_joints
+    def theta_from_joints(
+        self,
+        goal_soa: torch.Tensor,
+        current_joints: torch.Tensor,
+        preferred_theta: Sequence[float],
+        arm: Optional[torch.Tensor] = None,
+        arm_uniform: int = 0,
+        want: Sequence[str] = ("joints", "bracket", "distance", "state"),
+        out: Optional[Dict[str, torch.Tensor]] = None,
+        plan_only: bool = False,
+    ) -> Dict[str, torch.Tensor]:
+        """For n independent rows, the theta of the elbow circle whose solution is closest to the row's measured joints
+        (utils.get_best_theta_to_current_joints after is_reachable_no_limits: what a caller of the reference does when it
+        starts or restarts an arm).  goal_soa: [6, n] poses (px,py,pz,roll,pitch,yaw) or [12, n] matrices (R row-major, t):
+        the pose each arm is in.  current_joints: [n, 7].  preferred_theta: 2 values, r and l, used as given.
+        Returns theta [n] and, as named in `want`, joints [n,7] (of the last evaluation), bracket [n,2] (the final low, high;
+        NaN where the preferred theta itself matched), distance [n] (the objective at theta), state [n] u8.  Asynchronous on
+        the current stream; nothing is allocated when every output is in `out`, so the call can be captured into a graph."""
+        if not isinstance(goal_soa, torch.Tensor) or goal_soa.dim() != 2 or goal_soa.shape[0] not in (6, 12):
+            raise ValueError("goal_soa must have shape [6, n] or [12, n]")
+        rows, n = int(goal_soa.shape[0]), int(goal_soa.shape[1])
+        if goal_soa.dtype != _F64:
+            raise ValueError(f"goal_soa must be float64, got {goal_soa.dtype}")
+        goal_soa = self._dev_cols(goal_soa, rows, n, "goal_soa")
+        if isinstance(current_joints, torch.Tensor) and current_joints.dtype != _F64:
+            raise ValueError(f"current_joints must be float64, got {current_joints.dtype}")
+        current_joints = self._dev_f64(current_joints, (n, 7), "current_joints")
+        if arm is not None:
+            arm = self._dev_u8(arm, n, "arm")
+        pts = np.ascontiguousarray(preferred_theta, dtype=np.float64)
+        if pts.shape != (2,):
+            raise ValueError("preferred_theta must have 2 entries (r, l)")
+        unknown = set(want) - {"joints", "bracket", "distance", "state"}
+        if unknown:
+            raise ValueError(f"unknown outputs {sorted(unknown)}")
+        res = {"theta": self._out_buf(out, "theta", (n,), _F64)}
+        for key, shape, dt in (("joints", (n, 7), _F64), ("bracket", (n, 2), _F64), ("distance", (n,), _F64), ("state", (n,), _U8)):
+            if key in want:
+                res[key] = self._out_buf(out, key, shape, dt)
+        cols = (C.c_void_p * rows)(*[goal_soa[k].data_ptr() for k in range(rows)])
+        kind = _abi.GOAL_M12 if rows == 12 else _abi.GOAL_POSE6
+        cargs = (n, kind, cols, _ptr(arm), int(arm_uniform), _ptr(current_joints), pts.ctypes.data_as(C.POINTER(C.c_double)),
+                 _ptr(res["theta"]), _ptr(res.get("joints")), _ptr(res.get("bracket")), _ptr(res.get("distance")), _ptr(res.get("state")))
+        if plan_only:
+            res["launch"] = self.plan("rsik_theta_from_joints", *cargs)
+            res["_keepalive"] = (goal_soa, current_joints, arm, cols, pts)
+        else:
+            with torch.cuda.device(self.device):
+                self._bind_stream()
+                self._check(self.lib.rsik_theta_from_joints(self._h, *cargs))
+        return res
+
+    def theta_from_joints_state(self, solver_state: torch.Tensor, current_joints: torch.Tensor, preferred_theta: Sequence[float],
+                                arm: Optional[torch.Tensor] = None, arm_uniform: int = 0) -> Dict[str, torch.Tensor]:
+        """The same search on stored solver-state rows (after reach_state), each row left as the reference leaves `self`
+        (rsik_theta_from_joints_state).  current_joints: [n, 7], or [n, 14] for the list-of-both-arms form of ControlIK.__init__.
+        Returns theta [n], bracket [n, 2]."""
+        n = int(solver_state.shape[0]) if isinstance(solver_state, torch.Tensor) and solver_state.dim() == 2 else -1
+        self._check_state(solver_state, n)
+        width = int(current_joints.shape[1]) if getattr(current_joints, "ndim", 0) == 2 else -1
+        if width not in (7, 14):
+            raise ValueError("current_joints must have shape [n, 7] or [n, 14]")
+        current_joints = self._dev_f64(current_joints, (n, width), "current_joints")
+        if arm is not None:
+            arm = self._dev_u8(arm, n, "arm")
+        pts = np.ascontiguousarray(preferred_theta, dtype=np.float64)
+        if pts.shape != (2,):
+            raise ValueError("preferred_theta must have 2 entries (r, l)")
+        theta = torch.empty((n,), dtype=_F64, device=self.device)
+        bracket = torch.empty((n, 2), dtype=_F64, device=self.device)
+        with torch.cuda.device(self.device):
+            self._bind_stream()
+            self._check(self.lib.rsik_theta_from_joints_state(self._h, n, _ptr(solver_state), _ptr(arm), int(arm_uniform),
+                                                              _ptr(current_joints), width, pts.ctypes.data_as(C.POINTER(C.c_double)),
+                                                              _ptr(theta), _ptr(bracket)))
+        return {"theta": theta, "bracket": bracket}
+
     def stage(self, op: int, rows: torch.Tensor, arm_uniform: int = 0) -> torch.Tensor:
         """rsik_stage: one stage of SymbolicIK.is_reachable (include/rsik.h RSIK_STAGE_*) on explicit operands, row by row.
         rows: [n, doubles the stage reads] float64 on the device (or pinned host memory); returns [n, doubles it writes]."""

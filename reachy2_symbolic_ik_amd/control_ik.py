@@ -381,10 +381,39 @@ class ControlIK:
         return out
 
     # ------------------------------------------------------------------ MI355X-native batch API
-    def new_continuous_state(self, name: Any, n: int) -> torch.Tensor:
+    def start_theta_batch(self, name: Any, current_pose: Any, current_joints: Any,
+                          out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+        """The start theta of n arms at once: for every row is_reachable_no_limits(current_pose) and the theta whose solution is
+        closest to current_joints (utils.get_best_theta_to_current_joints with this object's preferred_theta of the row's arm) —
+        what the continuous start-up (control_ik.py:306-325) computes for one arm.  name: "r_arm" / "l_arm" or [n] uint8 arm ids;
+        current_pose: [n,4,4] or packed [12,n]; current_joints: [n,7].  Returns device tensors theta [n], joints [n,7],
+        bracket [n,2], distance [n], state [n] u8 (HipSolver.theta_from_joints)."""
+        m12 = matrices_to_m12_soa(current_pose, self._solver.device)
+        arm_t, arm_uniform = (None, ARM_IDS[name]) if isinstance(name, str) else (name, 0)
+        pts = [self.preferred_theta.get("r_arm", -4 * np.pi / 6), self.preferred_theta.get("l_arm", -np.pi + 4 * np.pi / 6)]
+        self._upload_arms()
+        return self._solver.theta_from_joints(m12, current_joints, pts, arm=arm_t, arm_uniform=arm_uniform, out=out)
+
+    def new_continuous_state(self, name: Any, n: int, current_joints: Any = None, current_pose: Any = None) -> torch.Tensor:
         """Per-trajectory state [RSIK_CONT_STATE_ROWS, n] initialised like a freshly constructed ControlIK (control_ik.py:133-160):
-        previous_theta / previous_sol of the arm(s), init = True, no emergency stop."""
+        previous_theta / previous_sol of the arm(s), init = True, no emergency stop.
+        With current_joints [n,7] AND current_pose ([n,4,4] or [12,n]) every trajectory starts from its own measured joints:
+        previous_sol = its current_joints and previous_theta = its own start theta (start_theta_batch) — the state a first step
+        with timed_out = 1 and the same current_joints / current_pose would (re)initialise, so that step needs neither."""
+        if (current_joints is None) != (current_pose is None):
+            raise ValueError("new_continuous_state: current_joints and current_pose go together")
         st = self._solver.new_continuous_state(n)
+        if current_joints is not None:
+            cj = self._solver._dev_f64(current_joints, (n, 7), "current_joints")
+            arm_t, arm_uniform = (None, ARM_IDS[name]) if isinstance(name, str) else (name, 0)
+            pts = [self.preferred_theta.get("r_arm", -4 * np.pi / 6), self.preferred_theta.get("l_arm", -np.pi + 4 * np.pi / 6)]
+            self._upload_arms()
+            self._solver.theta_from_joints(matrices_to_m12_soa(current_pose, self._solver.device), cj, pts, arm=arm_t,
+                                           arm_uniform=arm_uniform, want=(), out={"theta": st[0]})
+            st[1:8].copy_(cj.t())
+            st[8].fill_(1.0)
+            st[10].fill_(1.0)
+            return st
         if isinstance(name, str):
             arm_ids = np.full(n, ARM_IDS[name], dtype=np.int64)
         else:

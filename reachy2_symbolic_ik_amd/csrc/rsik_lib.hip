@@ -27,6 +27,7 @@
 #include "rsik_kernel_pipeline.hpp"
 #include "rsik_kernel_state.hpp"
 #include "rsik_kernel_stages.hpp"
+#include "rsik_kernel_theta_from_joints.hpp"
 
 // =====================================================================================
 // C ABI
@@ -1318,12 +1319,93 @@ int rsik_elbow_from_state(rsik_ctx* ctx, int64_t n, const double* solver_state, 
     return RSIK_OK;
 }
 
+// utils.get_best_theta_to_current_joints for n rows (rsik_kernel_theta_from_joints.hpp)
+static int fill_theta_from_joints(rsik_ctx* ctx, const char* who, rsik::ThetaFromJointsArgs& K, int64_t n, const uint8_t* arm,
+                                  int arm_uniform, const double* preferred_theta_host) {
+    int rc = check_arms(ctx, arm, arm_uniform, who);
+    if (rc != RSIK_OK) return rc;
+    std::memset(&K, 0, sizeof K);
+    K.n = n;
+    K.arm = arm;
+    K.euler_roundtrip = ctx->options[RSIK_OPT_EULER_ROUNDTRIP];
+    for (int slot = 0; slot < 2; slot++) {
+        const int a = arm ? slot : arm_uniform;
+        K.pref[slot] = preferred_theta_host ? preferred_theta_host[a] : 0.0;
+        K.arms[slot] = ctx->arms[a];
+    }
+    return RSIK_OK;
+}
+
+int rsik_theta_from_joints(rsik_ctx* ctx, int64_t n, int goal_kind, const double* const* goal_soa, const uint8_t* arm,
+                           int arm_uniform, const double* current_joints, const double* preferred_theta_host, double* theta,
+                           double* joints, double* bracket, double* distance, uint8_t* state) {
+    const char* who = "rsik_theta_from_joints";
+    if (!ctx) return RSIK_E_INVALID;
+    if (n < 0) return fail(ctx, RSIK_E_INVALID, std::string(who) + ": n < 0");
+    if (goal_kind != RSIK_GOAL_POSE6 && goal_kind != RSIK_GOAL_M12)
+        return fail(ctx, RSIK_E_INVALID, std::string(who) + ": goal_kind must be RSIK_GOAL_POSE6 or RSIK_GOAL_M12");
+    rsik::ThetaFromJointsArgs K;
+    int rc = fill_theta_from_joints(ctx, who, K, n, arm, arm_uniform, preferred_theta_host);
+    if (rc != RSIK_OK) return rc;
+    if (n == 0) return RSIK_OK;
+    if (!goal_soa || !current_joints || !preferred_theta_host || !theta)
+        return fail(ctx, RSIK_E_INVALID, std::string(who) + ": goal_soa / current_joints / preferred_theta_host / theta is NULL");
+    const bool m12 = goal_kind == RSIK_GOAL_M12;
+    for (int k = 0; k < (m12 ? 12 : 6); k++) {
+        if (!goal_soa[k]) return fail(ctx, RSIK_E_INVALID, std::string(who) + ": a goal_soa column is NULL");
+        K.goal[k] = goal_soa[k];
+    }
+    K.current_joints = current_joints; K.n_current = 7;
+    K.theta = theta; K.joints = joints; K.bracket = bracket; K.distance = distance; K.state = state;
+    RSIK_HIP(ctx, hipSetDevice(ctx->device));
+    dim3 grid, block(rsik::kBlock);
+    rc = launch_dims(ctx, n, &grid, who);
+    if (rc != RSIK_OK) return rc;
+    // an arm byte per row: do the two blocks agree in everything that has no handedness (arm_const_is_sided)?
+    bool mirror = arm != nullptr && !ctx->options[RSIK_OPT_NO_MIRROR];
+    for (int i = 0; mirror && i < RSIK_ARM_CONSTS_COUNT; i++)
+        if (!rsik::arm_const_is_sided(i) && std::memcmp(&K.arms[0].v[i], &K.arms[1].v[i], sizeof(double)) != 0) mirror = false;
+    const int form = arm ? (mirror ? 2 : 1) : 0;
+#define RSIK_TFJ(F, G) hipLaunchKernelGGL((rsik::theta_from_joints_kernel<F, G>), grid, block, 0, ctx->stream, K)
+    if (form == 0) { if (m12) RSIK_TFJ(0, true); else RSIK_TFJ(0, false); }
+    else if (form == 1) { if (m12) RSIK_TFJ(1, true); else RSIK_TFJ(1, false); }
+    else { if (m12) RSIK_TFJ(2, true); else RSIK_TFJ(2, false); }
+#undef RSIK_TFJ
+    RSIK_HIP(ctx, hipGetLastError());
+    return RSIK_OK;
+}
+
+int rsik_theta_from_joints_state(rsik_ctx* ctx, int64_t n, double* solver_state, const uint8_t* arm, int arm_uniform,
+                                 const double* current_joints, int n_current, const double* preferred_theta_host,
+                                 double* theta, double* bracket) {
+    const char* who = "rsik_theta_from_joints_state";
+    if (!ctx) return RSIK_E_INVALID;
+    if (n < 0) return fail(ctx, RSIK_E_INVALID, std::string(who) + ": n < 0");
+    if (n_current != 7 && n_current != 14) return fail(ctx, RSIK_E_INVALID, std::string(who) + ": n_current must be 7 or 14");
+    rsik::ThetaFromJointsArgs K;
+    int rc = fill_theta_from_joints(ctx, who, K, n, arm, arm_uniform, preferred_theta_host);
+    if (rc != RSIK_OK) return rc;
+    if (n == 0) return RSIK_OK;
+    if (!solver_state || !current_joints || !preferred_theta_host || !theta)
+        return fail(ctx, RSIK_E_INVALID, std::string(who) + ": solver_state / current_joints / preferred_theta_host / theta is NULL");
+    K.solver_state = solver_state; K.current_joints = current_joints; K.n_current = n_current;
+    K.theta = theta; K.bracket = bracket;
+    RSIK_HIP(ctx, hipSetDevice(ctx->device));
+    dim3 grid, block(rsik::kBlock);
+    rc = launch_dims(ctx, n, &grid, who);
+    if (rc != RSIK_OK) return rc;
+    if (arm) hipLaunchKernelGGL(rsik::theta_from_joints_state_kernel<true>, grid, block, 0, ctx->stream, K);
+    else hipLaunchKernelGGL(rsik::theta_from_joints_state_kernel<false>, grid, block, 0, ctx->stream, K);
+    RSIK_HIP(ctx, hipGetLastError());
+    return RSIK_OK;
+}
+
 int rsik_stage(rsik_ctx* ctx, int op, int64_t n, int arm, const double* in, int in_stride, double* out, int out_stride) {
     const char* who = "rsik_stage";
     if (!ctx) return RSIK_E_INVALID;
     // doubles a row takes and gives, by stage (include/rsik.h)
-    static const int need_in[RSIK_STAGE_COUNT] = {6, 6, 6, 3, 17, 12, 10, 3, 2, 3, 4, 9, 14, 4, 10, 21, 18},
-                     need_out[RSIK_STAGE_COUNT] = {5, 3, 7, 8, 3, 7, 7, 9, 1, 1, 2, 1, 7, 3, 8, 8, 3};
+    static const int need_in[RSIK_STAGE_COUNT] = {6, 6, 6, 3, 17, 12, 10, 3, 2, 3, 4, 9, 14, 4, 10, 21, 18, 3, 19},
+                     need_out[RSIK_STAGE_COUNT] = {5, 3, 7, 8, 3, 7, 7, 9, 1, 1, 2, 1, 7, 3, 8, 8, 3, 2, 4};
     // (stages 5 on read no arm constant: they do not need an arm to have been set)
     if (op < 0 || op >= RSIK_STAGE_COUNT) return fail(ctx, RSIK_E_INVALID, std::string(who) + ": unknown stage");
     if (n < 0) return fail(ctx, RSIK_E_INVALID, std::string(who) + ": n < 0");
@@ -1346,7 +1428,8 @@ int rsik_stage(rsik_ctx* ctx, int op, int64_t n, int arm, const double* in, int 
     dim3 grid, block(rsik::kBlock);
     rc = launch_dims(ctx, n, &grid, who);
     if (rc != RSIK_OK) return rc;
-    hipLaunchKernelGGL(rsik::stage_kernel, grid, block, 0, ctx->stream, K);
+    if (op >= RSIK_STAGE_TEND_TO_PREFERRED_THETA) hipLaunchKernelGGL(rsik::stage_limiter_kernel, grid, block, 0, ctx->stream, K);
+    else hipLaunchKernelGGL(rsik::stage_kernel, grid, block, 0, ctx->stream, K);
     RSIK_HIP(ctx, hipGetLastError());
     return RSIK_OK;
 }

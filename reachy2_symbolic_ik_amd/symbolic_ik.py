@@ -172,6 +172,39 @@ class SymbolicIK:
             self.elbow_position = np.array([s[16], s[17], s[18], 1.0])
         return joints, self.elbow_position
 
+    def _theta_from_joints_scalar(self, current_joints: Any, preferred_theta: float) -> Tuple[float, float, float]:
+        """utils.get_best_theta_to_current_joints on this object's state row, one launch (rsik_theta_from_joints_state): the
+        row, and with it goal_pose / wrist_position / elbow_position, end up as the reference's ~35 get_joints calls leave them.
+        current_joints: 7 values, or the two lists of 7 that ControlIK.__init__ hands over (Q15).  Returns (theta, low, high);
+        low and high are NaN when the preferred theta itself matched."""
+        cj = np.asarray(current_joints, dtype=np.float64)
+        if cj.shape not in ((7,), (2, 7)):
+            raise ValueError("current_joints must hold 7 joints, or two lists of 7 (the constructor's form)")
+        io = self._scalar_io()
+        tj = io.get("tj")
+        if tj is None:
+            import ctypes as C
+
+            tj = io["tj"] = torch.zeros(14 + 3, dtype=torch.float64).pin_memory()
+            io["tj_np"] = tj.numpy()
+            io["tj_cur"], io["tj_theta"], io["tj_bracket"] = (C.c_void_p(tj.data_ptr()), C.c_void_p(tj.data_ptr() + 8 * 14),
+                                                              C.c_void_p(tj.data_ptr() + 8 * 15))
+            io["tj_pref"] = np.zeros(2)
+            io["tj_pref_p"] = io["tj_pref"].ctypes.data_as(C.POINTER(C.c_double))
+        io["tj_np"][:cj.size] = cj.reshape(-1)
+        io["tj_pref"][:] = preferred_theta
+        sv = self._solver
+        self._upload()
+        with torch.cuda.device(sv.device):
+            sv._bind_stream()
+            sv._check(sv.lib.rsik_theta_from_joints_state(
+                sv._h, 1, io["state"], None, self.arm_id, io["tj_cur"], int(cj.size),
+                io["tj_pref_p"], io["tj_theta"], io["tj_bracket"]))
+            s = self._finish(io)
+        self.elbow_position = s[16:19].copy() if s[19] != 0.0 else np.array([s[16], s[17], s[18], 1.0])
+        o = io["tj_np"]
+        return float(o[14]), float(o[15]), float(o[16])
+
     def get_elbow_position(self, theta: float) -> npt.NDArray[np.float64]:
         """symbolic_ik.py:684-695."""
         io = self._scalar_io()
@@ -274,6 +307,20 @@ class SymbolicIK:
                                   previous_joints=previous_joints, want_elbow=want_elbow, out=out, plan_only=plan_only,
                                   previous_joints_rows=rows)
 
+    def theta_from_joints_batch(self, poses: Any, current_joints: Any, preferred_theta: Optional[float] = None,
+                                out: Optional[Dict[str, torch.Tensor]] = None, plan_only: bool = False) -> Dict[str, torch.Tensor]:
+        """For every row, the theta whose solution is closest to that row's measured joints: is_reachable_no_limits(pose),
+        then utils.get_best_theta_to_current_joints — what a caller does before it starts or restarts an arm, for n arms in
+        one launch.  poses: [n,2,3] or SoA [6,n] (the pose each arm is in); current_joints: [n,7]; preferred_theta: tried
+        first (default: ControlIK's for this arm, -4 pi / 6 for r and its mirror image for l).
+        Returns device tensors theta [n], joints [n,7], bracket [n,2], distance [n], state [n] u8 (HipSolver.theta_from_joints)."""
+        soa = poses_to_soa(poses, self._solver.device)
+        if preferred_theta is None:
+            preferred_theta = default_preferred_theta(self.arm_id)
+        self._upload()
+        return self._solver.theta_from_joints(soa, current_joints, [float(preferred_theta)] * 2, arm_uniform=self.arm_id,
+                                              out=out, plan_only=plan_only)
+
     def is_reachable_batch(self, poses: Any) -> Dict[str, torch.Tensor]:
         return self.solve_batch(poses, theta="none")
 
@@ -354,6 +401,12 @@ class SymbolicIK:
         return [STATE_STRINGS[int(k)] for k in c]
 
 
+def default_preferred_theta(arm_id: int) -> float:
+    """ControlIK.preferred_theta of an arm (control_ik.py:133-139): -4 pi / 6 for r, -pi + 4 pi / 6 for l."""
+    base = -4 * np.pi / 6
+    return base if arm_id == 0 else -np.pi - base
+
+
 def _split_previous_joints(previous_joints: Any):
     """solve_batch's previous_joints: None or (7,) -> the launch-uniform vector; a 2-D (n, 7) array -> one row per pose
     (the backend checks n and raises ValueError before anything is launched).  Returns (uniform, rows)."""
@@ -393,3 +446,14 @@ class DualArmIK:
         previous_joints, rows = _split_previous_joints(previous_joints)
         return self._solver.solve(soa, arm=arm_ids, theta_policy=policy, theta_in=theta_in, previous_joints=previous_joints,
                                   want_elbow=want_elbow, out=out, plan_only=plan_only, previous_joints_rows=rows)
+
+    def theta_from_joints_batch(self, arm_ids: Any, poses: Any, current_joints: Any, preferred_theta: Optional[Sequence[float]] = None,
+                                out: Optional[Dict[str, torch.Tensor]] = None, plan_only: bool = False) -> Dict[str, torch.Tensor]:
+        """SymbolicIK.theta_from_joints_batch for rows of both arms (arm_ids [n] uint8).  preferred_theta: (r, l), default
+        ControlIK's pair."""
+        soa = poses_to_soa(poses, self._solver.device)
+        if preferred_theta is None:
+            preferred_theta = (default_preferred_theta(0), default_preferred_theta(1))
+        self.r_arm._upload()
+        self.l_arm._upload()
+        return self._solver.theta_from_joints(soa, current_joints, preferred_theta, arm=arm_ids, out=out, plan_only=plan_only)

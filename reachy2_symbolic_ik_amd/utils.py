@@ -7,9 +7,11 @@ message texts and the URDF reader (constants.py) are host code.
 The functions share one device context, created on first use on the current device (`set_default_solver` hands over another:
 an existing HipSolver, or a device index); calls are serialised by a lock, 20-30 us each (a launch and a stream synchronisation
 through pinned host rows: these are scalar utilities — batches go through `HipSolver.stage`).  Importing this module needs no GPU;
-calling a helper does.  Not provided: the matplotlib drawing helpers (show_*), dead code (get_best_continuous_theta,
-get_best_continuous_theta2 and tend_to_preferred_theta live inside the continuous control kernels and take closures that only
-exist there) — SURVEY section 2's out-of-scope lines.
+calling a helper does.  get_best_theta_to_current_joints runs its whole search (about 35 get_joints evaluations) in one launch on
+the state row of the solver whose get_joints it is handed (rsik_theta_from_joints_state); tend_to_preferred_theta and
+get_best_continuous_theta2, the continuous mode's rate limiter, are stages like the others.  Not provided: the matplotlib drawing
+helpers (show_*) and dead code (get_best_continuous_theta, which nothing in the reference calls) — SURVEY section 2's out-of-scope
+lines.
 """
 from __future__ import annotations
 
@@ -221,6 +223,75 @@ def get_best_discrete_theta(
     if o[0] != 0.0:
         return True, float(o[1]), state
     return False, previous_theta, state
+
+
+def tend_to_preferred_theta(
+    previous_theta: float,
+    interval: npt.NDArray[np.float64],
+    get_joints: Any,
+    d_theta_max: float,
+    goal_theta: float = -np.pi * 5 / 4,
+) -> Tuple[bool, float]:
+    """utils.py:115-127: goal_theta if it is within d_theta_max of previous_theta, else one step of d_theta_max towards it
+    (`interval` and `get_joints` are not used, as in the reference)."""
+    o = _stage(_abi.STAGE_TEND_TO_PREFERRED_THETA, previous_theta, d_theta_max, goal_theta)
+    if o[0] != 0.0:
+        return True, goal_theta
+    return False, float(o[1])
+
+
+def get_best_continuous_theta2(
+    previous_theta: float,
+    interval: npt.NDArray[np.float64],
+    get_elbow_position: Any,
+    nb_search_points: int,
+    d_theta_max: float,
+    preferred_theta: float,
+    arm: str,
+    singularity_offset: float,
+    singularity_limit_coeff: float,
+    elbow_singularity_position: npt.NDArray[np.float64],
+) -> Tuple[bool, float, str]:
+    """utils.py:220-264: get_best_discrete_theta's theta, approached by at most d_theta_max per call.  `get_elbow_position` is the
+    bound method of a SymbolicIK solver, as for get_best_discrete_theta."""
+    owner = getattr(get_elbow_position, "__self__", None)
+    circle = getattr(owner, "intersection_circle", None)
+    if circle is None:
+        raise TypeError("get_best_continuous_theta2: get_elbow_position must be the get_elbow_position method of a SymbolicIK solver "
+                        "(the search reads the solver's intersection_circle)")
+    side = -1 if arm == "l_arm" else 1
+    o = _stage(_abi.STAGE_BEST_CONTINUOUS_THETA2, previous_theta, interval[0], interval[1], nb_search_points, preferred_theta, side,
+               singularity_offset, singularity_limit_coeff, np.asarray(elbow_singularity_position, dtype=np.float64)[:3],
+               np.asarray(circle[0], dtype=np.float64)[:3], circle[1], np.asarray(circle[2], dtype=np.float64)[:3], d_theta_max)
+    state = f"{arm}" + "\n" + f"interval: {interval}, preferred_theta: {preferred_theta}"
+    if o[3] != 0.0:
+        state += "\n" + "preferred_theta worked!"
+    if o[0] == 0.0:
+        return False, previous_theta, state
+    if o[2] == 1.0:
+        return True, (preferred_theta if o[3] != 0.0 else float(o[1])), state + "\n" + "theta theta_goal ok et proche"
+    return True, float(o[1]), "\n" + "theta theta_goal ok mais loin"
+
+
+def get_best_theta_to_current_joints(
+    get_joints: Any, nb_search_points: int, current_joints: Any, arm: str, preferred_theta: float
+) -> Tuple[float, str]:
+    """utils.py:267-331: the theta of the whole circle whose joints are closest to current_joints — the preferred theta if it is
+    within 0.01, else a ternary search.  `get_joints` is the closure is_reachable / is_reachable_no_limits returned (the bound
+    get_joints of a SymbolicIK solver): the whole search, about 35 evaluations, runs in one launch on that solver's state, which
+    ends up as the reference's calls leave it (Q1).  current_joints: 7 values, or ControlIK.__init__'s two lists of 7 (Q15).
+    `arm` picks the bracket ([0, 2 pi] for "l_arm") in the reference; here the solver's own arm does, and the two must agree.
+    The returned text carries the bracket like the reference's (its joints / distance lines are debugging aids: not rebuilt)."""
+    owner = getattr(get_joints, "__self__", None)
+    if owner is None or not hasattr(owner, "_theta_from_joints_scalar"):
+        raise TypeError("get_best_theta_to_current_joints: get_joints must be the closure a SymbolicIK solver's is_reachable / "
+                        "is_reachable_no_limits returned (the search runs on that solver's state)")
+    if (arm == "l_arm") != (owner.arm == "l_arm"):
+        raise ValueError(f"get_best_theta_to_current_joints: arm is {arm!r} but the solver is a {owner.arm}")
+    theta, low, high = owner._theta_from_joints_scalar(current_joints, float(preferred_theta))
+    if low != low:  # NaN bracket: the preferred theta itself matched
+        return preferred_theta, "preferred_theta worked!"
+    return theta, f" \n low = {low}, high = {high}"
 
 
 def utils_on_device() -> Optional[Any]:
