@@ -263,12 +263,13 @@ __device__ __forceinline__ V3 frame_c0(V3 u) {
     }
     return c0;
 }
-__device__ __forceinline__ Frame frame_from_unit(V3 u) {
+// h = 1 / (1 + u_x): the caller that has it from elsewhere passes it in (reach_impl: one reciprocal square root serves the
+// circle's radius and this frame)
+__device__ __forceinline__ Frame frame_from_unit(V3 u, double h) {
     Frame F;
     // Rodrigues I + K + K^2 (1-c)/s^2 with v = e_x x u = (0, -u_z, u_y)
     // (1 - c) / s^2 = 1 / (1 + c) for a unit vector; well conditioned for the half space u_x > -1 + 1e-8 left by the
     // special cases below
-    double h = fast_rcp(1.0 + u.x);
     double yh = u.y * h, zh = u.z * h;
     double yzh = u.y * zh;
     F.c0 = u;
@@ -281,6 +282,7 @@ __device__ __forceinline__ Frame frame_from_unit(V3 u) {
     }
     return F;
 }
+__device__ __forceinline__ Frame frame_from_unit(V3 u) { return frame_from_unit(u, fast_rcp(1.0 + u.x)); }
 
 // Result of the is_reachable stage: what SymbolicIK leaves on `self` for get_joints (Q1).
 struct Reach {
@@ -449,22 +451,39 @@ __device__ Reach reach_impl(const Acc& A, V3 pos_in, const V3 woff, const NL no_
     V3 n2 = P * inv_d;
     double r2, ir2;  // radius and its reciprocal (0 for the degenerate circle)
     double kk;
+    double fh;       // 1 / (1 + n2.x) for the circle's frame (frame_from_unit)
     V3 c2;
     {
         double d2 = d * d, k = d2 - f * f + u * u;
         // [D] the radicand is exactly 0 for a fully extended arm (Q23) and must not become -1e-18 through an fma
         double rad = 4 * d2 * (u * u) - k * k;
         // radius = sqrt(rad) / (2 d) and its reciprocal from ONE reciprocal square root (sqrt(rad) = rad / sqrt(rad) to
-        // 1 - 2 ulp; the radius is not a decision value)
-        const double irad = (rad != 0.0) ? rsqrt_fast(rad) : 0.0;
+        // 1 - 2 ulp; the radius is not a decision value) — and the same one serves the frame's 1 / (1 + n2.x) = d / m with
+        // m = d + P.x: z = 1 / sqrt(rad m^2) gives 1 / sqrt(rad) = z m and 1 / m = z sqrt(rad).  A quarter-rate instruction
+        // holds its SIMD as long as four fp64 multiplies; this trades one of them and its correction for four multiplies.
+        // rad m^2 >= 1e-49 wherever rad > 0 and n2 is not the frame's colinear special case (rad >= an ulp of d^2 u^2,
+        // m >= 2e-16 d); what is left — the degenerate circle, n2 = -e_x exactly — takes the two separate operations.
+        const double m = d + P.x;
+        const double g = rad * (m * m);
+        double irad, srad;  // 1 / sqrt(rad), sqrt(rad)
+        if (RSIK_RARE(!(g > 0.0))) {
+            irad = (rad != 0.0) ? rsqrt_fast(rad) : 0.0;
+            srad = rad * irad;
+            fh = fast_rcp(1.0 + n2.x);
+        } else {
+            const double z = rsqrt_fast(g);
+            irad = z * m;
+            srad = rad * irad;
+            fh = d * (z * srad);
+        }
         const double hid = 0.5 * inv_d;
-        r2 = hid * (rad * irad);
+        r2 = hid * srad;
         ir2 = (d + d) * irad;
         kk = k * hid;  // distance of the circle's centre from the shoulder along n2
         c2 = s + n2 * kk;
     }
     RSIK_MARK("reach_frame");
-    Frame F2 = frame_from_unit(n2);
+    Frame F2 = frame_from_unit(n2, fh);
     r.c2 = c2; r.r2 = r2; r.n2 = n2; r.a1 = F2.c1; r.a2 = F2.c2;
     r.stage = 2;
     if (NO_LIMITS || GEOM_ONLY) {
@@ -525,11 +544,15 @@ __device__ Reach reach_impl(const Acc& A, V3 pos_in, const V3 woff, const NL no_
             if (disc < 0) { whole_or_nothing(); return r; }
             r.ok = true;
             r.state = RSIK_STATE_REACHABLE;
-            const double iR = rsqrt_fast(R2);
-            const double cphi = Ap * iR, sphi = Bp * iR;
-            const double cal = Dp * iR, sal = (disc * rsqrt_fast(disc)) * iR;
-            const double c0 = fma(cphi, cal, sphi * sal), s0 = fma(sphi, cal, -(cphi * sal));
-            const double c1 = fma(cphi, cal, -(sphi * sal)), s1 = fma(sphi, cal, cphi * sal);
+            // (cos, sin)(phi -+ alpha) = (A', B') (x) (D', -+sqrt(disc)) / R'^2: both vectors have length R' (disc = R'^2 - D'^2),
+            // so ONE reciprocal square root normalises the product.  z = 1 / (R'^2 sqrt(disc)):  sqrt(disc) / R'^2 = disc z,
+            // 1 / R'^2 = (R'^2 disc) z^2.  The guard above keeps R'^2 >= 1e-12 and disc >= 1e-8: R'^4 disc >= 1e-32.
+            const double rd = R2 * disc;
+            const double z = rsqrt_fast(R2 * rd);
+            const double sal = disc * z;              // sqrt(disc) / R'^2
+            const double cal = Dp * (rd * (z * z));   // D' / R'^2
+            const double c0 = fma(Ap, cal, Bp * sal), s0 = fma(Bp, cal, -(Ap * sal));
+            const double c1 = fma(Ap, cal, -(Bp * sal)), s1 = fma(Bp, cal, Ap * sal);
             const double ss[2] = {s0, s1}, cc[2] = {c0, c1};
             double aa[2];
             unit_atan2_n<2>(A.utab, ss, cc, aa);

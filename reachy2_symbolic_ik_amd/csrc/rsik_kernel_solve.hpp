@@ -236,6 +236,11 @@ __device__ __forceinline__ void flush_rows(double* __restrict__ out, int64_t wav
     __builtin_amdgcn_wave_barrier();
 }
 
+// A compiler-only memory fence at the end of a branch that stages a lane's outputs in LDS.  Without it the compiler sinks the
+// stores of the reachable and the unreachable branch into one sequence after the join and feeds it through ten register
+// pairs that it first fills with the other branch's value: nine v_mov_b64 executed by every wave, reachable or not.
+__device__ __forceinline__ void branch_stores_stay() { asm volatile("" ::: "memory"); }
+
 #ifndef RSIK_SOLVE_MIN_WAVES
 #define RSIK_SOLVE_MIN_WAVES 1
 #endif
@@ -314,6 +319,8 @@ __global__ __launch_bounds__(kBlock, RSIK_SOLVE_MIN_WAVES) void solve_kernel(con
 
     // joints [64,7] and elbow [64,3] of the wave are staged in LDS (row-major, as they go to HBM) by whichever branch
     // the lane takes, then written out with coalesced rows: failed poses only cost their NaN fill when one exists
+    // (the elbow rows only when the caller asked for them: a launch constant, every test of it a scalar branch)
+    const bool want_elbow = K.elbow != nullptr;
     if (K.theta_policy != RSIK_THETA_NONE) {
         double* jrow = lds_wave + lane * 7;
         double* erow = lds_wave + 64 * 7 + lane * 3;
@@ -337,13 +344,15 @@ __global__ __launch_bounds__(kBlock, RSIK_SOLVE_MIN_WAVES) void solve_kernel(con
                 RSIK_MARK("stores");
 #pragma unroll
                 for (int k = 0; k < 7; k++) jrow[k] = o.j[k];
-                erow[0] = o.elbow.x; erow[1] = o.elbow.y; erow[2] = o.elbow.z;
+                if (want_elbow) { erow[0] = o.elbow.x; erow[1] = o.elbow.y; erow[2] = o.elbow.z; }
+                branch_stores_stay();
             } else {
                 JointsOut o = joints_from_theta_g<true, TIPZ>(A, r, G, ct, st, (const double*)K.prev);
                 RSIK_MARK("stores");
 #pragma unroll
                 for (int k = 0; k < 7; k++) jrow[k] = o.j[k];
-                erow[0] = o.elbow.x; erow[1] = o.elbow.y; erow[2] = o.elbow.z;
+                if (want_elbow) { erow[0] = o.elbow.x; erow[1] = o.elbow.y; erow[2] = o.elbow.z; }
+                branch_stores_stay();
             }
         } else {
             // (`opaque`: the value is made inside this branch — otherwise the compiler merges the two branches' LDS writes and
@@ -351,7 +360,8 @@ __global__ __launch_bounds__(kBlock, RSIK_SOLVE_MIN_WAVES) void solve_kernel(con
             const double nan = opaque(__builtin_nan(""));
 #pragma unroll
             for (int k = 0; k < 7; k++) jrow[k] = nan;
-            erow[0] = nan; erow[1] = nan; erow[2] = nan;
+            if (want_elbow) { erow[0] = nan; erow[1] = nan; erow[2] = nan; }
+            branch_stores_stay();
         }
 #ifdef RSIK_TIMELINE_PROBE
         probe_mid = __builtin_amdgcn_s_memrealtime();  // all arithmetic done, outputs staged in LDS
@@ -359,10 +369,10 @@ __global__ __launch_bounds__(kBlock, RSIK_SOLVE_MIN_WAVES) void solve_kernel(con
         const int64_t wave_base = tile0 + wave * 64;
         if (rows >= (unsigned)(wave * 64 + 64)) {  // the wave's 64 rows all exist (wave-uniform, scalar)
             if (K.joints) flush_rows_full<7>(K.joints, wave_base, lane, lds_wave);
-            if (K.elbow) flush_rows_full<3>(K.elbow, wave_base, lane, lds_wave + 64 * 7);
+            if (want_elbow) flush_rows_full<3>(K.elbow, wave_base, lane, lds_wave + 64 * 7);
         } else if (rows > (unsigned)(wave * 64)) {
             if (K.joints) flush_rows<7>(K.joints, wave_base, K.n, lane, lds_wave);
-            if (K.elbow) flush_rows<3>(K.elbow, wave_base, K.n, lane, lds_wave + 64 * 7);
+            if (want_elbow) flush_rows<3>(K.elbow, wave_base, K.n, lane, lds_wave + 64 * 7);
         }
     }
     if (live) {

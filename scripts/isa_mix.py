@@ -7,7 +7,10 @@
 
 Classes: fp64 arithmetic (add / mul / fma / fmac / min / max / rndne / floor / fract ...), fp64 transcendental seeds
 (v_rcp / v_rsq / v_sqrt _f64), fp64 compares, selects (v_cndmask), conversions, 64-bit moves, 32-bit moves, integer /
-address arithmetic (everything else on the VALU), LDS, global / buffer memory, SALU (by kind), waits and branches."""
+address arithmetic (everything else on the VALU), LDS, global / buffer memory, SALU (by kind), waits and branches.
+
+The column "issue cycles" weighs the vector instructions by how long a wave64 one holds its SIMD: 4 cycles, and 16 for the
+quarter-rate fp64 seeds (v_rcp / v_rsq / v_sqrt_f64); the other classes do not issue on the VALU and show "-"."""
 import collections
 import re
 import sys
@@ -61,12 +64,25 @@ def klass(op):
 by = collections.defaultdict(collections.Counter)
 for op, c in ops.items():
     by[klass(op)][op] += c
+
+
+def issue_cycles(op, c):
+    if not op.startswith("v_"):
+        return 0
+    return c * (16 if re.match(r"v_(rcp|rsq|sqrt)_f64", op) else 4)
+
+
 tot = sum(ops.values())
 valu = sum(c for op, c in ops.items() if op.startswith("v_"))
 print(m.group(1))
 print(f"static instructions: {tot}   VALU {valu}   SALU {sum(c for op, c in ops.items() if op.startswith('s_'))}   "
       f"LDS {sum(c for op, c in ops.items() if op.startswith('ds_'))}")
+cyc_tot = sum(issue_cycles(op, c) for op, c in ops.items())
+print(f"VALU issue cycles per wave (4 per instruction, 16 per quarter-rate seed): {cyc_tot}")
+print(f"{'count':>6s}  {'share':>7s}  {'issue cycles':>12s}  class")
 for k in sorted(by, key=lambda k: -sum(by[k].values())):
     n = sum(by[k].values())
+    cyc = sum(issue_cycles(op, c) for op, c in by[k].items())
     top = ", ".join(f"{op} {c}" for op, c in by[k].most_common(6))
-    print(f"{n:6d}  {100 * n / tot:5.1f} %  {k:58s} {top}")
+    cyc_s = f"{cyc:6d} {100 * cyc / cyc_tot:4.1f}%" if cyc else f"{'-':>12s}"
+    print(f"{n:6d}  {100 * n / tot:5.1f} %  {cyc_s:>12s}  {k:58s} {top}")
