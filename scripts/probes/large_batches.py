@@ -6,7 +6,7 @@ compared with the first tile's bit for bit (a wrong 32-bit offset anywhere shows
 
 rsik_solve: joints [n, 7] f64 = 4.7 GB at 80 Mi poses; rsik_control_discrete: goal matrices [12, n] = 8 GB; the continuous run:
 n trajectories x 96 steps (joints [96, n, 7] = 4.5 GB at 1 Mi trajectories; its blocks are sized so that the sequential phases' 2 GB
-buffer windows hold them, cont_plan in rsik_lib.hip)."""
+buffer windows hold them, cont_plan in rsik_cont_run.hpp)."""
 import os
 import sys
 

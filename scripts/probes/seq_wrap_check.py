@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The words that tie the streams of rsik_control_continuous_run carry a 32-bit run number and only ever grow; before it wraps the
-library drains what it has issued and starts the words over (RSIK_EDGE_SEQ_WRAP in rsik_lib.hip: 0xfffffff0 runs).  A test build puts
+library drains what it has issued and starts the words over (RSIK_EDGE_SEQ_WRAP in rsik_cont_run.hpp: 0xfffffff0 runs).  A test build puts
 that point at run 5 (scripts/build_variant.py seqwrap -DRSIK_EDGE_SEQ_WRAP=5); this script issues 14 runs that continue one eventful
 trajectory batch — overlapping (RSIK_OPT_CONT_GOALS_RESIDENT), two output sets in turn, 13 blocks through eight workspace slots —
 and saves every run's outputs and the trajectory state:

@@ -1164,7 +1164,7 @@ def test_continuous_pipeline_every_short_length(torch_mod):
 def test_continuous_pipeline_theta_step_per_interval_kind(torch_mod, arm, mode, d_theta_max):
     """The theta phase of the trajectory pipeline runs a step specialised for the launch's control interval (wrap-around
     for the right arm unconstrained, inner intervals for the others — one of them starting at -pi), with the choice of
-    the nearer interval end reduced to one threshold the host derives (theta_snap_plan, rsik_lib.hip).  The step kernel
+    the nearer interval end reduced to one threshold the host derives (theta_snap_plan, rsik_cont_run.hpp).  The step kernel
     (one launch per control step) keeps limit_theta_to_interval's own arithmetic: both must give the same bits for every
     arm x constrained mode, also with a rate limit large enough for theta to cross the gap's middle in one step."""
     from bench import make_config5_trajectories

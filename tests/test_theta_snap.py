@@ -1,5 +1,5 @@
 """Host-side check of the argument the theta phase of the trajectory pipeline relies on (continuous_next_theta_lean,
-reachy2_symbolic_ik_amd/csrc/rsik_device.hpp; theta_snap_plan, rsik_lib.hip): limit_theta_to_interval's choice of the
+reachy2_symbolic_ik_amd/csrc/rsik_device.hpp; theta_snap_plan, rsik_cont_run.hpp): limit_theta_to_interval's choice of the
 nearer interval end — abs(angle_diff(theta, l1)) < abs(angle_diff(theta, l0)), utils.py:105-111 — is, for a theta in
 (-pi, pi] outside the interval, ONE comparison with a threshold, and the whole snap is min / max arithmetic around it:
 
