@@ -309,6 +309,42 @@ int rsik_solve_rows(rsik_ctx *ctx, int64_t n, const double *const pose_soa[6], c
                     double *interval, double *elbow, uint8_t *reachable, uint8_t *state);
 
 /*
+ * rsik_solve_sweep — SymbolicIK.is_reachable once per pose, then the closure it returns (theta_to_joints_func = get_joints,
+ * symbolic_ik.py:235, 697-863) at n_theta elbow angles of that pose, all from one launch: the arm's redundant degree of freedom
+ * sampled for a planner, a reachability map or a data generator.  Added within ABI version 8: a new symbol, nothing else changed.
+ *
+ * Sample (k, i) is, bit for bit, what rsik_solve returns for pose i under the same theta_policy with theta_in = that sample's
+ * value (with previous_joints: what rsik_solve_rows returns for that row); interval / reachable / state are rsik_solve's for
+ * the same poses.  The samples are independent of each other and of their order: every one starts from the wrist is_reachable
+ * left, so a sample whose elbow projection fired (symbolic_ik.py:708-718: the goal is MOVED, the joints reach the moved goal)
+ * leaves nothing behind for the next — unlike get_joints called repeatedly on one SymbolicIK object, or
+ * rsik_joints_from_state on one solver-state row.  Every sample's cos / sin are those of its theta (fraction 0 included: as
+ * RSIK_THETA_FRACTION with 0, not as RSIK_THETA_INTERVAL0).
+ *
+ *   n_theta          samples per pose, 1 ... 4096
+ *   theta_policy     RSIK_THETA_FRACTION or RSIK_THETA_EXPLICIT (anything else: RSIK_E_INVALID)
+ *   theta_in         device; theta_per_pose == 0: [n_theta] values shared by every pose (a grid of fractions, one set of angles);
+ *                    otherwise [n_theta][n], sample-major
+ *   previous_joints  [n,7] device or NULL for zeros: one row per pose, shared by its samples (read only at an exact singularity)
+ * Outputs are sample-major — each sample is one contiguous [n, W] array of the shape rsik_solve writes:
+ *   joints           [n_theta][n][7]
+ *   elbow            [n_theta][n][3] or NULL
+ *   projected        [n_theta][n] uint8 or NULL: 1 where the elbow projection fired for that sample; 0 for unreachable poses
+ *   theta            [n_theta][n] or NULL: the angle evaluated — FRACTION: i0 + u * (i1' - i0), i1' = i1 + 2 pi when i0 > i1;
+ *                    EXPLICIT: the input; NaN for unreachable poses
+ *   interval [n,2], reachable [n], state [n]   as rsik_solve, any of them NULL
+ * Unreachable and invalid poses give NaN joints and elbow in every sample.  "Rows that are not numbers" applies: a pose with a
+ * NaN or an infinity reports RSIK_STATE_INVALID_INPUT and NaN in all its samples; a theta that is not a number poisons its own
+ * (sample, pose) — that sample of every pose where it sits in a shared grid — and nothing else.
+ * n == 0 launches nothing.  Enqueued on the context's stream; never waits for the device.
+ */
+int rsik_solve_sweep(rsik_ctx *ctx, int64_t n, const double *const pose_soa[6], const uint8_t *arm, int arm_uniform,
+                     int n_theta, int theta_policy, const double *theta_in, int theta_per_pose,
+                     const double *previous_joints,
+                     double *joints, double *elbow, uint8_t *projected, double *theta,
+                     double *interval, uint8_t *reachable, uint8_t *state);
+
+/*
  * rsik_control_discrete_rows — rsik_control_discrete with previous_sol [n,7]: row i is ControlIK.previous_sol[name] of the
  *   caller that owns goal i, for that row's own arm (no 2x7 split).  It is get_joints' previous_joints (control_ik.py:454-456),
  *   the fallback joints when no theta is found and current_joints is NULL (:237-238, :457-458), and safety_checks'

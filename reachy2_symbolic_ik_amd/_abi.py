@@ -58,6 +58,8 @@ PROTOTYPES = {
     "rsik_control_discrete": (C.c_int, [_vp, C.c_int64, C.POINTER(_vp), _vp, C.c_int, C.c_int, C.c_double, C.c_int, _dp,
                                         _vp, C.c_double, _vp, _vp, _vp, _vp]),
     "rsik_solve_rows": (C.c_int, [_vp, C.c_int64, C.POINTER(_vp), _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rsik_solve_sweep": (C.c_int, [_vp, C.c_int64, C.POINTER(_vp), _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp,
+                                   _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rsik_control_discrete_rows": (C.c_int, [_vp, C.c_int64, C.POINTER(_vp), _vp, C.c_int, C.c_int, C.c_double, C.c_int, _vp,
                                              _vp, C.c_double, _vp, _vp, _vp, _vp]),
     "rsik_control_continuous_step": (C.c_int, [_vp, C.c_int64, C.POINTER(_vp), C.POINTER(_vp), _vp, C.c_int, _vp, C.c_double, _dp,

@@ -216,6 +216,70 @@ class HipSolver:
             res["elbow"] = elbow
         return res
 
+    # ------------------------------------------------------------------ rsik_solve_sweep
+    def solve_sweep(
+        self,
+        pose_soa: torch.Tensor,
+        thetas: torch.Tensor,
+        policy: str = "fraction",
+        arm: Optional[torch.Tensor] = None,
+        arm_uniform: int = 0,
+        previous_joints: Optional[torch.Tensor] = None,
+        want_elbow: bool = True,
+        out: Optional[Dict[str, torch.Tensor]] = None,
+        plan_only: bool = False,
+    ) -> Dict[str, torch.Tensor]:
+        """K elbow angles per pose from one launch (rsik_solve_sweep): is_reachable once per pose, then get_joints at every
+        sample, each sample bit for bit what solve() returns for that theta — independent of the other samples and their order.
+        pose_soa: [6, n] float64.  thetas: 1-D [K], shared by every pose, or 2-D [K, n], one column per pose; `policy`
+        "fraction" (of the pose's interval, 0 ... 1 from interval[0] to interval[1]) or "explicit" (angles).
+        previous_joints: [n, 7] or None for zeros, one row per pose.
+        Returns device tensors, sample-major: joints [K, n, 7], elbow [K, n, 3] (want_elbow), projected [K, n] u8 (1 where the
+        elbow projection moved the goal for that sample), theta [K, n] (the angle evaluated), and interval [n, 2],
+        reachable [n] u8, state [n] u8 as solve().  Sample k is the contiguous array joints[k];
+        joints.permute(1, 0, 2) is the per-pose view [n, K, 7].
+        plan_only=True launches nothing and adds res["launch"], a zero-overhead re-launch callable (see plan())."""
+        if pose_soa.dim() != 2 or pose_soa.shape[0] != 6:
+            raise ValueError("pose_soa must have shape [6, n]")
+        codes = {"fraction": _abi.THETA_FRACTION, "explicit": _abi.THETA_EXPLICIT}
+        if policy not in codes:
+            raise ValueError("policy must be 'fraction' or 'explicit'")
+        n = int(pose_soa.shape[1])
+        pose_soa = self._dev_cols(pose_soa, 6, n, "pose_soa")
+        if not isinstance(thetas, torch.Tensor):
+            thetas = torch.as_tensor(np.asarray(thetas, dtype=np.float64))
+        if thetas.dim() not in (1, 2):
+            raise ValueError("thetas must have shape [K] or [K, n]")
+        k = int(thetas.shape[0])
+        per_pose = thetas.dim() == 2
+        if not 1 <= k <= 4096:
+            raise ValueError("thetas: between 1 and 4096 samples per pose")
+        thetas = self._dev_f64(thetas, (k, n) if per_pose else (k,), "thetas")
+        if arm is not None:
+            arm = self._dev_u8(arm, n, "arm")
+        if previous_joints is not None:
+            previous_joints = self._dev_f64(previous_joints, (n, 7), "previous_joints")
+        res = {"joints": self._out_buf(out, "joints", (k, n, 7), _F64)}
+        if want_elbow:
+            res["elbow"] = self._out_buf(out, "elbow", (k, n, 3), _F64)
+        res["projected"] = self._out_buf(out, "projected", (k, n), _U8)
+        res["theta"] = self._out_buf(out, "theta", (k, n), _F64)
+        res["interval"] = self._out_buf(out, "interval", (n, 2), _F64)
+        res["reachable"] = self._out_buf(out, "reachable", (n,), _U8)
+        res["state"] = self._out_buf(out, "state", (n,), _U8)
+        cols = (C.c_void_p * 6)(*[pose_soa[c].data_ptr() for c in range(6)])
+        cargs = (n, cols, _ptr(arm), int(arm_uniform), k, codes[policy], _ptr(thetas), int(per_pose),
+                 _ptr(previous_joints), _ptr(res["joints"]), _ptr(res.get("elbow")), _ptr(res["projected"]), _ptr(res["theta"]),
+                 _ptr(res["interval"]), _ptr(res["reachable"]), _ptr(res["state"]))
+        if plan_only:
+            res["launch"] = self.plan("rsik_solve_sweep", *cargs)
+            res["_keepalive"] = (pose_soa, arm, thetas, cols, previous_joints)
+        else:
+            with torch.cuda.device(self.device):
+                self._bind_stream()
+                self._check(self.lib.rsik_solve_sweep(self._h, *cargs))
+        return res
+
     def plan(self, fn_name: str, *args):
         """Binds one C-ABI call with all its arguments once; the returned callable re-issues exactly that launch (a few
         microseconds of host time per call — the hot loop of a caller that re-solves resident buffers, e.g. bench.py).

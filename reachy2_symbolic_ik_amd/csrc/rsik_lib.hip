@@ -29,6 +29,7 @@
 #include "rsik_kernel_state.hpp"
 #include "rsik_kernel_stages.hpp"
 #include "rsik_kernel_theta_from_joints.hpp"
+#include "rsik_kernel_sweep.hpp"
 
 // =====================================================================================
 // C ABI
@@ -323,6 +324,55 @@ int rsik_solve_rows(rsik_ctx* ctx, int64_t n, const double* const pose_soa[6], c
     if (!previous_joints) return fail(ctx, RSIK_E_INVALID, "rsik_solve_rows: previous_joints is NULL");
     return solve_impl(ctx, "rsik_solve_rows", n, pose_soa, arm, arm_uniform, theta_policy, theta_in, nullptr, previous_joints,
                       joints, interval, elbow, reachable, state);
+}
+
+// rsik_solve_sweep: is_reachable once per pose, get_joints at n_theta elbow angles (rsik_kernel_sweep.hpp)
+int rsik_solve_sweep(rsik_ctx* ctx, int64_t n, const double* const pose_soa[6], const uint8_t* arm, int arm_uniform,
+                     int n_theta, int theta_policy, const double* theta_in, int theta_per_pose,
+                     const double* previous_joints,
+                     double* joints, double* elbow, uint8_t* projected, double* theta,
+                     double* interval, uint8_t* reachable, uint8_t* state) {
+    if (!ctx) return RSIK_E_INVALID;
+    const char* who = "rsik_solve_sweep";
+    const std::string w(who);
+    if (n < 0) return fail(ctx, RSIK_E_INVALID, w + ": n < 0");
+    if (n_theta < 1 || n_theta > 4096) return fail(ctx, RSIK_E_INVALID, w + ": n_theta must be in [1, 4096]");
+    if (theta_policy != RSIK_THETA_EXPLICIT && theta_policy != RSIK_THETA_FRACTION)
+        return fail(ctx, RSIK_E_INVALID, w + ": theta_policy must be RSIK_THETA_EXPLICIT or RSIK_THETA_FRACTION");
+    int rc = check_arms(ctx, arm, arm_uniform, who);
+    if (rc != RSIK_OK) return rc;
+    if (n == 0) return RSIK_OK;
+    if (!pose_soa) return fail(ctx, RSIK_E_INVALID, w + ": pose_soa is NULL");
+    if (!theta_in) return fail(ctx, RSIK_E_INVALID, w + ": theta_in is NULL");
+    if (!joints) return fail(ctx, RSIK_E_INVALID, w + ": joints is NULL");
+    rsik::SweepArgs K;
+    K.n = n;
+    for (int k = 0; k < 6; k++) {
+        if (!pose_soa[k]) return fail(ctx, RSIK_E_INVALID, w + ": a pose_soa column is NULL");
+        K.in[k] = pose_soa[k];
+    }
+    K.arm = arm;
+    K.theta_policy = theta_policy;
+    K.n_theta = n_theta;
+    K.theta_per_pose = theta_per_pose != 0;
+    K.theta_in = theta_in;
+    if (previous_joints) K.prev_rows = previous_joints;  // (shares its kernarg bytes with K.prev)
+    else for (int k = 0; k < 7; k++) K.prev[k] = 0.0;
+    K.joints = joints; K.elbow = elbow; K.projected = projected; K.theta = theta;
+    K.interval = interval; K.reachable = reachable; K.state = state;
+    if (arm) { K.arms[0] = ctx->arms[0]; K.arms[1] = ctx->arms[1]; }
+    else { K.arms[0] = ctx->arms[arm_uniform]; K.arms[1] = ctx->arms[arm_uniform]; }
+    RSIK_HIP(ctx, hipSetDevice(ctx->device));
+    dim3 grid, block(rsik::kBlock);
+    if ((rc = launch_dims(ctx, n, &grid, who)) != RSIK_OK) return rc;
+    // the kernel variant is chosen as rsik_solve chooses its own
+    const bool tipz = K.arms[0].v[RSIK_C_TIPL] == 0.0 && K.arms[0].v[RSIK_C_TIPL + 1] == 0.0 &&
+                      K.arms[1].v[RSIK_C_TIPL] == 0.0 && K.arms[1].v[RSIK_C_TIPL + 1] == 0.0 && !ctx->options[RSIK_OPT_NO_TIPZ];
+    const int form = arm ? (arms_mirror(ctx, K.arms, arm) ? 2 : 1) : 0;
+    with_int3(form, [&](auto FORM) { with_bool(tipz, [&](auto TIPZ) { with_bool(previous_joints != nullptr, [&](auto PREV_ROWS) {
+        hipLaunchKernelGGL((rsik::solve_sweep_kernel<FORM(), TIPZ(), PREV_ROWS()>), grid, block, 0, ctx->stream, K); }); }); });
+    RSIK_HIP(ctx, hipGetLastError());
+    return RSIK_OK;
 }
 
 // Python float modulo (sign of the divisor), used for the l-arm limit wrap (C:243-250).

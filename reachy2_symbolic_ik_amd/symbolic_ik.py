@@ -307,6 +307,25 @@ class SymbolicIK:
                                   previous_joints=previous_joints, want_elbow=want_elbow, out=out, plan_only=plan_only,
                                   previous_joints_rows=rows)
 
+    def sweep_batch(self, poses: Any, thetas: Any = None, n_theta: int = 16, policy: str = "fraction",
+                    previous_joints: Any = None, want_elbow: bool = True,
+                    out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+        """The arm's redundant degree of freedom sampled for a batch of poses of this arm, in one launch: is_reachable once per
+        pose, then the closure it returns (theta_to_joints_func) at K elbow angles — every sample a fresh get_joints on the
+        goal asked for, whatever the other samples did (HipSolver.solve_sweep, rsik_solve_sweep).
+
+        poses: [n,2,3] or SoA [6,n].  thetas: [K] shared by every pose, or [K, n]; None: `n_theta` evenly spaced fractions
+        from 0 to 1 inclusive (interval[0] ... interval[1]).  policy: "fraction" or "explicit".  previous_joints: (n, 7) or None.
+        Returns device tensors, sample-major: joints [K,n,7], elbow [K,n,3], projected [K,n] u8 (1: the elbow projection moved
+        the goal, the joints reach the moved goal), theta [K,n], interval [n,2], reachable [n] u8, state [n] u8.
+        joints.permute(1, 0, 2) is the per-pose view [n,K,7]."""
+        soa = poses_to_soa(poses, self._solver.device)
+        if thetas is None:
+            thetas = torch.linspace(0.0, 1.0, int(n_theta), dtype=torch.float64)
+        self._upload()
+        return self._solver.solve_sweep(soa, thetas, policy=policy, arm_uniform=self.arm_id, previous_joints=previous_joints,
+                                        want_elbow=want_elbow, out=out)
+
     def theta_from_joints_batch(self, poses: Any, current_joints: Any, preferred_theta: Optional[float] = None,
                                 out: Optional[Dict[str, torch.Tensor]] = None, plan_only: bool = False) -> Dict[str, torch.Tensor]:
         """For every row, the theta whose solution is closest to that row's measured joints: is_reachable_no_limits(pose),
@@ -446,6 +465,19 @@ class DualArmIK:
         previous_joints, rows = _split_previous_joints(previous_joints)
         return self._solver.solve(soa, arm=arm_ids, theta_policy=policy, theta_in=theta_in, previous_joints=previous_joints,
                                   want_elbow=want_elbow, out=out, plan_only=plan_only, previous_joints_rows=rows)
+
+    def sweep_batch(self, arm_ids: Any, poses: Any, thetas: Any = None, n_theta: int = 16, policy: str = "fraction",
+                    previous_joints: Any = None, want_elbow: bool = True,
+                    out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+        """SymbolicIK.sweep_batch for rows of both arms (arm_ids [n] uint8): K elbow angles per pose in one launch.  Returns
+        sample-major tensors (joints [K,n,7] ...); joints.permute(1, 0, 2) is the per-pose view [n,K,7]."""
+        soa = poses_to_soa(poses, self._solver.device)
+        if thetas is None:
+            thetas = torch.linspace(0.0, 1.0, int(n_theta), dtype=torch.float64)
+        self.r_arm._upload()
+        self.l_arm._upload()
+        return self._solver.solve_sweep(soa, thetas, policy=policy, arm=arm_ids, previous_joints=previous_joints,
+                                        want_elbow=want_elbow, out=out)
 
     def theta_from_joints_batch(self, arm_ids: Any, poses: Any, current_joints: Any, preferred_theta: Optional[Sequence[float]] = None,
                                 out: Optional[Dict[str, torch.Tensor]] = None, plan_only: bool = False) -> Dict[str, torch.Tensor]:
