@@ -75,6 +75,34 @@ class HipSolver:
         s = torch.cuda.current_stream(self.device).cuda_stream
         self._check(self.lib.rsik_set_stream(self._h, C.c_void_p(s)))
 
+    def _call(self, fn_name: str, *cargs) -> None:
+        """One C-ABI call of this context on its device and torch's current stream, checked."""
+        with torch.cuda.device(self.device):
+            self._bind_stream()
+            self._check(getattr(self.lib, fn_name)(self._h, *cargs))
+
+    def _finish(self, res: Dict[str, Any], fn_name: str, cargs: tuple, plan_only: bool, keepalive: tuple) -> Dict[str, Any]:
+        """Launches, or (plan_only) adds res["launch"] (see plan()) and what the planned launch points into."""
+        if plan_only:
+            res["launch"] = self.plan(fn_name, *cargs)
+            res["_keepalive"] = keepalive
+        else:
+            self._call(fn_name, *cargs)
+        return res
+
+    @staticmethod
+    def _cols(t: torch.Tensor, rows: int):
+        """The ABI's column table of an SoA tensor [rows, n]: one pointer per row."""
+        return (C.c_void_p * rows)(*[t[k].data_ptr() for k in range(rows)])
+
+    @staticmethod
+    def _pair(v: Sequence[float], name: str):
+        """A per-arm launch constant: 2 float64 values (r, l), and the pointer the ABI takes."""
+        pts = np.ascontiguousarray(v, dtype=np.float64)
+        if pts.shape != (2,):
+            raise ValueError(f"{name} must have 2 entries (r, l)")
+        return pts, pts.ctypes.data_as(C.POINTER(C.c_double))
+
     def set_arm(self, arm_id: int, consts: np.ndarray) -> None:
         c = np.ascontiguousarray(consts, dtype=np.float64)
         if c.shape != (ARM_CONSTS_COUNT,):
@@ -89,16 +117,12 @@ class HipSolver:
 
     def synchronize(self) -> None:
         """Waits for the work on the CURRENT torch stream of this device (the stream every non-planned call uses)."""
-        with torch.cuda.device(self.device):
-            self._bind_stream()  # (a planned launch may have left the context on another, possibly destroyed, stream)
-            self._check(self.lib.rsik_sync(self._h))
+        self._call("rsik_sync")  # (binds the stream first: a planned launch may have left the context on another, possibly destroyed, one)
 
     def control_continuous_reserve(self, n: int, n_steps: int) -> None:
         """rsik_control_continuous_reserve: workspace, side streams and events of a control_continuous_run(n, n_steps), so
         that the run allocates nothing — needed before such a run is captured into a hipGraph on a fresh context."""
-        with torch.cuda.device(self.device):
-            self._bind_stream()
-            self._check(self.lib.rsik_control_continuous_reserve(self._h, int(n), int(n_steps)))
+        self._call("rsik_control_continuous_reserve", int(n), int(n_steps))
 
     def control_continuous_release(self) -> None:
         """rsik_control_continuous_release: waits for the device and frees the workspace(s) continuous runs keep in the context
@@ -186,7 +210,7 @@ class HipSolver:
         interval = self._out_buf(out, "interval", (n, 2), _F64)
         reachable = self._out_buf(out, "reachable", (n,), _U8)
         state = self._out_buf(out, "state", (n,), _U8)
-        cols = (C.c_void_p * 6)(*[pose_soa[k].data_ptr() for k in range(6)])
+        cols = self._cols(pose_soa, 6)
         prev = None
         fn_name = "rsik_solve"
         if previous_joints_rows is not None:
@@ -203,13 +227,7 @@ class HipSolver:
         cargs = (n, cols, _ptr(arm), int(arm_uniform), int(theta_policy), _ptr(theta_in), prev,
                  _ptr(joints), _ptr(interval), _ptr(elbow), _ptr(reachable), _ptr(state))
         res = {"interval": interval, "reachable": reachable, "state": state}
-        if plan_only:
-            res["launch"] = self.plan(fn_name, *cargs)
-            res["_keepalive"] = (pose_soa, arm, theta_in, cols, prev, previous_joints_rows)
-        else:
-            with torch.cuda.device(self.device):
-                self._bind_stream()
-                self._check(getattr(self.lib, fn_name)(self._h, *cargs))
+        self._finish(res, fn_name, cargs, plan_only, (pose_soa, arm, theta_in, cols, prev, previous_joints_rows))
         if joints is not None:
             res["joints"] = joints
         if elbow is not None:
@@ -267,18 +285,11 @@ class HipSolver:
         res["interval"] = self._out_buf(out, "interval", (n, 2), _F64)
         res["reachable"] = self._out_buf(out, "reachable", (n,), _U8)
         res["state"] = self._out_buf(out, "state", (n,), _U8)
-        cols = (C.c_void_p * 6)(*[pose_soa[c].data_ptr() for c in range(6)])
+        cols = self._cols(pose_soa, 6)
         cargs = (n, cols, _ptr(arm), int(arm_uniform), k, codes[policy], _ptr(thetas), int(per_pose),
                  _ptr(previous_joints), _ptr(res["joints"]), _ptr(res.get("elbow")), _ptr(res["projected"]), _ptr(res["theta"]),
                  _ptr(res["interval"]), _ptr(res["reachable"]), _ptr(res["state"]))
-        if plan_only:
-            res["launch"] = self.plan("rsik_solve_sweep", *cargs)
-            res["_keepalive"] = (pose_soa, arm, thetas, cols, previous_joints)
-        else:
-            with torch.cuda.device(self.device):
-                self._bind_stream()
-                self._check(self.lib.rsik_solve_sweep(self._h, *cargs))
-        return res
+        return self._finish(res, "rsik_solve_sweep", cargs, plan_only, (pose_soa, arm, thetas, cols, previous_joints))
 
     def plan(self, fn_name: str, *args):
         """Binds one C-ABI call with all its arguments once; the returned callable re-issues exactly that launch (a few
@@ -348,18 +359,11 @@ class HipSolver:
         reachable = self._out_buf(out, "reachable", (n,), _U8)
         state = self._out_buf(out, "state", (n,), _U8)
         emergency = self._out_buf(out, "emergency", (n,), _U8)
-        cols = (C.c_void_p * 12)(*[m12_soa[k].data_ptr() for k in range(12)])
+        cols = self._cols(m12_soa, 12)
         cargs = (n, cols, _ptr(arm), int(arm_uniform), int(nb_search_points), float(preferred_theta), int(constrained_mode),
                  prev, _ptr(current_joints), float(orbita3d_max_angle), _ptr(joints), _ptr(reachable), _ptr(state), _ptr(emergency))
         res = {"joints": joints, "reachable": reachable, "state": state, "emergency": emergency}
-        if plan_only:
-            res["launch"] = self.plan(fn_name, *cargs)
-            res["_keepalive"] = (m12_soa, arm, current_joints, cols, ps)
-        else:
-            with torch.cuda.device(self.device):
-                self._bind_stream()
-                self._check(getattr(self.lib, fn_name)(self._h, *cargs))
-        return res
+        return self._finish(res, fn_name, cargs, plan_only, (m12_soa, arm, current_joints, cols, ps))
 
     # ------------------------------------------------------------------ rsik_control_continuous_step
     def new_continuous_state(self, n: int) -> torch.Tensor:
@@ -386,9 +390,7 @@ class HipSolver:
             raise ValueError("m12_soa must have shape [12, n]")
         n = int(m12_soa.shape[1])
         m12_soa = self._dev_f64(m12_soa, (12, n), "m12_soa")
-        if (not isinstance(cont_state, torch.Tensor) or cont_state.dtype != _F64 or cont_state.device != self.device
-                or tuple(cont_state.shape) != (_abi.CONT_STATE_ROWS, n) or not cont_state.is_contiguous()):
-            raise ValueError(f"cont_state must be a contiguous float64 [{_abi.CONT_STATE_ROWS}, {n}] tensor on {self.device}")
+        self._check_cont_state(cont_state, n)
         if arm is not None:
             arm = self._dev_u8(arm, n, "arm")
         if timed_out is not None:
@@ -398,20 +400,14 @@ class HipSolver:
         cp = None
         if current_pose_m12 is not None:
             current_pose_m12 = self._dev_f64(current_pose_m12, (12, n), "current_pose_m12")
-            cp = (C.c_void_p * 12)(*[current_pose_m12[k].data_ptr() for k in range(12)])
-        pts = np.ascontiguousarray(preferred_theta_self, dtype=np.float64)
-        if pts.shape != (2,):
-            raise ValueError("preferred_theta_self must have 2 entries (r, l)")
+            cp = self._cols(current_pose_m12, 12)
+        pref_self, pts = self._pair(preferred_theta_self, "preferred_theta_self")  # (pref_self: alive until the call returns)
         joints = self._out_buf(out, "joints", (n, 7), _F64)
         reachable = self._out_buf(out, "reachable", (n,), _U8)
         state = self._out_buf(out, "state", (n,), _U8)
-        cols = (C.c_void_p * 12)(*[m12_soa[k].data_ptr() for k in range(12)])
-        with torch.cuda.device(self.device):
-            self._bind_stream()
-            self._check(self.lib.rsik_control_continuous_step(
-                self._h, n, cols, cp, _ptr(arm), int(arm_uniform), _ptr(timed_out), float(preferred_theta),
-                pts.ctypes.data_as(C.POINTER(C.c_double)), int(constrained_mode), float(d_theta_max), _ptr(current_joints),
-                float(orbita3d_max_angle), _ptr(cont_state), _ptr(joints), _ptr(reachable), _ptr(state)))
+        self._call("rsik_control_continuous_step", n, self._cols(m12_soa, 12), cp, _ptr(arm), int(arm_uniform), _ptr(timed_out),
+                   float(preferred_theta), pts, int(constrained_mode), float(d_theta_max), _ptr(current_joints),
+                   float(orbita3d_max_angle), _ptr(cont_state), _ptr(joints), _ptr(reachable), _ptr(state))
         return {"joints": joints, "reachable": reachable, "state": state}
 
     def control_continuous_run(
@@ -443,9 +439,7 @@ class HipSolver:
         n_steps, _, n = (int(v) for v in m12_steps.shape)
         if m12_steps.dtype != _F64 or m12_steps.device != self.device or not m12_steps.is_contiguous():
             m12_steps = m12_steps.to(device=self.device, dtype=_F64).contiguous()
-        if (cont_state.dtype != _F64 or cont_state.device != self.device or tuple(cont_state.shape) != (_abi.CONT_STATE_ROWS, n)
-                or not cont_state.is_contiguous()):
-            raise ValueError(f"cont_state must be a contiguous float64 [{_abi.CONT_STATE_ROWS}, {n}] tensor on {self.device}")
+        self._check_cont_state(cont_state, n)
         if arm is not None:
             arm = self._dev_u8(arm, n, "arm")
         if current_joints is not None:
@@ -453,7 +447,8 @@ class HipSolver:
         cp = None
         if current_pose_m12 is not None:
             current_pose_m12 = self._dev_f64(current_pose_m12, (12, n), "current_pose_m12")
-            cp = (C.c_void_p * 12)(*[current_pose_m12[k].data_ptr() for k in range(12)])
+            cp = self._cols(current_pose_m12, 12)
+        # (not _pair: this entry point has never refused a preferred_theta_self of another shape, and does not start to here)
         pts = np.ascontiguousarray(preferred_theta_self, dtype=np.float64)
         joints = self._out_buf(out, "joints", (n_steps, n, 7), _F64)
         reachable = self._out_buf(out, "reachable", (n_steps, n), _U8)
@@ -463,12 +458,10 @@ class HipSolver:
             before = self.get_option(_abi.OPT_CONT_GOALS_RESIDENT)
             self.set_option(_abi.OPT_CONT_GOALS_RESIDENT, int(bool(goals_resident)))
         try:
-            with torch.cuda.device(self.device):
-                self._bind_stream()
-                self._check(self.lib.rsik_control_continuous_run(
-                    self._h, n, n_steps, _ptr(m12_steps), cp, _ptr(arm), int(arm_uniform), int(bool(first_step_timed_out)),
-                    float(preferred_theta), pts.ctypes.data_as(C.POINTER(C.c_double)), int(constrained_mode), float(d_theta_max),
-                    _ptr(current_joints), float(orbita3d_max_angle), _ptr(cont_state), _ptr(joints), _ptr(reachable), _ptr(state)))
+            self._call("rsik_control_continuous_run", n, n_steps, _ptr(m12_steps), cp, _ptr(arm), int(arm_uniform),
+                       int(bool(first_step_timed_out)), float(preferred_theta), pts.ctypes.data_as(C.POINTER(C.c_double)),
+                       int(constrained_mode), float(d_theta_max), _ptr(current_joints), float(orbita3d_max_angle),
+                       _ptr(cont_state), _ptr(joints), _ptr(reachable), _ptr(state))
         finally:
             if before is not None:
                 self.set_option(_abi.OPT_CONT_GOALS_RESIDENT, before)
@@ -494,11 +487,8 @@ class HipSolver:
         interval = torch.empty((n, 2), dtype=_F64, device=self.device)
         reachable = torch.empty((n,), dtype=_U8, device=self.device)
         state = torch.empty((n,), dtype=_U8, device=self.device)
-        cols = (C.c_void_p * 6)(*[pose_soa[k].data_ptr() for k in range(6)])
-        with torch.cuda.device(self.device):
-            self._bind_stream()
-            self._check(self.lib.rsik_reach_state(self._h, n, cols, _ptr(arm), int(arm_uniform), int(bool(no_limits)),
-                                                  _ptr(solver_state), _ptr(interval), _ptr(reachable), _ptr(state)))
+        self._call("rsik_reach_state", n, self._cols(pose_soa, 6), _ptr(arm), int(arm_uniform), int(bool(no_limits)),
+                   _ptr(solver_state), _ptr(interval), _ptr(reachable), _ptr(state))
         return {"interval": interval, "reachable": reachable, "state": state}
 
     def joints_from_state(self, solver_state: torch.Tensor, theta: torch.Tensor, arm: Optional[torch.Tensor] = None,
@@ -512,10 +502,8 @@ class HipSolver:
             previous_joints = self._dev_f64(previous_joints, (n, 7), "previous_joints")
         joints = torch.empty((n, 7), dtype=_F64, device=self.device)
         elbow = torch.empty((n, 3), dtype=_F64, device=self.device)
-        with torch.cuda.device(self.device):
-            self._bind_stream()
-            self._check(self.lib.rsik_joints_from_state(self._h, n, _ptr(solver_state), _ptr(arm), int(arm_uniform),
-                                                        _ptr(theta), _ptr(previous_joints), _ptr(joints), _ptr(elbow)))
+        self._call("rsik_joints_from_state", n, _ptr(solver_state), _ptr(arm), int(arm_uniform),
+                   _ptr(theta), _ptr(previous_joints), _ptr(joints), _ptr(elbow))
         return {"joints": joints, "elbow": elbow}
 
     def elbow_from_state(self, solver_state: torch.Tensor, theta: torch.Tensor) -> torch.Tensor:
@@ -523,9 +511,7 @@ class HipSolver:
         self._check_state(solver_state, n)
         theta = self._dev_f64(theta, (n,), "theta")
         elbow = torch.empty((n, 3), dtype=_F64, device=self.device)
-        with torch.cuda.device(self.device):
-            self._bind_stream()
-            self._check(self.lib.rsik_elbow_from_state(self._h, n, _ptr(solver_state), _ptr(theta), _ptr(elbow)))
+        self._call("rsik_elbow_from_state", n, _ptr(solver_state), _ptr(theta), _ptr(elbow))
         return elbow
 
     # ------------------------------------------------------------------ rsik_theta_from_joints
@@ -558,9 +544,7 @@ class HipSolver:
         current_joints = self._dev_f64(current_joints, (n, 7), "current_joints")
         if arm is not None:
             arm = self._dev_u8(arm, n, "arm")
-        pts = np.ascontiguousarray(preferred_theta, dtype=np.float64)
-        if pts.shape != (2,):
-            raise ValueError("preferred_theta must have 2 entries (r, l)")
+        pref, pts = self._pair(preferred_theta, "preferred_theta")
         unknown = set(want) - {"joints", "bracket", "distance", "state"}
         if unknown:
             raise ValueError(f"unknown outputs {sorted(unknown)}")
@@ -568,18 +552,11 @@ class HipSolver:
         for key, shape, dt in (("joints", (n, 7), _F64), ("bracket", (n, 2), _F64), ("distance", (n,), _F64), ("state", (n,), _U8)):
             if key in want:
                 res[key] = self._out_buf(out, key, shape, dt)
-        cols = (C.c_void_p * rows)(*[goal_soa[k].data_ptr() for k in range(rows)])
+        cols = self._cols(goal_soa, rows)
         kind = _abi.GOAL_M12 if rows == 12 else _abi.GOAL_POSE6
-        cargs = (n, kind, cols, _ptr(arm), int(arm_uniform), _ptr(current_joints), pts.ctypes.data_as(C.POINTER(C.c_double)),
+        cargs = (n, kind, cols, _ptr(arm), int(arm_uniform), _ptr(current_joints), pts,
                  _ptr(res["theta"]), _ptr(res.get("joints")), _ptr(res.get("bracket")), _ptr(res.get("distance")), _ptr(res.get("state")))
-        if plan_only:
-            res["launch"] = self.plan("rsik_theta_from_joints", *cargs)
-            res["_keepalive"] = (goal_soa, current_joints, arm, cols, pts)
-        else:
-            with torch.cuda.device(self.device):
-                self._bind_stream()
-                self._check(self.lib.rsik_theta_from_joints(self._h, *cargs))
-        return res
+        return self._finish(res, "rsik_theta_from_joints", cargs, plan_only, (goal_soa, current_joints, arm, cols, pref))
 
     def theta_from_joints_state(self, solver_state: torch.Tensor, current_joints: torch.Tensor, preferred_theta: Sequence[float],
                                 arm: Optional[torch.Tensor] = None, arm_uniform: int = 0) -> Dict[str, torch.Tensor]:
@@ -594,16 +571,11 @@ class HipSolver:
         current_joints = self._dev_f64(current_joints, (n, width), "current_joints")
         if arm is not None:
             arm = self._dev_u8(arm, n, "arm")
-        pts = np.ascontiguousarray(preferred_theta, dtype=np.float64)
-        if pts.shape != (2,):
-            raise ValueError("preferred_theta must have 2 entries (r, l)")
+        pref, pts = self._pair(preferred_theta, "preferred_theta")  # (pref: alive until the call returns)
         theta = torch.empty((n,), dtype=_F64, device=self.device)
         bracket = torch.empty((n, 2), dtype=_F64, device=self.device)
-        with torch.cuda.device(self.device):
-            self._bind_stream()
-            self._check(self.lib.rsik_theta_from_joints_state(self._h, n, _ptr(solver_state), _ptr(arm), int(arm_uniform),
-                                                              _ptr(current_joints), width, pts.ctypes.data_as(C.POINTER(C.c_double)),
-                                                              _ptr(theta), _ptr(bracket)))
+        self._call("rsik_theta_from_joints_state", n, _ptr(solver_state), _ptr(arm), int(arm_uniform),
+                   _ptr(current_joints), width, pts, _ptr(theta), _ptr(bracket))
         return {"theta": theta, "bracket": bracket}
 
     def stage(self, op: int, rows: torch.Tensor, arm_uniform: int = 0) -> torch.Tensor:
@@ -615,10 +587,13 @@ class HipSolver:
             raise ValueError(f"stage {op} takes a contiguous float64 [n, {need_in}] tensor on {self.device} (or in pinned host memory)")
         n = int(rows.shape[0])
         out = torch.empty((n, need_out), dtype=_F64, device=self.device)
-        with torch.cuda.device(self.device):
-            self._bind_stream()
-            self._check(self.lib.rsik_stage(self._h, int(op), n, int(arm_uniform), _ptr(rows), need_in, _ptr(out), need_out))
+        self._call("rsik_stage", int(op), n, int(arm_uniform), _ptr(rows), need_in, _ptr(out), need_out)
         return out
+
+    def _check_cont_state(self, cont_state: torch.Tensor, n: int) -> None:
+        if (not isinstance(cont_state, torch.Tensor) or cont_state.dtype != _F64 or cont_state.device != self.device
+                or tuple(cont_state.shape) != (_abi.CONT_STATE_ROWS, n) or not cont_state.is_contiguous()):
+            raise ValueError(f"cont_state must be a contiguous float64 [{_abi.CONT_STATE_ROWS}, {n}] tensor on {self.device}")
 
     def _check_state(self, solver_state: torch.Tensor, n: int) -> None:
         if (not isinstance(solver_state, torch.Tensor) or solver_state.dtype != _F64 or solver_state.device != self.device
@@ -644,11 +619,7 @@ class HipSolver:
         n = int(m12_soa.shape[1])
         m12_soa = self._dev_f64(m12_soa, (12, n), "m12_soa")
         out = torch.empty((6, n), dtype=_F64, device=self.device)
-        cin = (C.c_void_p * 12)(*[m12_soa[k].data_ptr() for k in range(12)])
-        cout = (C.c_void_p * 6)(*[out[k].data_ptr() for k in range(6)])
-        with torch.cuda.device(self.device):
-            self._bind_stream()
-            self._check(self.lib.rsik_matrix_to_pose(self._h, n, cin, 1 if identity_shortcut else 0, cout))
+        self._call("rsik_matrix_to_pose", n, self._cols(m12_soa, 12), 1 if identity_shortcut else 0, self._cols(out, 6))
         return out
 
     # ------------------------------------------------------------------ forward kinematics
@@ -660,9 +631,7 @@ class HipSolver:
             arm = self._dev_u8(arm, n, "arm")
         pos = torch.empty((n, 3), dtype=_F64, device=self.device)
         rot = torch.empty((n, 3, 3), dtype=_F64, device=self.device)
-        with torch.cuda.device(self.device):
-            self._bind_stream()
-            self._check(self.lib.rsik_forward_kinematics(self._h, n, _ptr(joints), _ptr(arm), int(arm_uniform), _ptr(pos), _ptr(rot)))
+        self._call("rsik_forward_kinematics", n, _ptr(joints), _ptr(arm), int(arm_uniform), _ptr(pos), _ptr(rot))
         return pos, rot
 
     def fk_residual(self, goal_soa: torch.Tensor, joints: torch.Tensor, arm: Optional[torch.Tensor] = None,
@@ -677,11 +646,8 @@ class HipSolver:
         if arm is not None:
             arm = self._dev_u8(arm, n, "arm")
         err = torch.empty((n, 2), dtype=_F64, device=self.device)
-        cols = (C.c_void_p * rows)(*[goal_soa[k].data_ptr() for k in range(rows)])
         kind = _abi.GOAL_M12 if rows == 12 else _abi.GOAL_POSE6
-        with torch.cuda.device(self.device):
-            self._bind_stream()
-            self._check(self.lib.rsik_fk_residual(self._h, n, kind, cols, _ptr(joints), _ptr(arm), int(arm_uniform), _ptr(err)))
+        self._call("rsik_fk_residual", n, kind, self._cols(goal_soa, rows), _ptr(joints), _ptr(arm), int(arm_uniform), _ptr(err))
         return err
 
     # ------------------------------------------------------------------ measurement hooks
@@ -715,7 +681,5 @@ class HipSolver:
             b = self._dev_f64(b, (n,), "b")
         o0 = torch.empty((n,), dtype=_F64, device=self.device)
         o1 = torch.empty((n,), dtype=_F64, device=self.device)
-        with torch.cuda.device(self.device):
-            self._bind_stream()
-            self._check(self.lib.rsik_debug_math(self._h, int(op), n, _ptr(a), _ptr(b), _ptr(o0), _ptr(o1)))
+        self._call("rsik_debug_math", int(op), n, _ptr(a), _ptr(b), _ptr(o0), _ptr(o1))
         return o0, o1

@@ -1,5 +1,5 @@
 // rsik_cont_run.hpp — the host-side scheduler of rsik_control_continuous_run: plan, workspace, dependency words, issue order
-// (included by rsik_lib.hip inside its extern "C" block, after the context, the error helpers and fill_continuous)
+// (included by rsik_lib.hip inside its extern "C" block, after the context, the error and launch helpers and fill_continuous)
 //
 // The dependency graph.  Streams: the caller's (start-up and theta kernels), prepare, joints, chain (the context's own).  Kernels on
 // one stream run in issue order; what else a kernel waits for, by form — captured (events, a run recorded into a hipGraph, or variant
@@ -378,8 +378,7 @@ struct ContRun {
             K.state = K0.state ? K0.state + (size_t)k * n : nullptr;
             launch_continuous_step(ctx, K0.arm, K, grid, block);
         }
-        RSIK_HIP(ctx, hipGetLastError());
-        return RSIK_OK;
+        return launch_end(ctx);
     }
 
     // ---- phased pipeline.  The four phases of a block run on four streams (theta on the caller's, the others on the
@@ -684,8 +683,7 @@ struct ContRun {
         }
         // the caller's stream continues once the last chain (hence every phase of every block) is done
         RSIK_HIP(ctx, wait_for(s_main, edge_id(kEdgeChain, n_blocks - 1), seq));
-        RSIK_HIP(ctx, hipGetLastError());
-        return RSIK_OK;
+        return launch_end(ctx);
     }
     // A failure part-way leaves value waits queued on the context's streams whose words nobody is going to write (an event
     // that was never recorded is no wait at all; a word is one).  Every word of the context is raised to this run's number
@@ -747,8 +745,7 @@ int rsik_control_continuous_run(rsik_ctx* ctx, int64_t n, int64_t n_steps, const
                              preferred_theta, preferred_theta_self_host, constrained_mode, d_theta_max, current_joints,
                              orbita3d_max_angle, cont_state, joints_steps, reachable_steps, state_steps);
     if (rc != RSIK_OK) return rc;
-    RSIK_HIP(ctx, hipSetDevice(ctx->device));
-    if ((rc = launch_dims(ctx, n, &run.grid, who)) != RSIK_OK) return rc;
+    if ((rc = launch_begin(ctx, n, &run.grid, who)) != RSIK_OK) return rc;
     // is_reachable_no_limits can only fail (C:385-387) for a projection margin that lets the pulled-back wrist land beyond
     // u + f (S:343-345); the pipeline's phases do not carry that outcome, the step kernel does.
     bool no_limits_can_fail = false;

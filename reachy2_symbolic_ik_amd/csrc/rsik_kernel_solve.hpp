@@ -118,7 +118,7 @@ __device__ __forceinline__ void stage_tables(SharedTables& S, const ArmC* arms) 
             vc[r] = ((r + 1) * NB <= NC || k < NC) ? arms[k / RSIK_ARM_CONSTS_COUNT].v[k % RSIK_ARM_CONSTS_COUNT] : 0.0;
         }
     }
-        double* la = &S.utab[0][0];
+    double* la = &S.utab[0][0];
     double* ls = &g_sincos_tab[0][0];
 #pragma unroll
     for (int r = 0; r < RA; r++)
@@ -245,6 +245,39 @@ __device__ __forceinline__ void branch_stores_stay() { asm volatile("" ::: "memo
 #define RSIK_SOLVE_MIN_WAVES 1
 #endif
 
+// ---- what solve_kernel and solve_sweep_kernel (rsik_kernel_sweep.hpp) share, templated on the argument block and the accessor type: each
+// keeps instantiations of its own (see AccSweep).  Not the tile indices and the six pose loads: in a function both kernels compile differently.
+// The kernarg warm-up and the table staging.  (MIXED == 1 takes every constant from LDS: nothing to warm.  Here the warm-up goes BEFORE
+// the staging loads are issued, in the other kernels between their issue and their use (stage_tables<., WARM>): measured both ways per
+// kernel, config 2 31.1 vs 31.9 us, config 3 15.9 vs 15.7 us)
+template <int MIXED, class ARGS>
+__device__ __forceinline__ void warm_and_stage_tables(const ARGS& K, SharedTables& S) {
+    warm_kernarg<(MIXED == 1 ? 0 : (int)offsetof(ARGS, arms) + (int)sizeof(ArmC))>();
+    stage_tables<(MIXED != 0)>(S, K.arms);
+}
+// An AccK (or a type derived from it) over the arms of the kernel's own argument block ARGS, read through the kernarg segment
+template <class ACC, class ARGS>
+__device__ __forceinline__ ACC kernarg_acc(SharedTables& S, int slot) {
+    ACC A;
+    A.k = (KConst)&((const __attribute__((address_space(4))) ARGS*)__builtin_amdgcn_kernarg_segment_ptr())->arms[0].v[0];
+    A.lds = (LdsConst)S.arm[slot]; A.utab = (UnitAtanTab)&S.utab[0][0];
+    return A;
+}
+__device__ __forceinline__ void reach_invalid_input(Reach& r) {  // rsik.h "Rows that are not numbers": the reference raises (S:580) or projects an infinity
+    r.ok = false; r.state = RSIK_STATE_INVALID_INPUT; r.i0 = r.i1 = __builtin_nan("");
+}
+// the per-pose outputs of is_reachable: interval, reachable, state (each optional)
+template <class ARGS>
+__device__ __forceinline__ void store_reach(const ARGS& K, bool live, int64_t tile0, unsigned t, const Reach& r) {
+    if (!live) return;
+    if (K.interval) {
+        const f64x2 iv = {r.i0, r.i1};  // one 16-B store per lane
+        st_stream(reinterpret_cast<f64x2*>(K.interval + 2 * tile0) + t, iv);
+    }
+    if (K.reachable) st_stream(K.reachable + tile0 + t, (uint8_t)(r.ok ? 1 : 0));
+    if (K.state) st_stream(K.state + tile0 + t, (uint8_t)r.state);
+}
+
 // One workgroup = one tile of kBlock consecutive poses, one pose per lane.  Every global address is a scalar base
 // (column pointer + tile offset, computed on the SALU) plus a small per-lane offset, so the six loads and all the
 // stores share one or two address registers.  Lanes past the end of the batch recompute the last pose; their stores
@@ -278,11 +311,7 @@ __global__ __launch_bounds__(kBlock, RSIK_SOLVE_MIN_WAVES) void solve_kernel(con
     double in[6];
 #pragma unroll
     for (int k = 0; k < 6; k++) in[k] = ld_stream(K.in[k] + tile0 + tt);
-    // (MIXED == 1 takes every constant from LDS: nothing to warm.  Here the warm-up goes BEFORE the staging loads are issued,
-    // in the other kernels between their issue and their use (stage_tables<., WARM>): measured both ways per kernel, config
-    // 2 31.1 vs 31.9 us, config 3 15.9 vs 15.7 us)
-    warm_kernarg<(MIXED == 1 ? 0 : (int)offsetof(SolveArgs, arms) + (int)sizeof(ArmC))>();
-    stage_tables<(MIXED != 0)>(lds_tab, K.arms);
+    warm_and_stage_tables<MIXED>(K, lds_tab);
 #ifdef RSIK_TIMELINE_PROBE
     const uint64_t probe_t1 = __builtin_amdgcn_s_memrealtime();
     uint64_t probe_mid = 0, probe_goal = 0, probe_reach = 0;
@@ -290,8 +319,7 @@ __global__ __launch_bounds__(kBlock, RSIK_SOLVE_MIN_WAVES) void solve_kernel(con
 #else
 #define RSIK_SOLVE_PROBE(v) do { } while (0)
 #endif
-    const AccK<MIXED> A{(KConst)&((const __attribute__((address_space(4))) SolveArgs*)__builtin_amdgcn_kernarg_segment_ptr())->arms[0].v[0],
-                        (LdsConst)lds_tab.arm[(MIXED != 0 && K.arm[tile0 + tt] != 0) ? 1 : 0], (UnitAtanTab)&lds_tab.utab[0][0]};
+    const AccK<MIXED> A = kernarg_acc<AccK<MIXED>, SolveArgs>(lds_tab, (MIXED != 0 && K.arm[tile0 + tt] != 0) ? 1 : 0);
     double* lds_wave = lds[wave];
 
     // rsik.h "Rows that are not numbers": judged here, while the six values are at hand (further down it would keep them all alive)
@@ -310,11 +338,7 @@ __global__ __launch_bounds__(kBlock, RSIK_SOLVE_MIN_WAVES) void solve_kernel(con
     RSIK_SOLVE_PROBE(probe_goal);
     Reach r = reach_g<false, false>(A, pos, G.woff);
     RSIK_SOLVE_PROBE(probe_reach);
-    if (RSIK_RARE(invalid)) {  // where the reference raises (S:580) or projects an infinity
-        r.ok = false;
-        r.state = RSIK_STATE_INVALID_INPUT;
-        r.i0 = r.i1 = __builtin_nan("");
-    }
+    if (RSIK_RARE(invalid)) reach_invalid_input(r);
     RSIK_MARK("after_reach");
 
     // joints [64,7] and elbow [64,3] of the wave are staged in LDS (row-major, as they go to HBM) by whichever branch
@@ -375,14 +399,7 @@ __global__ __launch_bounds__(kBlock, RSIK_SOLVE_MIN_WAVES) void solve_kernel(con
             if (want_elbow) flush_rows<3>(K.elbow, wave_base, K.n, lane, lds_wave + 64 * 7);
         }
     }
-    if (live) {
-        if (K.interval) {
-            const f64x2 iv = {r.i0, r.i1};  // one 16-B store per lane
-            st_stream(reinterpret_cast<f64x2*>(K.interval + 2 * tile0) + t, iv);
-        }
-        if (K.reachable) st_stream(K.reachable + tile0 + t, (uint8_t)(r.ok ? 1 : 0));
-        if (K.state) st_stream(K.state + tile0 + t, (uint8_t)r.state);
-    }
+    store_reach(K, live, tile0, t, r);
 #ifdef RSIK_TIMELINE_PROBE
     // diagnostic build only (scripts/timeline_probe.py): lanes 0-2 of every wave overwrite their interval rows with
     // (start, tables staged), (outputs staged, stores issued), (HW_ID, XCC_ID)

@@ -32,7 +32,7 @@ template <bool MIXED>
 __global__ __launch_bounds__(kBlock) void reach_state_kernel(const StateArgs K) {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     __shared__ SharedTables lds_tab;
-        stage_tables<MIXED, (int)offsetof(StateArgs, arms) + (MIXED ? 0 : (int)sizeof(ArmC))>(lds_tab, K.arms);
+    stage_tables<MIXED, (int)offsetof(StateArgs, arms) + (MIXED ? 0 : (int)sizeof(ArmC))>(lds_tab, K.arms);
     if (i >= K.n) return;
     const Acc<MIXED> A = make_acc<MIXED>(K.arms, MIXED ? (K.arm[i] != 0) : false, lds_tab);
     V3 pos = {K.in[0][i], K.in[1][i], K.in[2][i]};
@@ -41,9 +41,7 @@ __global__ __launch_bounds__(kBlock) void reach_state_kernel(const StateArgs K) 
     const bool invalid = !all_finite(in6);
     Rot Rg = rot_from_euler(e0, e1, e2);
     Reach r = K.no_limits ? reach<true>(A, pos, Rg) : reach<false>(A, pos, Rg);
-    if (RSIK_RARE(invalid)) {  // rsik.h "Rows that are not numbers": the solver object stays as it was
-        r.ok = false; r.state = RSIK_STATE_INVALID_INPUT; r.stage = 0; r.i0 = r.i1 = __builtin_nan("");
-    }
+    if (RSIK_RARE(invalid)) { reach_invalid_input(r); r.stage = 0; }  // (stage 0: the solver object stays as it was)
     double* S = K.solver_state + i * RSIK_SOLVER_STATE_STRIDE;
     if (r.stage >= 1) {
         S[0] = r.pos.x; S[1] = r.pos.y; S[2] = r.pos.z; S[3] = e0; S[4] = e1; S[5] = e2;
@@ -77,7 +75,7 @@ template <bool MIXED>
 __global__ __launch_bounds__(kBlock) void joints_state_kernel(const StateArgs K) {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     __shared__ SharedTables lds_tab;
-        stage_tables<MIXED, (int)offsetof(StateArgs, arms) + (MIXED ? 0 : (int)sizeof(ArmC))>(lds_tab, K.arms);
+    stage_tables<MIXED, (int)offsetof(StateArgs, arms) + (MIXED ? 0 : (int)sizeof(ArmC))>(lds_tab, K.arms);
     if (i >= K.n) return;
     const Acc<MIXED> A = make_acc<MIXED>(K.arms, MIXED ? (K.arm[i] != 0) : false, lds_tab);
     double* S = K.solver_state + i * RSIK_SOLVER_STATE_STRIDE;

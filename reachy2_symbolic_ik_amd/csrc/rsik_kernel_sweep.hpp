@@ -62,10 +62,8 @@ __global__ __launch_bounds__(kBlock, RSIK_SWEEP_MIN_WAVES) void solve_sweep_kern
     double in[6];
 #pragma unroll
     for (int k = 0; k < 6; k++) in[k] = ld_stream(K.in[k] + tile0 + tt);
-    warm_kernarg<(MIXED == 1 ? 0 : (int)offsetof(SweepArgs, arms) + (int)sizeof(ArmC))>();
-    stage_tables<(MIXED != 0)>(lds_tab, K.arms);
-    const AccSweep<MIXED> A{{(KConst)&((const __attribute__((address_space(4))) SweepArgs*)__builtin_amdgcn_kernarg_segment_ptr())->arms[0].v[0],
-                             (LdsConst)lds_tab.arm[(MIXED != 0 && K.arm[tile0 + tt] != 0) ? 1 : 0], (UnitAtanTab)&lds_tab.utab[0][0]}};
+    warm_and_stage_tables<MIXED>(K, lds_tab);
+    const AccSweep<MIXED> A = kernarg_acc<AccSweep<MIXED>, SweepArgs>(lds_tab, (MIXED != 0 && K.arm[tile0 + tt] != 0) ? 1 : 0);
     double* lds_wave = lds[wave];
 
     const bool invalid = !all_finite(in);  // rsik.h "Rows that are not numbers"
@@ -78,20 +76,8 @@ __global__ __launch_bounds__(kBlock, RSIK_SWEEP_MIN_WAVES) void solve_sweep_kern
         G = make_goal(A, Rg);
     }
     Reach r = reach_g<false, false>(A, pos, G.woff);
-    if (RSIK_RARE(invalid)) {
-        r.ok = false;
-        r.state = RSIK_STATE_INVALID_INPUT;
-        r.i0 = r.i1 = __builtin_nan("");
-    }
-
-    if (live) {
-        if (K.interval) {
-            const f64x2 iv = {r.i0, r.i1};
-            st_stream(reinterpret_cast<f64x2*>(K.interval + 2 * tile0) + t, iv);
-        }
-        if (K.reachable) st_stream(K.reachable + tile0 + t, (uint8_t)(r.ok ? 1 : 0));
-        if (K.state) st_stream(K.state + tile0 + t, (uint8_t)r.state);
-    }
+    if (RSIK_RARE(invalid)) reach_invalid_input(r);
+    store_reach(K, live, tile0, t, r);
     if (rows <= (unsigned)(wave * 64)) return;  // a wave past the end of the batch (wave-uniform; no barrier follows)
 
     const bool want_elbow = K.elbow != nullptr;

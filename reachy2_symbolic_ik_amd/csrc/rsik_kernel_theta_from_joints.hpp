@@ -113,8 +113,7 @@ __global__ __launch_bounds__(kBlock) void theta_from_joints_kernel(const ThetaFr
     __shared__ SharedTables lds_tab;
     stage_tables<(MIXED != 0), (MIXED == 1 ? 0 : (int)offsetof(ThetaFromJointsArgs, arms) + (int)sizeof(ArmC))>(lds_tab, K.arms);
     const int slot = (MIXED != 0 && K.arm[ii] != 0) ? 1 : 0;
-    const AccK<MIXED> A{(KConst)&((const __attribute__((address_space(4))) ThetaFromJointsArgs*)__builtin_amdgcn_kernarg_segment_ptr())->arms[0].v[0],
-                        (LdsConst)lds_tab.arm[slot], (UnitAtanTab)&lds_tab.utab[0][0]};
+    const AccK<MIXED> A = kernarg_acc<AccK<MIXED>, ThetaFromJointsArgs>(lds_tab, slot);
 
     double cur[7];
 #pragma unroll

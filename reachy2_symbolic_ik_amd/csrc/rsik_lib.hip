@@ -1,6 +1,9 @@
 // rsik_lib.hip — the C ABI of include/rsik.h: context, argument checks and launches.  The kernels (gfx950) live in the
 // rsik_kernel_*.hpp files next to it, the per-pose mathematics in rsik_device.hpp / rsik_math.hpp, the host-side scheduler of
 // rsik_control_continuous_run in rsik_cont_run.hpp.
+// Every launching entry point reads: its own checks, in its own order (the return code and the message that wins are part of the
+// ABI), fill the kernel's argument block K, launch_begin, one launch line, launch_end.  What they share is below the memcpy entry
+// points: check_arms, bind_arms, copy_cols, launch_form / tip_on_z, launch_dims / launch_begin / launch_end.
 //
 // Kernel shape: one pose per lane, 256-thread workgroups (4 wave64), SoA float64 inputs so that
 // every global load is a fully coalesced 512-B wave access; the [n,7] / [n,3] row outputs are
@@ -99,12 +102,26 @@ static int hip_fail(rsik_ctx* ctx, hipError_t e, const char* what) {
     } while (0)
 
 // Runtime values as template arguments: with_bool(b, f) calls f(std::true_type()) or f(std::false_type()), with_int3(i, f) calls
-// f(std::integral_constant<int, i>()) for i = 0, 1, 2.  The launches nest them: every kernel has one launch line.
+// f(std::integral_constant<int, i>()) for i = 0, 1, 2.  The launches nest them, so that every kernel template has one launch line
+// (the one exception: cont_theta_kernel in rsik_cont_run.hpp, whose specialised steps exist for single-arm launches only).
 template <class F>
 static void with_bool(bool b, F&& f) { if (b) f(std::true_type()); else f(std::false_type()); }
 template <class F>
 static void with_int3(int i, F&& f) {
     if (i == 0) f(std::integral_constant<int, 0>()); else if (i == 1) f(std::integral_constant<int, 1>()); else f(std::integral_constant<int, 2>());
+}
+
+// A column table of the ABI (`count` device pointers): refuses a NULL table ("<table> is NULL") or a NULL column ("<a_column> is
+// NULL"), copies the pointers otherwise.  (An entry point that refuses its NULL table earlier, together with other pointers,
+// keeps that check and its message.)  A template: outside the extern "C" block.
+template <class T>
+static int copy_cols(rsik_ctx* ctx, const char* who, const char* table, const char* a_column, T* const* src, T** dst, int count) {
+    if (!src) return fail(ctx, RSIK_E_INVALID, std::string(who) + ": " + table + " is NULL");
+    for (int k = 0; k < count; k++) {
+        if (!src[k]) return fail(ctx, RSIK_E_INVALID, std::string(who) + ": " + a_column + " is NULL");
+        dst[k] = src[k];
+    }
+    return RSIK_OK;
 }
 
 static bool stream_is_capturing(hipStream_t stream) {
@@ -116,12 +133,19 @@ static void free_all(std::vector<void*>& device_blocks) {
     device_blocks.clear();
 }
 
-// mixed launch (an arm byte per row): do the two blocks agree in everything that has no handedness (arm_const_is_sided)?
-static bool arms_mirror(const rsik_ctx* ctx, const rsik::ArmC (&arms)[2], const uint8_t* arm) {
-    bool mirror = arm != nullptr && !ctx->options[RSIK_OPT_NO_MIRROR];
+// The accessor form of the solve, sweep and theta-from-joints kernels (AccK): 0 one arm for the launch, 1 mixed (an arm byte per
+// row), 2 mixed and the two blocks agree in everything that has no handedness (arm_const_is_sided)
+static int launch_form(const rsik_ctx* ctx, const rsik::ArmC (&arms)[2], const uint8_t* arm) {
+    if (!arm) return 0;
+    bool mirror = !ctx->options[RSIK_OPT_NO_MIRROR];
     for (int i = 0; mirror && i < RSIK_ARM_CONSTS_COUNT; i++)
         if (!rsik::arm_const_is_sided(i) && std::memcmp(&arms[0].v[i], &arms[1].v[i], sizeof(double)) != 0) mirror = false;
-    return mirror;
+    return mirror ? 2 : 1;
+}
+// tip offset along the goal z axis only (the default arm / the URDF): the specialised goal stage of solve and sweep applies
+static bool tip_on_z(const rsik_ctx* ctx, const rsik::ArmC (&arms)[2]) {
+    return arms[0].v[RSIK_C_TIPL] == 0.0 && arms[0].v[RSIK_C_TIPL + 1] == 0.0 &&
+           arms[1].v[RSIK_C_TIPL] == 0.0 && arms[1].v[RSIK_C_TIPL + 1] == 0.0 && !ctx->options[RSIK_OPT_NO_TIPZ];
 }
 
 // Can the singularity-plane half of is_elbow_ok (utils.py:459-464) fail at all?  The elbow lies on the sphere of
@@ -210,8 +234,18 @@ int rsik_set_arm(rsik_ctx* ctx, int arm, const double* consts_host, int count) {
 int rsik_set_option(rsik_ctx* ctx, int option, int value) {
     if (!ctx) return RSIK_E_INVALID;
     if (option < 0 || option >= RSIK_OPT_COUNT) return fail(ctx, RSIK_E_INVALID, "rsik_set_option: unknown option");
-    static const int max_value[RSIK_OPT_COUNT] = {RSIK_EULER_NEVER, 2, 1, 1, RSIK_CONT_RUN_STEPS, 65535, 127, 1};
-    if (value < 0 || value > max_value[option]) return fail(ctx, RSIK_E_INVALID, "rsik_set_option: value out of range");
+    int max_value = 0;  // by name: a new option cannot shift the others, and one without a case takes no value but 0
+    switch (option) {
+        case RSIK_OPT_EULER_ROUNDTRIP: max_value = RSIK_EULER_NEVER; break;
+        case RSIK_OPT_SWEEP_MODE: max_value = 2; break;
+        case RSIK_OPT_NO_TIPZ: max_value = 1; break;
+        case RSIK_OPT_NO_MIRROR: max_value = 1; break;
+        case RSIK_OPT_CONT_RUN_MODE: max_value = RSIK_CONT_RUN_STEPS; break;
+        case RSIK_OPT_CONT_BLOCK_STEPS: max_value = 65535; break;
+        case RSIK_OPT_CONT_PHASED_VARIANT: max_value = 127; break;
+        case RSIK_OPT_CONT_GOALS_RESIDENT: max_value = 1; break;
+    }
+    if (value < 0 || value > max_value) return fail(ctx, RSIK_E_INVALID, "rsik_set_option: value out of range");
     ctx->options[option] = value;
     return RSIK_OK;
 }
@@ -267,6 +301,21 @@ static int launch_dims(rsik_ctx* ctx, int64_t n, dim3* grid, const char* who, in
     *grid = dim3((unsigned)blocks);
     return RSIK_OK;
 }
+// what brackets every launch: the context's device and the grid for n rows, then the launch's own error
+static int launch_begin(rsik_ctx* ctx, int64_t n, dim3* grid, const char* who, int threads = rsik::kBlock) {
+    RSIK_HIP(ctx, hipSetDevice(ctx->device));
+    return launch_dims(ctx, n, grid, who, threads);
+}
+static int launch_end(rsik_ctx* ctx) {
+    RSIK_HIP(ctx, hipGetLastError());
+    return RSIK_OK;
+}
+
+// K.arms of a launch check_arms has passed: slot 0 = r, slot 1 = l with per-pose arm ids, the one arm in both slots without
+static int slot_arm(const uint8_t* arm, int arm_uniform, int slot) { return arm ? slot : arm_uniform; }
+static void bind_arms(const rsik_ctx* ctx, const uint8_t* arm, int arm_uniform, rsik::ArmC (&arms)[2]) {
+    for (int slot = 0; slot < 2; slot++) arms[slot] = ctx->arms[slot_arm(arm, arm_uniform, slot)];
+}
 
 // rsik_solve (previous_rows == NULL: previous_joints_host for every pose) and rsik_solve_rows (previous_rows: one device row per pose)
 static int solve_impl(rsik_ctx* ctx, const char* who, int64_t n, const double* const pose_soa[6], const uint8_t* arm, int arm_uniform,
@@ -281,32 +330,21 @@ static int solve_impl(rsik_ctx* ctx, const char* who, int64_t n, const double* c
     int rc = check_arms(ctx, arm, arm_uniform, who);
     if (rc != RSIK_OK) return rc;
     if (n == 0) return RSIK_OK;
-    if (!pose_soa) return fail(ctx, RSIK_E_INVALID, w + ": pose_soa is NULL");
     rsik::SolveArgs K;
     K.n = n;
-    for (int k = 0; k < 6; k++) {
-        if (!pose_soa[k]) return fail(ctx, RSIK_E_INVALID, w + ": a pose_soa column is NULL");
-        K.in[k] = pose_soa[k];
-    }
+    if ((rc = copy_cols(ctx, who, "pose_soa", "a pose_soa column", pose_soa, K.in, 6)) != RSIK_OK) return rc;
     K.arm = arm;
     K.theta_policy = theta_policy;
     K.theta_in = theta_in;
     if (previous_rows) K.prev_rows = previous_rows;  // (shares its kernarg bytes with K.prev)
     else for (int k = 0; k < 7; k++) K.prev[k] = previous_joints_host ? previous_joints_host[k] : 0.0;
     K.joints = joints; K.interval = interval; K.elbow = elbow; K.reachable = reachable; K.state = state;
-    if (arm) { K.arms[0] = ctx->arms[0]; K.arms[1] = ctx->arms[1]; }
-    else { K.arms[0] = ctx->arms[arm_uniform]; K.arms[1] = ctx->arms[arm_uniform]; }
-    RSIK_HIP(ctx, hipSetDevice(ctx->device));
+    bind_arms(ctx, arm, arm_uniform, K.arms);
     dim3 grid, block(rsik::kBlock);
-    if ((rc = launch_dims(ctx, n, &grid, who)) != RSIK_OK) return rc;
-    // tip offset along the goal z axis only (the default arm / the URDF): the specialised goal stage applies
-    const bool tipz = K.arms[0].v[RSIK_C_TIPL] == 0.0 && K.arms[0].v[RSIK_C_TIPL + 1] == 0.0 &&
-                      K.arms[1].v[RSIK_C_TIPL] == 0.0 && K.arms[1].v[RSIK_C_TIPL + 1] == 0.0 && !ctx->options[RSIK_OPT_NO_TIPZ];
-    const int form = arm ? (arms_mirror(ctx, K.arms, arm) ? 2 : 1) : 0;
-    with_int3(form, [&](auto FORM) { with_bool(tipz, [&](auto TIPZ) { with_bool(previous_rows != nullptr, [&](auto PREV_ROWS) {
+    if ((rc = launch_begin(ctx, n, &grid, who)) != RSIK_OK) return rc;
+    with_int3(launch_form(ctx, K.arms, arm), [&](auto FORM) { with_bool(tip_on_z(ctx, K.arms), [&](auto TIPZ) { with_bool(previous_rows != nullptr, [&](auto PREV_ROWS) {
         hipLaunchKernelGGL((rsik::solve_kernel<FORM(), TIPZ(), PREV_ROWS()>), grid, block, 0, ctx->stream, K); }); }); });
-    RSIK_HIP(ctx, hipGetLastError());
-    return RSIK_OK;
+    return launch_end(ctx);
 }
 
 int rsik_solve(rsik_ctx* ctx, int64_t n, const double* const pose_soa[6], const uint8_t* arm, int arm_uniform,
@@ -347,10 +385,7 @@ int rsik_solve_sweep(rsik_ctx* ctx, int64_t n, const double* const pose_soa[6], 
     if (!joints) return fail(ctx, RSIK_E_INVALID, w + ": joints is NULL");
     rsik::SweepArgs K;
     K.n = n;
-    for (int k = 0; k < 6; k++) {
-        if (!pose_soa[k]) return fail(ctx, RSIK_E_INVALID, w + ": a pose_soa column is NULL");
-        K.in[k] = pose_soa[k];
-    }
+    if ((rc = copy_cols(ctx, who, "pose_soa", "a pose_soa column", pose_soa, K.in, 6)) != RSIK_OK) return rc;
     K.arm = arm;
     K.theta_policy = theta_policy;
     K.n_theta = n_theta;
@@ -360,19 +395,12 @@ int rsik_solve_sweep(rsik_ctx* ctx, int64_t n, const double* const pose_soa[6], 
     else for (int k = 0; k < 7; k++) K.prev[k] = 0.0;
     K.joints = joints; K.elbow = elbow; K.projected = projected; K.theta = theta;
     K.interval = interval; K.reachable = reachable; K.state = state;
-    if (arm) { K.arms[0] = ctx->arms[0]; K.arms[1] = ctx->arms[1]; }
-    else { K.arms[0] = ctx->arms[arm_uniform]; K.arms[1] = ctx->arms[arm_uniform]; }
-    RSIK_HIP(ctx, hipSetDevice(ctx->device));
+    bind_arms(ctx, arm, arm_uniform, K.arms);
     dim3 grid, block(rsik::kBlock);
-    if ((rc = launch_dims(ctx, n, &grid, who)) != RSIK_OK) return rc;
-    // the kernel variant is chosen as rsik_solve chooses its own
-    const bool tipz = K.arms[0].v[RSIK_C_TIPL] == 0.0 && K.arms[0].v[RSIK_C_TIPL + 1] == 0.0 &&
-                      K.arms[1].v[RSIK_C_TIPL] == 0.0 && K.arms[1].v[RSIK_C_TIPL + 1] == 0.0 && !ctx->options[RSIK_OPT_NO_TIPZ];
-    const int form = arm ? (arms_mirror(ctx, K.arms, arm) ? 2 : 1) : 0;
-    with_int3(form, [&](auto FORM) { with_bool(tipz, [&](auto TIPZ) { with_bool(previous_joints != nullptr, [&](auto PREV_ROWS) {
+    if ((rc = launch_begin(ctx, n, &grid, who)) != RSIK_OK) return rc;
+    with_int3(launch_form(ctx, K.arms, arm), [&](auto FORM) { with_bool(tip_on_z(ctx, K.arms), [&](auto TIPZ) { with_bool(previous_joints != nullptr, [&](auto PREV_ROWS) {
         hipLaunchKernelGGL((rsik::solve_sweep_kernel<FORM(), TIPZ(), PREV_ROWS()>), grid, block, 0, ctx->stream, K); }); }); });
-    RSIK_HIP(ctx, hipGetLastError());
-    return RSIK_OK;
+    return launch_end(ctx);
 }
 
 // Python float modulo (sign of the divisor), used for the l-arm limit wrap (C:243-250).
@@ -421,10 +449,7 @@ static int control_discrete_impl(rsik_ctx* ctx, const char* who, int64_t n, cons
     if (!m12_soa || !joints) return fail(ctx, RSIK_E_INVALID, w + ": m12_soa / joints is NULL");
     rsik::DiscreteArgs K;
     K.n = n;
-    for (int k = 0; k < 12; k++) {
-        if (!m12_soa[k]) return fail(ctx, RSIK_E_INVALID, w + ": an m12_soa column is NULL");
-        K.in[k] = m12_soa[k];
-    }
+    if ((rc = copy_cols(ctx, who, "m12_soa", "an m12_soa column", m12_soa, K.in, 12)) != RSIK_OK) return rc;
     K.arm = arm;
     K.nb = nb_search_points;
     int lg = 0;
@@ -435,7 +460,7 @@ static int control_discrete_impl(rsik_ctx* ctx, const char* who, int64_t n, cons
     // one round = every workgroup resident at once: 4 workgroups per compute unit (their LDS slabs)
     K.stagger = n <= (int64_t)ctx->compute_units * 4 * rsik::kDiscBlock ? 1 : 0;
     for (int slot = 0; slot < 2; slot++) {
-        const int a = arm ? slot : arm_uniform;
+        const int a = slot_arm(arm, arm_uniform, slot);
         control_limits(a, constrained_mode, preferred_theta, K.lim[slot], &K.pref[slot]);
         K.pref_cs[slot] = std::cos(K.pref[slot]);  // np.cos / np.sin of the reference (U:359-360), once per launch
         K.pref_sn[slot] = std::sin(K.pref[slot]);
@@ -446,23 +471,19 @@ static int control_discrete_impl(rsik_ctx* ctx, const char* who, int64_t n, cons
                 K.prev_sn[slot][k] = std::sin(K.prev_sol[slot][4 + k]);
             }
         }
-        K.arms[slot] = ctx->arms[a];
     }
-    const bool plane_binds = singularity_plane_binds(K.arms);
+    bind_arms(ctx, arm, arm_uniform, K.arms);
     if (previous_rows) K.prev_rows = previous_rows;  // (shares its kernarg bytes with K.prev_sol)
     K.current_joints = current_joints;
     K.max_angle = orbita3d_max_angle;
     K.cos_max = std::cos(orbita3d_max_angle);
     K.sin_max = std::sin(orbita3d_max_angle);
     K.joints = joints; K.reachable = reachable; K.state = state; K.emergency = emergency;
-    RSIK_HIP(ctx, hipSetDevice(ctx->device));
     dim3 grid, block(rsik::kDiscBlock);
-    rc = launch_dims(ctx, n, &grid, who, rsik::kDiscBlock);
-    if (rc != RSIK_OK) return rc;
-    with_bool(arm != nullptr, [&](auto MIXED) { with_bool(plane_binds, [&](auto PLANE) { with_bool(previous_rows != nullptr, [&](auto PREV_ROWS) {
+    if ((rc = launch_begin(ctx, n, &grid, who, rsik::kDiscBlock)) != RSIK_OK) return rc;
+    with_bool(arm != nullptr, [&](auto MIXED) { with_bool(singularity_plane_binds(K.arms), [&](auto PLANE) { with_bool(previous_rows != nullptr, [&](auto PREV_ROWS) {
         hipLaunchKernelGGL((rsik::control_discrete_kernel<MIXED(), PLANE(), PREV_ROWS()>), grid, block, 0, ctx->stream, K); }); }); });
-    RSIK_HIP(ctx, hipGetLastError());
-    return RSIK_OK;
+    return launch_end(ctx);
 }
 
 int rsik_control_discrete(rsik_ctx* ctx, int64_t n, const double* const m12_soa[12], const uint8_t* arm,
@@ -502,7 +523,7 @@ static int fill_continuous(rsik_ctx* ctx, const char* who, rsik::ContinuousArgs&
     std::memset(&K, 0, sizeof K);
     K.n = n;
     K.first_timed_out = first_timed_out;
-    for (int k = 0; k < 12; k++) {
+    for (int k = 0; k < 12; k++) {  // (the two tables column by column: which refusal wins is this loop's order, not copy_cols')
         if (!m12_soa[k]) return fail(ctx, RSIK_E_INVALID, std::string(who) + ": an m12_soa column is NULL");
         K.in[k] = m12_soa[k];
         K.cur_pose[k] = current_pose_m12_soa ? current_pose_m12_soa[k] : nullptr;
@@ -513,13 +534,13 @@ static int fill_continuous(rsik_ctx* ctx, const char* who, rsik::ContinuousArgs&
     K.timed_out = timed_out;
     K.euler_roundtrip = ctx->options[RSIK_OPT_EULER_ROUNDTRIP];
     for (int slot = 0; slot < 2; slot++) {
-        const int a = arm ? slot : arm_uniform;
+        const int a = slot_arm(arm, arm_uniform, slot);
         control_limits(a, constrained_mode, preferred_theta, K.lim[slot], &K.pref_arg[slot]);
         K.pref_self[slot] = preferred_theta_self_host[a];
         K.pref_self_cs[slot] = std::cos(K.pref_self[slot]);  // np.cos / np.sin of the reference (U:359-360)
         K.pref_self_sn[slot] = std::sin(K.pref_self[slot]);
-        K.arms[slot] = ctx->arms[a];
     }
+    bind_arms(ctx, arm, arm_uniform, K.arms);
     K.d_theta_max = d_theta_max;
     K.current_joints = current_joints;
     K.max_angle = orbita3d_max_angle;
@@ -537,22 +558,16 @@ int rsik_control_continuous_step(rsik_ctx* ctx, int64_t n, const double* const m
                                  uint8_t* state) {
     if (!ctx) return RSIK_E_INVALID;
     if (n < 0) return fail(ctx, RSIK_E_INVALID, "rsik_control_continuous_step: n < 0");
-    if (n == 0) {
-        int rc0 = check_arms(ctx, arm, arm_uniform, "rsik_control_continuous_step");
-        return rc0;
-    }
+    if (n == 0) return check_arms(ctx, arm, arm_uniform, "rsik_control_continuous_step");
     rsik::ContinuousArgs K;
     int rc = fill_continuous(ctx, "rsik_control_continuous_step", K, n, m12_soa, current_pose_m12_soa, arm, arm_uniform, timed_out,
                              0, preferred_theta, preferred_theta_self_host, constrained_mode, d_theta_max, current_joints,
                              orbita3d_max_angle, cont_state, joints, reachable, state);
     if (rc != RSIK_OK) return rc;
-    RSIK_HIP(ctx, hipSetDevice(ctx->device));
     dim3 grid, block(rsik::kBlock);
-    rc = launch_dims(ctx, n, &grid, "rsik_control_continuous_step");
-    if (rc != RSIK_OK) return rc;
+    if ((rc = launch_begin(ctx, n, &grid, "rsik_control_continuous_step")) != RSIK_OK) return rc;
     launch_continuous_step(ctx, arm, K, grid, block);
-    RSIK_HIP(ctx, hipGetLastError());
-    return RSIK_OK;
+    return launch_end(ctx);
 }
 
 #include "rsik_cont_run.hpp"
@@ -566,21 +581,13 @@ int rsik_matrix_to_pose(rsik_ctx* ctx, int64_t n, const double* const m12_soa[12
     rsik::MatrixToPoseArgs K;
     K.n = n;
     K.identity_shortcut = identity_shortcut;
-    for (int k = 0; k < 12; k++) {
-        if (!m12_soa[k]) return fail(ctx, RSIK_E_INVALID, "rsik_matrix_to_pose: an m12_soa column is NULL");
-        K.in[k] = m12_soa[k];
-    }
-    for (int k = 0; k < 6; k++) {
-        if (!pose_soa[k]) return fail(ctx, RSIK_E_INVALID, "rsik_matrix_to_pose: a pose_soa column is NULL");
-        K.out[k] = pose_soa[k];
-    }
-    RSIK_HIP(ctx, hipSetDevice(ctx->device));
-    dim3 grid, block(rsik::kBlock);
-    int rc = launch_dims(ctx, n, &grid, "rsik_matrix_to_pose");
+    int rc = copy_cols(ctx, "rsik_matrix_to_pose", "m12_soa", "an m12_soa column", m12_soa, K.in, 12);
     if (rc != RSIK_OK) return rc;
+    if ((rc = copy_cols(ctx, "rsik_matrix_to_pose", "pose_soa", "a pose_soa column", pose_soa, K.out, 6)) != RSIK_OK) return rc;
+    dim3 grid, block(rsik::kBlock);
+    if ((rc = launch_begin(ctx, n, &grid, "rsik_matrix_to_pose")) != RSIK_OK) return rc;
     hipLaunchKernelGGL(rsik::matrix_to_pose_kernel, grid, block, 0, ctx->stream, K);
-    RSIK_HIP(ctx, hipGetLastError());
-    return RSIK_OK;
+    return launch_end(ctx);
 }
 
 static int fill_state_args(rsik_ctx* ctx, rsik::StateArgs* K, int64_t n, const uint8_t* arm, int arm_uniform,
@@ -591,7 +598,7 @@ static int fill_state_args(rsik_ctx* ctx, rsik::StateArgs* K, int64_t n, const u
     std::memset(K, 0, sizeof *K);
     K->n = n;
     K->arm = arm;
-    for (int slot = 0; slot < 2; slot++) K->arms[slot] = ctx->arms[arm ? slot : arm_uniform];
+    bind_arms(ctx, arm, arm_uniform, K->arms);
     return RSIK_OK;
 }
 
@@ -603,20 +610,13 @@ int rsik_reach_state(rsik_ctx* ctx, int64_t n, const double* const pose_soa[6], 
     if (rc != RSIK_OK) return rc;
     if (n == 0) return RSIK_OK;
     if (!pose_soa || !solver_state) return fail(ctx, RSIK_E_INVALID, "rsik_reach_state: pose_soa / solver_state is NULL");
-    for (int k = 0; k < 6; k++) {
-        if (!pose_soa[k]) return fail(ctx, RSIK_E_INVALID, "rsik_reach_state: a pose_soa column is NULL");
-        K.in[k] = pose_soa[k];
-    }
+    if ((rc = copy_cols(ctx, "rsik_reach_state", "pose_soa", "a pose_soa column", pose_soa, K.in, 6)) != RSIK_OK) return rc;
     K.no_limits = no_limits ? 1 : 0;
     K.solver_state = solver_state; K.interval = interval; K.reachable = reachable; K.state = state;
-    RSIK_HIP(ctx, hipSetDevice(ctx->device));
     dim3 grid, block(rsik::kBlock);
-    rc = launch_dims(ctx, n, &grid, "rsik_reach_state");
-    if (rc != RSIK_OK) return rc;
-    if (arm) hipLaunchKernelGGL(rsik::reach_state_kernel<true>, grid, block, 0, ctx->stream, K);
-    else hipLaunchKernelGGL(rsik::reach_state_kernel<false>, grid, block, 0, ctx->stream, K);
-    RSIK_HIP(ctx, hipGetLastError());
-    return RSIK_OK;
+    if ((rc = launch_begin(ctx, n, &grid, "rsik_reach_state")) != RSIK_OK) return rc;
+    with_bool(arm != nullptr, [&](auto MIXED) { hipLaunchKernelGGL(rsik::reach_state_kernel<MIXED()>, grid, block, 0, ctx->stream, K); });
+    return launch_end(ctx);
 }
 
 int rsik_joints_from_state(rsik_ctx* ctx, int64_t n, double* solver_state, const uint8_t* arm, int arm_uniform,
@@ -629,14 +629,10 @@ int rsik_joints_from_state(rsik_ctx* ctx, int64_t n, double* solver_state, const
     if (!solver_state || !theta)  // joints may be NULL: the row's slots 24-30 carry them too
         return fail(ctx, RSIK_E_INVALID, "rsik_joints_from_state: solver_state / theta is NULL");
     K.solver_state = solver_state; K.theta = theta; K.prev = previous_joints; K.joints = joints; K.elbow = elbow;
-    RSIK_HIP(ctx, hipSetDevice(ctx->device));
     dim3 grid, block(rsik::kBlock);
-    rc = launch_dims(ctx, n, &grid, "rsik_joints_from_state");
-    if (rc != RSIK_OK) return rc;
-    if (arm) hipLaunchKernelGGL(rsik::joints_state_kernel<true>, grid, block, 0, ctx->stream, K);
-    else hipLaunchKernelGGL(rsik::joints_state_kernel<false>, grid, block, 0, ctx->stream, K);
-    RSIK_HIP(ctx, hipGetLastError());
-    return RSIK_OK;
+    if ((rc = launch_begin(ctx, n, &grid, "rsik_joints_from_state")) != RSIK_OK) return rc;
+    with_bool(arm != nullptr, [&](auto MIXED) { hipLaunchKernelGGL(rsik::joints_state_kernel<MIXED()>, grid, block, 0, ctx->stream, K); });
+    return launch_end(ctx);
 }
 
 int rsik_elbow_from_state(rsik_ctx* ctx, int64_t n, const double* solver_state, const double* theta, double* elbow) {
@@ -649,13 +645,11 @@ int rsik_elbow_from_state(rsik_ctx* ctx, int64_t n, const double* solver_state, 
     std::memset(&K, 0, sizeof K);
     K.n = n;
     K.solver_state = const_cast<double*>(solver_state); K.theta = theta; K.elbow = elbow;
-    RSIK_HIP(ctx, hipSetDevice(ctx->device));
     dim3 grid, block(rsik::kBlock);
-    int rc = launch_dims(ctx, n, &grid, "rsik_elbow_from_state");
+    int rc = launch_begin(ctx, n, &grid, "rsik_elbow_from_state");
     if (rc != RSIK_OK) return rc;
     hipLaunchKernelGGL(rsik::elbow_state_kernel, grid, block, 0, ctx->stream, K);
-    RSIK_HIP(ctx, hipGetLastError());
-    return RSIK_OK;
+    return launch_end(ctx);
 }
 
 // utils.get_best_theta_to_current_joints for n rows (rsik_kernel_theta_from_joints.hpp)
@@ -667,11 +661,8 @@ static int fill_theta_from_joints(rsik_ctx* ctx, const char* who, rsik::ThetaFro
     K.n = n;
     K.arm = arm;
     K.euler_roundtrip = ctx->options[RSIK_OPT_EULER_ROUNDTRIP];
-    for (int slot = 0; slot < 2; slot++) {
-        const int a = arm ? slot : arm_uniform;
-        K.pref[slot] = preferred_theta_host ? preferred_theta_host[a] : 0.0;
-        K.arms[slot] = ctx->arms[a];
-    }
+    for (int slot = 0; slot < 2; slot++) K.pref[slot] = preferred_theta_host ? preferred_theta_host[slot_arm(arm, arm_uniform, slot)] : 0.0;
+    bind_arms(ctx, arm, arm_uniform, K.arms);
     return RSIK_OK;
 }
 
@@ -690,21 +681,14 @@ int rsik_theta_from_joints(rsik_ctx* ctx, int64_t n, int goal_kind, const double
     if (!goal_soa || !current_joints || !preferred_theta_host || !theta)
         return fail(ctx, RSIK_E_INVALID, std::string(who) + ": goal_soa / current_joints / preferred_theta_host / theta is NULL");
     const bool m12 = goal_kind == RSIK_GOAL_M12;
-    for (int k = 0; k < (m12 ? 12 : 6); k++) {
-        if (!goal_soa[k]) return fail(ctx, RSIK_E_INVALID, std::string(who) + ": a goal_soa column is NULL");
-        K.goal[k] = goal_soa[k];
-    }
+    if ((rc = copy_cols(ctx, who, "goal_soa", "a goal_soa column", goal_soa, K.goal, m12 ? 12 : 6)) != RSIK_OK) return rc;
     K.current_joints = current_joints; K.n_current = 7;
     K.theta = theta; K.joints = joints; K.bracket = bracket; K.distance = distance; K.state = state;
-    RSIK_HIP(ctx, hipSetDevice(ctx->device));
     dim3 grid, block(rsik::kBlock);
-    rc = launch_dims(ctx, n, &grid, who);
-    if (rc != RSIK_OK) return rc;
-    const int form = arm ? (arms_mirror(ctx, K.arms, arm) ? 2 : 1) : 0;
-    with_int3(form, [&](auto FORM) { with_bool(m12, [&](auto M12) {
+    if ((rc = launch_begin(ctx, n, &grid, who)) != RSIK_OK) return rc;
+    with_int3(launch_form(ctx, K.arms, arm), [&](auto FORM) { with_bool(m12, [&](auto M12) {
         hipLaunchKernelGGL((rsik::theta_from_joints_kernel<FORM(), M12()>), grid, block, 0, ctx->stream, K); }); });
-    RSIK_HIP(ctx, hipGetLastError());
-    return RSIK_OK;
+    return launch_end(ctx);
 }
 
 int rsik_theta_from_joints_state(rsik_ctx* ctx, int64_t n, double* solver_state, const uint8_t* arm, int arm_uniform,
@@ -722,14 +706,10 @@ int rsik_theta_from_joints_state(rsik_ctx* ctx, int64_t n, double* solver_state,
         return fail(ctx, RSIK_E_INVALID, std::string(who) + ": solver_state / current_joints / preferred_theta_host / theta is NULL");
     K.solver_state = solver_state; K.current_joints = current_joints; K.n_current = n_current;
     K.theta = theta; K.bracket = bracket;
-    RSIK_HIP(ctx, hipSetDevice(ctx->device));
     dim3 grid, block(rsik::kBlock);
-    rc = launch_dims(ctx, n, &grid, who);
-    if (rc != RSIK_OK) return rc;
-    if (arm) hipLaunchKernelGGL(rsik::theta_from_joints_state_kernel<true>, grid, block, 0, ctx->stream, K);
-    else hipLaunchKernelGGL(rsik::theta_from_joints_state_kernel<false>, grid, block, 0, ctx->stream, K);
-    RSIK_HIP(ctx, hipGetLastError());
-    return RSIK_OK;
+    if ((rc = launch_begin(ctx, n, &grid, who)) != RSIK_OK) return rc;
+    with_bool(arm != nullptr, [&](auto MIXED) { hipLaunchKernelGGL(rsik::theta_from_joints_state_kernel<MIXED()>, grid, block, 0, ctx->stream, K); });
+    return launch_end(ctx);
 }
 
 int rsik_stage(rsik_ctx* ctx, int op, int64_t n, int arm, const double* in, int in_stride, double* out, int out_stride) {
@@ -756,14 +736,12 @@ int rsik_stage(rsik_ctx* ctx, int op, int64_t n, int arm, const double* in, int 
     std::memset(&K, 0, sizeof K);
     K.n = n; K.op = op; K.in = in; K.out = out; K.in_stride = in_stride; K.out_stride = out_stride;
     if (ctx->have_arm[arm]) K.arms[0] = K.arms[1] = ctx->arms[arm];  // (else zeros: the utils helpers read none of it)
-    RSIK_HIP(ctx, hipSetDevice(ctx->device));
     dim3 grid, block(rsik::kBlock);
-    rc = launch_dims(ctx, n, &grid, who);
-    if (rc != RSIK_OK) return rc;
+    if ((rc = launch_begin(ctx, n, &grid, who)) != RSIK_OK) return rc;
+    // (two kernels, not two forms of one: the limiter stages are compiled apart from is_reachable's)
     if (op >= RSIK_STAGE_TEND_TO_PREFERRED_THETA) hipLaunchKernelGGL(rsik::stage_limiter_kernel, grid, block, 0, ctx->stream, K);
     else hipLaunchKernelGGL(rsik::stage_kernel, grid, block, 0, ctx->stream, K);
-    RSIK_HIP(ctx, hipGetLastError());
-    return RSIK_OK;
+    return launch_end(ctx);
 }
 
 static int launch_fk(rsik_ctx* ctx, rsik::FkArgs& K, int64_t n, const uint8_t* arm, int arm_uniform, const char* who) {
@@ -771,15 +749,11 @@ static int launch_fk(rsik_ctx* ctx, rsik::FkArgs& K, int64_t n, const uint8_t* a
     if (rc != RSIK_OK) return rc;
     K.n = n;
     K.arm = arm;
-    for (int slot = 0; slot < 2; slot++) K.arms[slot] = ctx->arms[arm ? slot : arm_uniform];
-    RSIK_HIP(ctx, hipSetDevice(ctx->device));
+    bind_arms(ctx, arm, arm_uniform, K.arms);
     dim3 grid, block(rsik::kBlock);
-    rc = launch_dims(ctx, n, &grid, who);
-    if (rc != RSIK_OK) return rc;
-    if (arm) hipLaunchKernelGGL(rsik::fk_kernel<true>, grid, block, 0, ctx->stream, K);
-    else hipLaunchKernelGGL(rsik::fk_kernel<false>, grid, block, 0, ctx->stream, K);
-    RSIK_HIP(ctx, hipGetLastError());
-    return RSIK_OK;
+    if ((rc = launch_begin(ctx, n, &grid, who)) != RSIK_OK) return rc;
+    with_bool(arm != nullptr, [&](auto MIXED) { hipLaunchKernelGGL(rsik::fk_kernel<MIXED()>, grid, block, 0, ctx->stream, K); });
+    return launch_end(ctx);
 }
 
 int rsik_forward_kinematics(rsik_ctx* ctx, int64_t n, const double* joints, const uint8_t* arm, int arm_uniform,
@@ -805,11 +779,8 @@ int rsik_fk_residual(rsik_ctx* ctx, int64_t n, int goal_kind, const double* cons
     if (!goal_soa || !joints || !err) return fail(ctx, RSIK_E_INVALID, "rsik_fk_residual: goal_soa / joints / err is NULL");
     rsik::FkArgs K;
     std::memset(&K, 0, sizeof K);
-    const int cols = goal_kind == RSIK_GOAL_M12 ? 12 : 6;
-    for (int k = 0; k < cols; k++) {
-        if (!goal_soa[k]) return fail(ctx, RSIK_E_INVALID, "rsik_fk_residual: a goal_soa column is NULL");
-        K.goal[k] = goal_soa[k];
-    }
+    int rc = copy_cols(ctx, "rsik_fk_residual", "goal_soa", "a goal_soa column", goal_soa, K.goal, goal_kind == RSIK_GOAL_M12 ? 12 : 6);
+    if (rc != RSIK_OK) return rc;
     K.goal_kind = goal_kind; K.joints = joints; K.err = err;
     return launch_fk(ctx, K, n, arm, arm_uniform, "rsik_fk_residual");
 }
@@ -824,14 +795,12 @@ int rsik_debug_math(rsik_ctx* ctx, int op, int64_t n, const double* a, const dou
     if (op == 8) {  // clock monitor: n waves, one per 64-thread workgroup so that they spread over the chip
         if (!out1 || n > 4096) return fail(ctx, RSIK_E_INVALID, "rsik_debug_math: op 8 needs out1 and n <= 4096 waves");
         hipLaunchKernelGGL(rsik::clock_monitor_kernel, dim3((unsigned)n), dim3(64), 0, ctx->stream, a, n, out0, out1);
-        RSIK_HIP(ctx, hipGetLastError());
-        return RSIK_OK;
+        return launch_end(ctx);
     }
-    int rc = launch_dims(ctx, n, &grid, "rsik_debug_math");
+    int rc = launch_dims(ctx, n, &grid, "rsik_debug_math");  // (not launch_begin: the device is set above, ahead of op 8's own refusal)
     if (rc != RSIK_OK) return rc;
     hipLaunchKernelGGL(rsik::debug_math_kernel, grid, block, 0, ctx->stream, op, n, a, b, out0, out1);
-    RSIK_HIP(ctx, hipGetLastError());
-    return RSIK_OK;
+    return launch_end(ctx);
 }
 
 #include "rsik_comm.hpp"
