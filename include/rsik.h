@@ -279,7 +279,8 @@ int rsik_solve(rsik_ctx *ctx, int64_t n, const double *const pose_soa[6], const 
  *   preferred_theta  the preferred_theta argument (r-arm convention; mirrored for l inside, control_ik.py:252)
  *   constrained_mode RSIK_MODE_*
  *   previous_sol_host 14 doubles: ControlIK.previous_sol["r_arm"], ["l_arm"] (control_ik.py:136,140)
- *   current_joints   [n,7] device or NULL (=> previous_sol of the pose's arm, control_ik.py:237-238)
+ *   current_joints   [n,7] device or NULL (=> previous_sol of the pose's arm, control_ik.py:237-238; rows that hold that
+ *                    vector give the NULL form's outputs bit for bit)
  *   orbita3d_max_angle  wrist cone half-angle in radians (control_ik.py:84)
  *   joints [n,7], reachable [n], state [n] as above; emergency [n] uint8 or NULL: non-zero where
  *   multiturn_safety_check tripped (utils.py:535-568), as RSIK_EMERGENCY_* cause bits.

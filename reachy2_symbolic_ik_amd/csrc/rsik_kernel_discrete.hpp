@@ -307,6 +307,17 @@ __global__ __launch_bounds__(kDiscBlock, RSIK_DISC_MIN_WAVES) RSIK_DISC_ATTR voi
         const double w3[3] = {jv[4], jv[5], jv[6]};
         double sn3[3], cs3[3];
         fast_sincos_n<3>(w3, sn3, cs3);
+        if constexpr (!PREV_ROWS) {
+            // rsik.h: current_joints == NULL is previous_sol of the pose's arm, whose wrist sin / cos come with the launch (the host's
+            // libm; fast_sincos differs from it in the last bits).  A wrist angle that IS previous_sol's takes those, so that
+            // the explicit form of that value has the bits of the NULL form.
+#pragma unroll
+            for (int q = 0; q < 3; q++) {
+                const bool own = __builtin_bit_cast(unsigned long long, w3[q]) == __builtin_bit_cast(unsigned long long, prev[4 + q]);
+                cs3[q] = own ? K.prev_cs[slot][q] : cs3[q];
+                sn3[q] = own ? K.prev_sn[slot][q] : sn3[q];
+            }
+        }
         c4 = cs3[0]; s4 = sn3[0]; c5 = cs3[1]; s5 = sn3[1]; c6 = cs3[2]; s6 = sn3[2];
     } else if constexpr (PREV_ROWS) {  // current_joints defaults to previous_sol (C:237-238): the row's own, sin / cos here
 #pragma unroll
