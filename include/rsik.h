@@ -234,7 +234,11 @@ int rsik_set_arm(rsik_ctx *ctx, int arm, const double *consts_host, int count);
  *                              length and stream, issued with value-word edges into the same workspace, on a context no hipGraph
  *                              points into; otherwise the run is issued as with 0 (rsik_control_continuous_last_form tells). */
 #define RSIK_OPT_CONT_GOALS_RESIDENT 7
-#define RSIK_OPT_COUNT 8
+/*   RSIK_OPT_NEAREST_LANES  rsik_solve_nearest, a kernel-variant selector as the ones above (every value gives the same bits in
+ *                           every output): lanes that share a pose's samples, 0 (default) = chosen by the library from n and
+ *                           n_theta, or 1, 8 or 64; any other value is RSIK_E_INVALID */
+#define RSIK_OPT_NEAREST_LANES 8
+#define RSIK_OPT_COUNT 9
 int rsik_set_option(rsik_ctx *ctx, int option, int value);
 int rsik_get_option(const rsik_ctx *ctx, int option, int *value);
 
@@ -344,6 +348,45 @@ int rsik_solve_sweep(rsik_ctx *ctx, int64_t n, const double *const pose_soa[6], 
                      const double *previous_joints,
                      double *joints, double *elbow, uint8_t *projected, double *theta,
                      double *interval, uint8_t *reachable, uint8_t *state);
+
+/*
+ * rsik_solve_nearest — rsik_solve_sweep's samples, and of them the one whose joints are nearest to the joints the caller has: what
+ * a planner, an IK-seeded trajectory optimiser or a data generator asks after a sweep, answered on the device with one row per
+ * pose instead of n_theta.  Added within ABI version 8: a new symbol and a new option (RSIK_OPT_NEAREST_LANES), nothing else changed.
+ *
+ * n ... previous_joints are rsik_solve_sweep's arguments, with its checks and its error codes (n_theta 1 ... 4096, RSIK_THETA_FRACTION or
+ * RSIK_THETA_EXPLICIT, theta_in [n_theta] or [n_theta][n]).  Sample k of pose i is what rsik_solve_sweep computes for it.
+ *
+ *   seed_joints      [n,7] device, row-major: the joints row i wants to stay near (not NULL: RSIK_E_INVALID)
+ *   weights_host     7 doubles (host) or NULL for ones; each finite and >= 0, otherwise RSIK_E_INVALID
+ *   flags            bit mask: RSIK_NEAREST_SKIP_PROJECTED — a sample whose elbow projection fired is not a candidate (its joints
+ *                    reach the MOVED goal, symbolic_ik.py:708-718); any other bit: RSIK_E_INVALID
+ *
+ * The cost of sample k of pose i is  c = sum_q w_q * d_q * d_q,  d_q = angle_diff(joints[k][i][q], seed[i][q])  (utils.py:486-490),
+ * q = 0 ... 6 in that order, unfused.  With unit weights sqrt(c) is the number rsik_theta_from_joints returns as `distance`.
+ * A sample is a candidate iff its pose is reachable, its c is a number (a theta or a seed entry that is NaN gives NaN) and `flags`
+ * does not exclude it.  The winner is the candidate with the smallest c — compared on c, not on its square root —, the lowest k
+ * among equal costs.
+ *
+ * Outputs, one row per pose, any of them NULL (index, theta and joints all NULL: RSIK_E_INVALID):
+ *   index            [n] int32: the winning k, or -1 where the pose has no candidate
+ *   theta [n], joints [n,7], elbow [n,3], projected [n] uint8
+ *                    bit for bit what rsik_solve_sweep writes for sample index[i] of pose i; without a candidate NaN, projected 0
+ *   cost             [n]: sqrt(c) of the winner, NaN without one
+ *   interval [n,2], reachable [n], state [n]   as rsik_solve.  `reachable` stays is_reachable's answer: a pose can be reachable
+ *                    and still have index -1 (every sample projected under RSIK_NEAREST_SKIP_PROJECTED, a NaN in its seed row,
+ *                    no theta that is a number).
+ * "Rows that are not numbers" applies row by row: a pose with a NaN or an infinity reports RSIK_STATE_INVALID_INPUT and index -1;
+ * a seed row with a NaN loses its own row only (index -1, reachable unchanged); a theta that is not a number never wins.
+ * The result does not depend on RSIK_OPT_NEAREST_LANES.  n == 0 launches nothing.  Enqueued on the context's stream; never waits
+ * for the device.
+ */
+#define RSIK_NEAREST_SKIP_PROJECTED 1
+int rsik_solve_nearest(rsik_ctx *ctx, int64_t n, const double *const pose_soa[6], const uint8_t *arm, int arm_uniform,
+                       int n_theta, int theta_policy, const double *theta_in, int theta_per_pose,
+                       const double *previous_joints, const double *seed_joints, const double *weights_host, int flags,
+                       int32_t *index, double *theta, double *joints, double *elbow, double *cost, uint8_t *projected,
+                       double *interval, uint8_t *reachable, uint8_t *state);
 
 /*
  * rsik_control_discrete_rows — rsik_control_discrete with previous_sol [n,7]: row i is ControlIK.previous_sol[name] of the

@@ -291,6 +291,75 @@ class HipSolver:
                  _ptr(res["interval"]), _ptr(res["reachable"]), _ptr(res["state"]))
         return self._finish(res, "rsik_solve_sweep", cargs, plan_only, (pose_soa, arm, thetas, cols, previous_joints))
 
+    # ------------------------------------------------------------------ rsik_solve_nearest
+    def solve_nearest(
+        self,
+        pose_soa: torch.Tensor,
+        thetas: torch.Tensor,
+        seed_joints: torch.Tensor,
+        policy: str = "fraction",
+        weights: Optional[Sequence[float]] = None,
+        skip_projected: bool = False,
+        arm: Optional[torch.Tensor] = None,
+        arm_uniform: int = 0,
+        previous_joints: Optional[torch.Tensor] = None,
+        want_elbow: bool = True,
+        out: Optional[Dict[str, torch.Tensor]] = None,
+        plan_only: bool = False,
+    ) -> Dict[str, torch.Tensor]:
+        """Of K elbow angles per pose, the one whose solution is nearest to the pose's seed joints, from one launch
+        (rsik_solve_nearest): solve_sweep's samples, the weighted squared angle_diff to seed_joints as the cost, the smallest cost
+        wins, the lowest sample among equal costs — one row per pose comes back instead of K.
+        pose_soa, thetas ([K] or [K, n]), policy, previous_joints, arm: as solve_sweep.  seed_joints: [n, 7].  weights: 7 values,
+        finite and >= 0, None for ones.  skip_projected: samples whose elbow projection moved the goal are no candidates.
+        Returns device tensors: index [n] int32 (the winning sample, -1 where the pose has no candidate), theta [n], joints [n,7],
+        elbow [n,3] (want_elbow), projected [n] u8 — the bits of solve_sweep's sample index[i] of pose i, NaN / 0 without a
+        candidate —, cost [n] (sqrt of the winner's weighted sum), and interval [n,2], reachable [n] u8, state [n] u8 as solve():
+        a pose can be reachable and have index -1.
+        plan_only=True launches nothing and adds res["launch"], a zero-overhead re-launch callable (see plan())."""
+        if pose_soa.dim() != 2 or pose_soa.shape[0] != 6:
+            raise ValueError("pose_soa must have shape [6, n]")
+        codes = {"fraction": _abi.THETA_FRACTION, "explicit": _abi.THETA_EXPLICIT}
+        if policy not in codes:
+            raise ValueError("policy must be 'fraction' or 'explicit'")
+        n = int(pose_soa.shape[1])
+        pose_soa = self._dev_cols(pose_soa, 6, n, "pose_soa")
+        if not isinstance(thetas, torch.Tensor):
+            thetas = torch.as_tensor(np.asarray(thetas, dtype=np.float64))
+        if thetas.dim() not in (1, 2):
+            raise ValueError("thetas must have shape [K] or [K, n]")
+        k = int(thetas.shape[0])
+        per_pose = thetas.dim() == 2
+        if not 1 <= k <= 4096:
+            raise ValueError("thetas: between 1 and 4096 samples per pose")
+        thetas = self._dev_f64(thetas, (k, n) if per_pose else (k,), "thetas")
+        seed_joints = self._dev_f64(seed_joints, (n, 7), "seed_joints")
+        if arm is not None:
+            arm = self._dev_u8(arm, n, "arm")
+        if previous_joints is not None:
+            previous_joints = self._dev_f64(previous_joints, (n, 7), "previous_joints")
+        w, wp = None, None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.float64)
+            if w.shape != (7,):
+                raise ValueError("weights must have 7 entries")
+            wp = w.ctypes.data_as(C.POINTER(C.c_double))
+        res = {"index": self._out_buf(out, "index", (n,), torch.int32), "theta": self._out_buf(out, "theta", (n,), _F64),
+               "joints": self._out_buf(out, "joints", (n, 7), _F64)}
+        if want_elbow:
+            res["elbow"] = self._out_buf(out, "elbow", (n, 3), _F64)
+        res["cost"] = self._out_buf(out, "cost", (n,), _F64)
+        res["projected"] = self._out_buf(out, "projected", (n,), _U8)
+        res["interval"] = self._out_buf(out, "interval", (n, 2), _F64)
+        res["reachable"] = self._out_buf(out, "reachable", (n,), _U8)
+        res["state"] = self._out_buf(out, "state", (n,), _U8)
+        cols = self._cols(pose_soa, 6)
+        cargs = (n, cols, _ptr(arm), int(arm_uniform), k, codes[policy], _ptr(thetas), int(per_pose), _ptr(previous_joints),
+                 _ptr(seed_joints), wp, _abi.NEAREST_SKIP_PROJECTED if skip_projected else 0,
+                 _ptr(res["index"]), _ptr(res["theta"]), _ptr(res["joints"]), _ptr(res.get("elbow")), _ptr(res["cost"]),
+                 _ptr(res["projected"]), _ptr(res["interval"]), _ptr(res["reachable"]), _ptr(res["state"]))
+        return self._finish(res, "rsik_solve_nearest", cargs, plan_only, (pose_soa, arm, thetas, cols, previous_joints, seed_joints, w))
+
     def plan(self, fn_name: str, *args):
         """Binds one C-ABI call with all its arguments once; the returned callable re-issues exactly that launch (a few
         microseconds of host time per call — the hot loop of a caller that re-solves resident buffers, e.g. bench.py).

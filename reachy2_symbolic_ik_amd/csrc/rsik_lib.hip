@@ -33,6 +33,7 @@
 #include "rsik_kernel_stages.hpp"
 #include "rsik_kernel_theta_from_joints.hpp"
 #include "rsik_kernel_sweep.hpp"
+#include "rsik_kernel_nearest.hpp"
 
 // =====================================================================================
 // C ABI
@@ -109,6 +110,10 @@ static void with_bool(bool b, F&& f) { if (b) f(std::true_type()); else f(std::f
 template <class F>
 static void with_int3(int i, F&& f) {
     if (i == 0) f(std::integral_constant<int, 0>()); else if (i == 1) f(std::integral_constant<int, 1>()); else f(std::integral_constant<int, 2>());
+}
+template <class F>
+static void with_lanes(int lanes, F&& f) {  // solve_nearest_kernel's lanes per pose
+    if (lanes == 1) f(std::integral_constant<int, 1>()); else if (lanes == 8) f(std::integral_constant<int, 8>()); else f(std::integral_constant<int, 64>());
 }
 
 // A column table of the ABI (`count` device pointers): refuses a NULL table ("<table> is NULL") or a NULL column ("<a_column> is
@@ -244,8 +249,11 @@ int rsik_set_option(rsik_ctx* ctx, int option, int value) {
         case RSIK_OPT_CONT_BLOCK_STEPS: max_value = 65535; break;
         case RSIK_OPT_CONT_PHASED_VARIANT: max_value = 127; break;
         case RSIK_OPT_CONT_GOALS_RESIDENT: max_value = 1; break;
+        case RSIK_OPT_NEAREST_LANES: max_value = 64; break;  // (a set, not a range: below)
     }
     if (value < 0 || value > max_value) return fail(ctx, RSIK_E_INVALID, "rsik_set_option: value out of range");
+    if (option == RSIK_OPT_NEAREST_LANES && value != 0 && value != 1 && value != 8 && value != 64)
+        return fail(ctx, RSIK_E_INVALID, "rsik_set_option: RSIK_OPT_NEAREST_LANES takes 0, 1, 8 or 64");
     ctx->options[option] = value;
     return RSIK_OK;
 }
@@ -400,6 +408,64 @@ int rsik_solve_sweep(rsik_ctx* ctx, int64_t n, const double* const pose_soa[6], 
     if ((rc = launch_begin(ctx, n, &grid, who)) != RSIK_OK) return rc;
     with_int3(launch_form(ctx, K.arms, arm), [&](auto FORM) { with_bool(tip_on_z(ctx, K.arms), [&](auto TIPZ) { with_bool(previous_joints != nullptr, [&](auto PREV_ROWS) {
         hipLaunchKernelGGL((rsik::solve_sweep_kernel<FORM(), TIPZ(), PREV_ROWS()>), grid, block, 0, ctx->stream, K); }); }); });
+    return launch_end(ctx);
+}
+
+// Lanes per pose of solve_nearest_kernel where RSIK_OPT_NEAREST_LANES leaves the choice to the library: a function of n and n_theta
+// alone, the form scripts/nearest_cost.py measured fastest at each of its shapes (DESIGN section 3 "Nearest": with 64 samples 1 lane
+// at 262 144 poses, 8 from 65 536 down to 4096, where 64 lanes draw level; 64 at 64 x 1024 and 2 x 1024).  The step from 8 lanes to 1
+// sits halfway (in the logarithm) between the two shapes that bracket it, and a pose never gets more lanes than it has samples for
+// more than one round of.
+static int nearest_lanes(int64_t n, int n_theta) {
+    if (n >= 131072 || n_theta == 1) return 1;
+    if (n >= 4096 || n_theta <= 8) return 8;
+    return 64;
+}
+
+// rsik_solve_nearest: rsik_solve_sweep's samples, and of them the one nearest to the pose's seed joints (rsik_kernel_nearest.hpp)
+int rsik_solve_nearest(rsik_ctx* ctx, int64_t n, const double* const pose_soa[6], const uint8_t* arm, int arm_uniform,
+                       int n_theta, int theta_policy, const double* theta_in, int theta_per_pose,
+                       const double* previous_joints, const double* seed_joints, const double* weights_host, int flags,
+                       int32_t* index, double* theta, double* joints, double* elbow, double* cost, uint8_t* projected,
+                       double* interval, uint8_t* reachable, uint8_t* state) {
+    if (!ctx) return RSIK_E_INVALID;
+    const char* who = "rsik_solve_nearest";
+    const std::string w(who);
+    if (n < 0) return fail(ctx, RSIK_E_INVALID, w + ": n < 0");
+    if (n_theta < 1 || n_theta > 4096) return fail(ctx, RSIK_E_INVALID, w + ": n_theta must be in [1, 4096]");
+    if (theta_policy != RSIK_THETA_EXPLICIT && theta_policy != RSIK_THETA_FRACTION)
+        return fail(ctx, RSIK_E_INVALID, w + ": theta_policy must be RSIK_THETA_EXPLICIT or RSIK_THETA_FRACTION");
+    if (flags & ~RSIK_NEAREST_SKIP_PROJECTED) return fail(ctx, RSIK_E_INVALID, w + ": unknown bits in flags");
+    for (int q = 0; weights_host && q < 7; q++)
+        if (!(weights_host[q] >= 0.0 && std::isfinite(weights_host[q]))) return fail(ctx, RSIK_E_INVALID, w + ": every weight must be finite and >= 0");
+    int rc = check_arms(ctx, arm, arm_uniform, who);
+    if (rc != RSIK_OK) return rc;
+    if (n == 0) return RSIK_OK;
+    if (!pose_soa) return fail(ctx, RSIK_E_INVALID, w + ": pose_soa is NULL");
+    if (!theta_in) return fail(ctx, RSIK_E_INVALID, w + ": theta_in is NULL");
+    if (!seed_joints) return fail(ctx, RSIK_E_INVALID, w + ": seed_joints is NULL");
+    if (!index && !theta && !joints) return fail(ctx, RSIK_E_INVALID, w + ": index, theta and joints are all NULL");
+    rsik::NearestArgs K;
+    K.n = n;
+    if ((rc = copy_cols(ctx, who, "pose_soa", "a pose_soa column", pose_soa, K.in, 6)) != RSIK_OK) return rc;
+    K.arm = arm;
+    K.theta_policy = theta_policy;
+    K.n_theta = n_theta;
+    K.theta_per_pose = theta_per_pose != 0;
+    K.skip_projected = (flags & RSIK_NEAREST_SKIP_PROJECTED) != 0;
+    K.theta_in = theta_in;
+    if (previous_joints) K.prev_rows = previous_joints;  // (shares its kernarg bytes with K.prev)
+    else for (int k = 0; k < 7; k++) K.prev[k] = 0.0;
+    K.seed = seed_joints;
+    for (int q = 0; q < 7; q++) K.weights[q] = weights_host ? weights_host[q] : 1.0;
+    K.index = index; K.theta = theta; K.joints = joints; K.elbow = elbow; K.cost = cost; K.projected = projected;
+    K.interval = interval; K.reachable = reachable; K.state = state;
+    bind_arms(ctx, arm, arm_uniform, K.arms);
+    const int lanes = ctx->options[RSIK_OPT_NEAREST_LANES] ? ctx->options[RSIK_OPT_NEAREST_LANES] : nearest_lanes(n, n_theta);
+    dim3 grid, block(rsik::kBlock);
+    if ((rc = launch_begin(ctx, n, &grid, who, rsik::kBlock / lanes)) != RSIK_OK) return rc;
+    with_int3(launch_form(ctx, K.arms, arm), [&](auto FORM) { with_bool(tip_on_z(ctx, K.arms), [&](auto TIPZ) { with_bool(previous_joints != nullptr, [&](auto PREV_ROWS) { with_lanes(lanes, [&](auto LANES) {
+        hipLaunchKernelGGL((rsik::solve_nearest_kernel<FORM(), TIPZ(), PREV_ROWS(), LANES()>), grid, block, 0, ctx->stream, K); }); }); }); });
     return launch_end(ctx);
 }
 

@@ -326,6 +326,27 @@ class SymbolicIK:
         return self._solver.solve_sweep(soa, thetas, policy=policy, arm_uniform=self.arm_id, previous_joints=previous_joints,
                                         want_elbow=want_elbow, out=out)
 
+    def nearest_batch(self, poses: Any, seed_joints: Any, n_theta: int = 64, thetas: Any = None, policy: str = "fraction",
+                      weights: Optional[Sequence[float]] = None, skip_projected: bool = False, previous_joints: Any = None,
+                      want_elbow: bool = True, out: Optional[Dict[str, torch.Tensor]] = None,
+                      plan_only: bool = False) -> Dict[str, torch.Tensor]:
+        """For every pose of this arm, the elbow angle — of K sampled ones — whose solution is nearest to that row's seed joints,
+        in one launch: sweep_batch's samples, judged on the device, one row per pose back (HipSolver.solve_nearest,
+        rsik_solve_nearest).  What a planner or a trajectory optimiser asks with the joints it has.
+
+        poses: [n,2,3] or SoA [6,n].  seed_joints: [n,7].  thetas: [K] shared by every pose, or [K, n]; None: `n_theta` evenly
+        spaced fractions from 0 to 1 inclusive, as sweep_batch.  policy: "fraction" or "explicit".  weights: 7 values >= 0 for the
+        squared joint differences (None: ones).  skip_projected: samples whose elbow projection moved the goal cannot win.
+        Returns device tensors: index [n] int32 (-1: no candidate), theta [n], joints [n,7], elbow [n,3], projected [n] u8,
+        cost [n], interval [n,2], reachable [n] u8, state [n] u8."""
+        soa = poses_to_soa(poses, self._solver.device)
+        if thetas is None:
+            thetas = torch.linspace(0.0, 1.0, int(n_theta), dtype=torch.float64)
+        self._upload()
+        return self._solver.solve_nearest(soa, thetas, seed_joints, policy=policy, weights=weights, skip_projected=skip_projected,
+                                          arm_uniform=self.arm_id, previous_joints=previous_joints, want_elbow=want_elbow,
+                                          out=out, plan_only=plan_only)
+
     def theta_from_joints_batch(self, poses: Any, current_joints: Any, preferred_theta: Optional[float] = None,
                                 out: Optional[Dict[str, torch.Tensor]] = None, plan_only: bool = False) -> Dict[str, torch.Tensor]:
         """For every row, the theta whose solution is closest to that row's measured joints: is_reachable_no_limits(pose),
@@ -478,6 +499,21 @@ class DualArmIK:
         self.l_arm._upload()
         return self._solver.solve_sweep(soa, thetas, policy=policy, arm=arm_ids, previous_joints=previous_joints,
                                         want_elbow=want_elbow, out=out)
+
+    def nearest_batch(self, arm_ids: Any, poses: Any, seed_joints: Any, n_theta: int = 64, thetas: Any = None, policy: str = "fraction",
+                      weights: Optional[Sequence[float]] = None, skip_projected: bool = False, previous_joints: Any = None,
+                      want_elbow: bool = True, out: Optional[Dict[str, torch.Tensor]] = None,
+                      plan_only: bool = False) -> Dict[str, torch.Tensor]:
+        """SymbolicIK.nearest_batch for rows of both arms (arm_ids [n] uint8): of K elbow angles per pose, the one whose solution
+        is nearest to the row's seed joints, one row per pose (index [n] int32, theta, joints [n,7] ...)."""
+        soa = poses_to_soa(poses, self._solver.device)
+        if thetas is None:
+            thetas = torch.linspace(0.0, 1.0, int(n_theta), dtype=torch.float64)
+        self.r_arm._upload()
+        self.l_arm._upload()
+        return self._solver.solve_nearest(soa, thetas, seed_joints, policy=policy, weights=weights, skip_projected=skip_projected,
+                                          arm=arm_ids, previous_joints=previous_joints, want_elbow=want_elbow, out=out,
+                                          plan_only=plan_only)
 
     def theta_from_joints_batch(self, arm_ids: Any, poses: Any, current_joints: Any, preferred_theta: Optional[Sequence[float]] = None,
                                 out: Optional[Dict[str, torch.Tensor]] = None, plan_only: bool = False) -> Dict[str, torch.Tensor]:
