@@ -389,6 +389,79 @@ int rsik_solve_nearest(rsik_ctx *ctx, int64_t n, const double *const pose_soa[6]
                        double *interval, uint8_t *reachable, uint8_t *state);
 
 /*
+ * rsik_solve_path — n paths of n_steps waypoints for one arm each: rsik_solve_sweep's n_theta samples at every waypoint, and of the
+ * n_theta ^ n_steps ways through them the one along which the joints move least, found on the device by dynamic programming, from one
+ * launch.  The offline, globally optimal counterpart of the continuous mode's greedy theta tracking (control_ik.py:276-407), and of a
+ * chain of rsik_solve_nearest launches each seeded with the winner before it.  Added within ABI version 8: two new symbols and two
+ * flags, nothing else changed.
+ *
+ * Every per-waypoint array is waypoint-major, [n_steps][n]: entry [t][i] is waypoint t of path i (the order of m12_steps and
+ * joints_steps of rsik_control_continuous_run).
+ *   n, n_steps       n >= 0 paths of 1 ... 65536 waypoints
+ *   pose_soa         six device arrays of n_steps * n doubles
+ *   arm              [n], one byte per path, or NULL with arm_uniform
+ *   n_theta          samples per waypoint, 1 ... 64 (anything else: RSIK_E_INVALID)
+ *   theta_policy     RSIK_THETA_FRACTION or RSIK_THETA_EXPLICIT
+ *   theta_in         device; theta_per_pose == 0: [n_theta] values shared by every waypoint; otherwise [n_theta][n_steps * n]
+ *   start_joints     [n,7] device or NULL: the joints each path starts from
+ *   weights_host     7 doubles (host) or NULL for ones; each finite and >= 0, otherwise RSIK_E_INVALID
+ *   flags            RSIK_PATH_SKIP_PROJECTED (as RSIK_NEAREST_SKIP_PROJECTED), RSIK_PATH_UNWIND (below); any other bit: RSIK_E_INVALID
+ *   workspace        device memory of the caller's, at least rsik_solve_path_workspace_bytes(n, n_steps, n_theta) bytes (the
+ *                    backpointer table, n * n_steps * n_theta bytes, and one byte per waypoint); NULL or too small: RSIK_E_INVALID.
+ *                    Only read and written by the launch; free to reuse once the launch has finished.
+ * There is no previous_joints: every sample is what rsik_solve_sweep computes with previous_joints == NULL.
+ *
+ * Definition (the result does not depend on how the kernel is laid out):
+ *   Sample k of waypoint (t, i) is rsik_solve_sweep's sample k over the same n_steps * n poses; J[k] are its joints.
+ *   A sample is a CANDIDATE iff its pose is reachable, none of its joints is a NaN, and `flags` does not exclude it.
+ *   A waypoint with at least one candidate is SOLVED; one without is SKIPPED (index -1, NaN rows, projected 0) and the path goes on
+ *   as if it were not there: the next solved waypoint is measured against the last solved one.
+ *   The transition cost is  c(a, b) = sum_q w_q * d_q * d_q,  d_q = angle_diff(b_q, a_q)  (utils.py:486-490), q = 0 ... 6 in that
+ *   order, unfused: rsik_solve_nearest's cost of joints b against seed a.
+ *   At a path's first solved waypoint A(k) = c(start_joints[i], J[k]), or 0 when start_joints is NULL, for every candidate k.
+ *   At every later solved waypoint A(j) = min over the candidates i of the previous solved waypoint of (A(i) + c(J_prev[i], J[j])) —
+ *   one rounding for the sum —, the lowest i among equal values.
+ *   The path ends in the candidate j with the smallest A at the last solved waypoint, the lowest j among equal values; the other
+ *   winners follow by going back along the i that gave each A.
+ *
+ * Outputs, any of them NULL (index, theta and joints all NULL: RSIK_E_INVALID):
+ *   index            [n_steps][n] int32: the winning k, -1 at a skipped waypoint
+ *   theta [n_steps][n], joints [n_steps][n][7], elbow [n_steps][n][3], projected [n_steps][n] uint8
+ *                    bit for bit what rsik_solve_sweep writes for sample index[t][i] of that waypoint; NaN / 0 at a skipped one
+ *   step_cost        [n_steps][n]: sqrt of the transition cost into waypoint t (rsik_solve_nearest's `cost` unit): from the last
+ *                    solved waypoint before it; at the first solved waypoint from start_joints, 0 without them; NaN at a skipped one
+ *   cost             [n]: the minimal sum itself (the smallest A of the last solved waypoint), not its root; NaN when no waypoint is solved
+ *   n_solved         [n] int32: the number of solved waypoints
+ *   interval [n_steps][n][2], reachable [n_steps][n], state [n_steps][n]   as rsik_solve for the n_steps * n poses.  `reachable`
+ *                    stays is_reachable's answer: a waypoint can be reachable and skipped.
+ *
+ * RSIK_PATH_UNWIND: row t of `joints` becomes allow_multiturn(row t as above, the previous solved waypoint's row AS WRITTEN)
+ * (utils.py:493-505: prev + angle_diff(new, prev) per joint, what RSIK_STAGE_ALLOW_MULTITURN computes), in order along the path; the
+ * first solved row is unwound against start_joints, or left as it is without them.  The rows are then continuous along the path and
+ * may leave [-pi, pi].  index, the costs and every other output do not change: angle_diff does not see whole turns.
+ *
+ * "Rows that are not numbers": a waypoint whose pose holds a NaN or an infinity reports RSIK_STATE_INVALID_INPUT and is skipped; a
+ * theta that is not a number never wins; a start_joints row that holds a NaN or an infinity loses its own path only — no sample of
+ * that path is a candidate: n_solved 0, every index -1, cost NaN, reachable and state unchanged.  Every other path's outputs are the
+ * bits of a run in which the bad value was an ordinary one.
+ * n == 0 launches nothing.  Enqueued on the context's stream; allocates nothing and never waits for the device.
+ *
+ * rsik_solve_path_workspace_bytes — the workspace rsik_solve_path needs for (n, n_steps, n_theta), monotone in each of them;
+ *   RSIK_E_INVALID for a NULL `bytes` or arguments rsik_solve_path refuses.
+ */
+#define RSIK_PATH_SKIP_PROJECTED 1
+#define RSIK_PATH_UNWIND 2
+int rsik_solve_path_workspace_bytes(int64_t n, int64_t n_steps, int n_theta, size_t *bytes);
+int rsik_solve_path(rsik_ctx *ctx, int64_t n, int64_t n_steps, const double *const pose_soa[6],
+                    const uint8_t *arm, int arm_uniform,
+                    int n_theta, int theta_policy, const double *theta_in, int theta_per_pose,
+                    const double *start_joints, const double *weights_host, int flags,
+                    void *workspace, size_t workspace_bytes,
+                    int32_t *index, double *theta, double *joints, double *elbow, uint8_t *projected,
+                    double *step_cost, double *cost, int32_t *n_solved,
+                    double *interval, uint8_t *reachable, uint8_t *state);
+
+/*
  * rsik_control_discrete_rows — rsik_control_discrete with previous_sol [n,7]: row i is ControlIK.previous_sol[name] of the
  *   caller that owns goal i, for that row's own arm (no 2x7 split).  It is get_joints' previous_joints (control_ik.py:454-456),
  *   the fallback joints when no theta is found and current_joints is NULL (:237-238, :457-458), and safety_checks'

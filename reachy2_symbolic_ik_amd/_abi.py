@@ -62,6 +62,9 @@ PROTOTYPES = {
                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rsik_solve_nearest": (C.c_int, [_vp, C.c_int64, C.POINTER(_vp), _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _dp, C.c_int,
                                      _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rsik_solve_path_workspace_bytes": (C.c_int, [C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_size_t)]),
+    "rsik_solve_path": (C.c_int, [_vp, C.c_int64, C.c_int64, C.POINTER(_vp), _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _dp, C.c_int,
+                                  _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rsik_control_discrete_rows": (C.c_int, [_vp, C.c_int64, C.POINTER(_vp), _vp, C.c_int, C.c_int, C.c_double, C.c_int, _vp,
                                              _vp, C.c_double, _vp, _vp, _vp, _vp]),
     "rsik_control_continuous_step": (C.c_int, [_vp, C.c_int64, C.POINTER(_vp), C.POINTER(_vp), _vp, C.c_int, _vp, C.c_double, _dp,
@@ -97,6 +100,7 @@ STAGE_IN_MAX, STAGE_OUT_MAX = 21, 9
 OPT_EULER_ROUNDTRIP, OPT_SWEEP_MODE, OPT_NO_TIPZ, OPT_NO_MIRROR, OPT_CONT_RUN_MODE = 0, 1, 2, 3, 4
 OPT_CONT_BLOCK_STEPS, OPT_CONT_PHASED_VARIANT, OPT_CONT_GOALS_RESIDENT, OPT_NEAREST_LANES = 5, 6, 7, 8
 NEAREST_SKIP_PROJECTED = 1  # rsik_solve_nearest flags
+PATH_SKIP_PROJECTED, PATH_UNWIND = 1, 2  # rsik_solve_path flags
 (CONT_FORM_NONE, CONT_FORM_PHASED, CONT_FORM_PHASED_OVERLAPPED, CONT_FORM_PHASED_CAPTURED, CONT_FORM_STEPS,
  CONT_FORM_STEPS_NO_LIMITS_CAN_FAIL) = range(6)
 CONT_FORM_NAMES = {0: "none", 1: "phased", 2: "phased, overlapping the run before", 3: "phased, captured", 4: "steps",

@@ -360,6 +360,95 @@ class HipSolver:
                  _ptr(res["projected"]), _ptr(res["interval"]), _ptr(res["reachable"]), _ptr(res["state"]))
         return self._finish(res, "rsik_solve_nearest", cargs, plan_only, (pose_soa, arm, thetas, cols, previous_joints, seed_joints, w))
 
+    # ------------------------------------------------------------------ rsik_solve_path
+    def solve_path_workspace_bytes(self, n: int, n_steps: int, n_theta: int) -> int:
+        """rsik_solve_path_workspace_bytes: the device workspace a solve_path of this shape needs."""
+        b = C.c_size_t(0)
+        rc = self.lib.rsik_solve_path_workspace_bytes(int(n), int(n_steps), int(n_theta), C.byref(b))
+        if rc != _abi.RSIK_OK:
+            raise _abi.RsikError(rc, "rsik_solve_path_workspace_bytes: n >= 0, n_steps 1 ... 65536, n_theta 1 ... 64")
+        return int(b.value)
+
+    def solve_path(
+        self,
+        pose_soa: torch.Tensor,
+        thetas: torch.Tensor,
+        start_joints: Optional[torch.Tensor] = None,
+        policy: str = "fraction",
+        weights: Optional[Sequence[float]] = None,
+        skip_projected: bool = False,
+        unwind: bool = False,
+        arm: Optional[torch.Tensor] = None,
+        arm_uniform: int = 0,
+        want_elbow: bool = True,
+        out: Optional[Dict[str, torch.Tensor]] = None,
+        plan_only: bool = False,
+    ) -> Dict[str, torch.Tensor]:
+        """The least-motion way through K elbow angles per waypoint, for n paths of T waypoints, from one launch (rsik_solve_path):
+        solve_sweep's samples at every waypoint, the weighted squared angle_diff between consecutive waypoints' joints as the
+        transition cost, and the sequence of samples with the smallest sum, found by dynamic programming on the device.
+        pose_soa: [6, T, n] float64, waypoint-major.  thetas: [K], shared by every waypoint, or [K, T, n]; K <= 64; policy
+        "fraction" or "explicit".  start_joints: [n, 7] or None, the joints each path starts from.  weights: 7 values, finite and
+        >= 0, None for ones.  skip_projected: samples whose elbow projection moved the goal are no candidates.  unwind: joints are
+        made continuous along the path (allow_multiturn against the row before), index and the costs do not change.  arm: [n], one
+        byte per path.
+        Returns device tensors: index [T, n] int32 (the winning sample, -1 at a waypoint without a candidate: the path skips it),
+        theta [T, n], joints [T, n, 7], elbow [T, n, 3] (want_elbow), projected [T, n] u8 — the bits of solve_sweep's sample
+        index[t, i] —, step_cost [T, n] (sqrt of the transition cost into the waypoint), cost [n] (the minimal sum, not its root),
+        n_solved [n] int32, and interval [T, n, 2], reachable [T, n] u8, state [T, n] u8 as solve().
+        The workspace is allocated here, with torch, from rsik_solve_path_workspace_bytes; a plan keeps it alive.
+        plan_only=True launches nothing and adds res["launch"], a zero-overhead re-launch callable (see plan())."""
+        if pose_soa.dim() != 3 or pose_soa.shape[0] != 6:
+            raise ValueError("pose_soa must have shape [6, T, n]")
+        codes = {"fraction": _abi.THETA_FRACTION, "explicit": _abi.THETA_EXPLICIT}
+        if policy not in codes:
+            raise ValueError("policy must be 'fraction' or 'explicit'")
+        t, n = int(pose_soa.shape[1]), int(pose_soa.shape[2])
+        if not 1 <= t <= 65536:
+            raise ValueError("pose_soa: between 1 and 65536 waypoints per path")
+        pose_soa = self._dev_cols(pose_soa.reshape(6, t * n), 6, t * n, "pose_soa")
+        if not isinstance(thetas, torch.Tensor):
+            thetas = torch.as_tensor(np.asarray(thetas, dtype=np.float64))
+        if thetas.dim() not in (1, 3):
+            raise ValueError("thetas must have shape [K] or [K, T, n]")
+        k = int(thetas.shape[0])
+        per_pose = thetas.dim() == 3
+        if not 1 <= k <= 64:
+            raise ValueError("thetas: between 1 and 64 samples per waypoint")
+        thetas = self._dev_f64(thetas, (k, t, n) if per_pose else (k,), "thetas")
+        if start_joints is not None:
+            start_joints = self._dev_f64(start_joints, (n, 7), "start_joints")
+        if arm is not None:
+            arm = self._dev_u8(arm, n, "arm")
+        w, wp = None, None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.float64)
+            if w.shape != (7,):
+                raise ValueError("weights must have 7 entries")
+            wp = w.ctypes.data_as(C.POINTER(C.c_double))
+        ws_bytes = self.solve_path_workspace_bytes(n, t, k)
+        workspace = torch.empty((max(ws_bytes, 1),), dtype=_U8, device=self.device)
+        res = {"index": self._out_buf(out, "index", (t, n), torch.int32), "theta": self._out_buf(out, "theta", (t, n), _F64),
+               "joints": self._out_buf(out, "joints", (t, n, 7), _F64)}
+        if want_elbow:
+            res["elbow"] = self._out_buf(out, "elbow", (t, n, 3), _F64)
+        res["projected"] = self._out_buf(out, "projected", (t, n), _U8)
+        res["step_cost"] = self._out_buf(out, "step_cost", (t, n), _F64)
+        res["cost"] = self._out_buf(out, "cost", (n,), _F64)
+        res["n_solved"] = self._out_buf(out, "n_solved", (n,), torch.int32)
+        res["interval"] = self._out_buf(out, "interval", (t, n, 2), _F64)
+        res["reachable"] = self._out_buf(out, "reachable", (t, n), _U8)
+        res["state"] = self._out_buf(out, "state", (t, n), _U8)
+        cols = self._cols(pose_soa, 6)
+        flags = (_abi.PATH_SKIP_PROJECTED if skip_projected else 0) | (_abi.PATH_UNWIND if unwind else 0)
+        cargs = (n, t, cols, _ptr(arm), int(arm_uniform), k, codes[policy], _ptr(thetas), int(per_pose), _ptr(start_joints), wp, flags,
+                 _ptr(workspace), ws_bytes,
+                 _ptr(res["index"]), _ptr(res["theta"]), _ptr(res["joints"]), _ptr(res.get("elbow")), _ptr(res["projected"]),
+                 _ptr(res["step_cost"]), _ptr(res["cost"]), _ptr(res["n_solved"]),
+                 _ptr(res["interval"]), _ptr(res["reachable"]), _ptr(res["state"]))
+        # (the workspace: torch allocated it on the launch's stream and hands it out again in stream order; a plan keeps it)
+        return self._finish(res, "rsik_solve_path", cargs, plan_only, (pose_soa, arm, thetas, cols, start_joints, w, workspace))
+
     def plan(self, fn_name: str, *args):
         """Binds one C-ABI call with all its arguments once; the returned callable re-issues exactly that launch (a few
         microseconds of host time per call — the hot loop of a caller that re-solves resident buffers, e.g. bench.py).

@@ -34,6 +34,7 @@
 #include "rsik_kernel_theta_from_joints.hpp"
 #include "rsik_kernel_sweep.hpp"
 #include "rsik_kernel_nearest.hpp"
+#include "rsik_kernel_path.hpp"
 
 // =====================================================================================
 // C ABI
@@ -466,6 +467,73 @@ int rsik_solve_nearest(rsik_ctx* ctx, int64_t n, const double* const pose_soa[6]
     if ((rc = launch_begin(ctx, n, &grid, who, rsik::kBlock / lanes)) != RSIK_OK) return rc;
     with_int3(launch_form(ctx, K.arms, arm), [&](auto FORM) { with_bool(tip_on_z(ctx, K.arms), [&](auto TIPZ) { with_bool(previous_joints != nullptr, [&](auto PREV_ROWS) { with_lanes(lanes, [&](auto LANES) {
         hipLaunchKernelGGL((rsik::solve_nearest_kernel<FORM(), TIPZ(), PREV_ROWS(), LANES()>), grid, block, 0, ctx->stream, K); }); }); }); });
+    return launch_end(ctx);
+}
+
+// rsik_solve_path's workspace: the backpointer table, one byte per (path, waypoint, sample), and one winner byte per (path, waypoint)
+static bool path_workspace_bytes(int64_t n, int64_t n_steps, int n_theta, size_t* bytes) {
+    if (n < 0 || n_steps < 1 || n_steps > 65536 || n_theta < 1 || n_theta > 64) return false;
+    const unsigned __int128 b = (unsigned __int128)n * (unsigned __int128)n_steps * (unsigned)(n_theta + 1);
+    if (b > (unsigned __int128)SIZE_MAX) return false;
+    *bytes = (size_t)b;
+    return true;
+}
+int rsik_solve_path_workspace_bytes(int64_t n, int64_t n_steps, int n_theta, size_t* bytes) {
+    if (!bytes || !path_workspace_bytes(n, n_steps, n_theta, bytes)) return RSIK_E_INVALID;
+    return RSIK_OK;
+}
+
+// rsik_solve_path: rsik_solve_sweep's samples at every waypoint of n paths, and the way through them that moves the joints least (rsik_kernel_path.hpp)
+int rsik_solve_path(rsik_ctx* ctx, int64_t n, int64_t n_steps, const double* const pose_soa[6], const uint8_t* arm, int arm_uniform,
+                    int n_theta, int theta_policy, const double* theta_in, int theta_per_pose,
+                    const double* start_joints, const double* weights_host, int flags,
+                    void* workspace, size_t workspace_bytes,
+                    int32_t* index, double* theta, double* joints, double* elbow, uint8_t* projected,
+                    double* step_cost, double* cost, int32_t* n_solved,
+                    double* interval, uint8_t* reachable, uint8_t* state) {
+    if (!ctx) return RSIK_E_INVALID;
+    const char* who = "rsik_solve_path";
+    const std::string w(who);
+    if (n < 0) return fail(ctx, RSIK_E_INVALID, w + ": n < 0");
+    if (n_steps < 1 || n_steps > 65536) return fail(ctx, RSIK_E_INVALID, w + ": n_steps must be in [1, 65536]");
+    if (n_theta < 1 || n_theta > 64) return fail(ctx, RSIK_E_INVALID, w + ": n_theta must be in [1, 64]");
+    if (theta_policy != RSIK_THETA_EXPLICIT && theta_policy != RSIK_THETA_FRACTION)
+        return fail(ctx, RSIK_E_INVALID, w + ": theta_policy must be RSIK_THETA_EXPLICIT or RSIK_THETA_FRACTION");
+    if (flags & ~(RSIK_PATH_SKIP_PROJECTED | RSIK_PATH_UNWIND)) return fail(ctx, RSIK_E_INVALID, w + ": unknown bits in flags");
+    for (int q = 0; weights_host && q < 7; q++)
+        if (!(weights_host[q] >= 0.0 && std::isfinite(weights_host[q]))) return fail(ctx, RSIK_E_INVALID, w + ": every weight must be finite and >= 0");
+    int rc = check_arms(ctx, arm, arm_uniform, who);
+    if (rc != RSIK_OK) return rc;
+    if (n == 0) return RSIK_OK;
+    if (!pose_soa) return fail(ctx, RSIK_E_INVALID, w + ": pose_soa is NULL");
+    if (!theta_in) return fail(ctx, RSIK_E_INVALID, w + ": theta_in is NULL");
+    if (!index && !theta && !joints) return fail(ctx, RSIK_E_INVALID, w + ": index, theta and joints are all NULL");
+    size_t need = 0;
+    if (!path_workspace_bytes(n, n_steps, n_theta, &need)) return fail(ctx, RSIK_E_INVALID, w + ": n * n_steps too large");
+    if (!workspace || workspace_bytes < need) return fail(ctx, RSIK_E_INVALID, w + ": workspace is NULL or smaller than rsik_solve_path_workspace_bytes");
+    rsik::PathArgs K;
+    K.n = n;
+    K.n_steps = n_steps;
+    if ((rc = copy_cols(ctx, who, "pose_soa", "a pose_soa column", pose_soa, K.in, 6)) != RSIK_OK) return rc;
+    K.arm = arm;
+    K.theta_policy = theta_policy;
+    K.n_theta = n_theta;
+    K.theta_per_pose = theta_per_pose != 0;
+    K.skip_projected = (flags & RSIK_PATH_SKIP_PROJECTED) != 0;
+    K.unwind = (flags & RSIK_PATH_UNWIND) != 0;
+    K.theta_in = theta_in;
+    for (int k = 0; k < 7; k++) K.prev[k] = 0.0;
+    K.start = start_joints;
+    for (int q = 0; q < 7; q++) K.weights[q] = weights_host ? weights_host[q] : 1.0;
+    K.back = static_cast<uint8_t*>(workspace);
+    K.index = index; K.theta = theta; K.joints = joints; K.elbow = elbow; K.projected = projected;
+    K.step_cost = step_cost; K.cost = cost; K.n_solved = n_solved;
+    K.interval = interval; K.reachable = reachable; K.state = state;
+    bind_arms(ctx, arm, arm_uniform, K.arms);
+    dim3 grid, block(rsik::kBlock);
+    if ((rc = launch_begin(ctx, n, &grid, who, rsik::kBlock / 64)) != RSIK_OK) return rc;
+    with_int3(launch_form(ctx, K.arms, arm), [&](auto FORM) { with_bool(tip_on_z(ctx, K.arms), [&](auto TIPZ) {
+        hipLaunchKernelGGL((rsik::solve_path_kernel<FORM(), TIPZ()>), grid, block, 0, ctx->stream, K); }); });
     return launch_end(ctx);
 }
 

@@ -34,6 +34,19 @@ def poses_to_soa(poses: Any, device: torch.device) -> torch.Tensor:
     return t if (t.shape[1] <= 1 or t.stride(1) == 1) else t.contiguous()
 
 
+def _path_soa(poses: Any, device: Any) -> torch.Tensor:
+    """Waypoint-major path poses as SoA [6, T, n]: [T,n,2,3] (position, Euler angles per waypoint), or SoA [6,T,n] as it is."""
+    if isinstance(poses, torch.Tensor):
+        t = poses.to(device=device, dtype=torch.float64)
+    else:
+        t = torch.as_tensor(np.asarray(poses, dtype=np.float64)).to(device)
+    if t.dim() == 3 and t.shape[0] == 6:
+        return t
+    if t.dim() == 4 and tuple(t.shape[2:]) == (2, 3):
+        return t.reshape(t.shape[0], t.shape[1], 6).permute(2, 0, 1).contiguous()
+    raise ValueError("poses must have shape [T,n,2,3] or SoA [6,T,n]")
+
+
 class SymbolicIK:
     def __init__(
         self,
@@ -347,6 +360,28 @@ class SymbolicIK:
                                           arm_uniform=self.arm_id, previous_joints=previous_joints, want_elbow=want_elbow,
                                           out=out, plan_only=plan_only)
 
+    def path_batch(self, poses: Any, start_joints: Any = None, n_theta: int = 16, thetas: Any = None, policy: str = "fraction",
+                   weights: Optional[Sequence[float]] = None, skip_projected: bool = False, unwind: bool = False,
+                   want_elbow: bool = True, out: Optional[Dict[str, torch.Tensor]] = None,
+                   plan_only: bool = False) -> Dict[str, torch.Tensor]:
+        """For n paths of T waypoints of this arm, the sequence of elbow angles — one of K sampled ones per waypoint — along which
+        the joints move least, in one launch: sweep_batch's samples at every waypoint, the best way through them found on the
+        device (HipSolver.solve_path, rsik_solve_path).  Not the greedy chain of nearest_batch calls: the optimum over all K ^ T.
+
+        poses: [T,n,2,3] or SoA [6,T,n], waypoint-major.  start_joints: [n,7] or None.  thetas: [K] shared by every waypoint, or
+        [K,T,n]; None: `n_theta` evenly spaced fractions from 0 to 1 inclusive; K <= 64.  policy: "fraction" or "explicit".
+        weights: 7 values >= 0 (None: ones).  skip_projected: samples whose elbow projection moved the goal cannot win.  unwind:
+        joints continuous along the path (allow_multiturn against the row before).
+        Returns device tensors: index [T, n] int32 (-1: a waypoint without a candidate, skipped), theta [T,n], joints [T,n,7],
+        elbow [T,n,3], projected [T,n] u8, step_cost [T,n], cost [n], n_solved [n] int32, interval [T,n,2], reachable [T,n] u8,
+        state [T,n] u8."""
+        soa = _path_soa(poses, self._solver.device)
+        if thetas is None:
+            thetas = torch.linspace(0.0, 1.0, int(n_theta), dtype=torch.float64) if int(n_theta) > 1 else torch.tensor([0.5], dtype=torch.float64)
+        self._upload()
+        return self._solver.solve_path(soa, thetas, start_joints, policy=policy, weights=weights, skip_projected=skip_projected,
+                                       unwind=unwind, arm_uniform=self.arm_id, want_elbow=want_elbow, out=out, plan_only=plan_only)
+
     def theta_from_joints_batch(self, poses: Any, current_joints: Any, preferred_theta: Optional[float] = None,
                                 out: Optional[Dict[str, torch.Tensor]] = None, plan_only: bool = False) -> Dict[str, torch.Tensor]:
         """For every row, the theta whose solution is closest to that row's measured joints: is_reachable_no_limits(pose),
@@ -514,6 +549,20 @@ class DualArmIK:
         return self._solver.solve_nearest(soa, thetas, seed_joints, policy=policy, weights=weights, skip_projected=skip_projected,
                                           arm=arm_ids, previous_joints=previous_joints, want_elbow=want_elbow, out=out,
                                           plan_only=plan_only)
+
+    def path_batch(self, arm_ids: Any, poses: Any, start_joints: Any = None, n_theta: int = 16, thetas: Any = None,
+                   policy: str = "fraction", weights: Optional[Sequence[float]] = None, skip_projected: bool = False,
+                   unwind: bool = False, want_elbow: bool = True, out: Optional[Dict[str, torch.Tensor]] = None,
+                   plan_only: bool = False) -> Dict[str, torch.Tensor]:
+        """SymbolicIK.path_batch for paths of both arms (arm_ids [n] uint8, one byte per path): the least-motion sequence of elbow
+        angles along every path (index [T, n] int32, theta, joints [T,n,7], step_cost, cost [n] ...)."""
+        soa = _path_soa(poses, self._solver.device)
+        if thetas is None:
+            thetas = torch.linspace(0.0, 1.0, int(n_theta), dtype=torch.float64) if int(n_theta) > 1 else torch.tensor([0.5], dtype=torch.float64)
+        self.r_arm._upload()
+        self.l_arm._upload()
+        return self._solver.solve_path(soa, thetas, start_joints, policy=policy, weights=weights, skip_projected=skip_projected,
+                                       unwind=unwind, arm=arm_ids, want_elbow=want_elbow, out=out, plan_only=plan_only)
 
     def theta_from_joints_batch(self, arm_ids: Any, poses: Any, current_joints: Any, preferred_theta: Optional[Sequence[float]] = None,
                                 out: Optional[Dict[str, torch.Tensor]] = None, plan_only: bool = False) -> Dict[str, torch.Tensor]:
