@@ -614,15 +614,16 @@ CUSTOM_GEOMETRY = {
 }
 
 
-def gen_custom_geometry(out, n_sweep=6000, n_reach=1536):
-    rng = np.random.default_rng(9)
+def gen_custom_geometry(out, n_sweep=6000, n_reach=1536, geometry=None, seed=9, fname="g9_custom_geometry.npz"):
+    geometry = CUSTOM_GEOMETRY if geometry is None else geometry
+    rng = np.random.default_rng(seed)
     data = {}
     for arm in ARMS:
-        solver = quiet(SymbolicIK, arm=arm, **CUSTOM_GEOMETRY)
+        solver = quiet(SymbolicIK, arm=arm, **geometry)
         for f in ("gripper_size", "max_arm_length", "shoulder_wrist_min_distance", "elbow_singularity_position",
                   "wrist_singularity_position"):
             data[f"{arm}_const_{f}"] = np.asarray(getattr(solver, f), dtype=float)
-        sh = CUSTOM_GEOMETRY["ik_parameters"][f"{arm[0]}_shoulder_position"]
+        sh = geometry["ik_parameters"][f"{arm[0]}_shoulder_position"]
         pos = sh + rng.uniform(-0.7, 0.7, size=(n_sweep, 3))
         eul = rng.uniform(-np.pi, np.pi, size=(n_sweep, 3))
         rows = [solve_symbolic(solver, p, e) for p, e in zip(pos, eul)]
@@ -649,7 +650,36 @@ def gen_custom_geometry(out, n_sweep=6000, n_reach=1536):
             data[f"{arm}_reach_i0_{k}"] = v
         for k, v in stack([solve_symbolic(solver, p, e, theta_u=u) for p, e, u in zip(P, E, tu)]).items():
             data[f"{arm}_reach_in_{k}"] = v
-    np.savez_compressed(os.path.join(out, "g9_custom_geometry.npz"), **data)
+    np.savez_compressed(os.path.join(out, fname), **data)
+
+
+# ----------------------------------------------------------------------------------------
+# G20: a second non-default arm whose tip stays on the goal z axis (the tip-on-z goal stage of the kernels applies, G9's tip has
+# x / y components): other segment lengths and limits on the default shoulder.  G9's record layout, a few hundred poses per block.
+# ----------------------------------------------------------------------------------------
+ZTIP_GEOMETRY = {
+    "ik_parameters": {
+        "r_shoulder_position": np.array([0.0, -0.2, 0.0]),
+        "r_shoulder_orientation": [-15, 0, 10],
+        "r_upper_arm_size": np.float64(0.30),
+        "r_forearm_size": np.float64(0.26),
+        "r_tip_position": np.array([0.0, 0.0, 0.09]),
+        "l_shoulder_position": np.array([0.0, 0.2, 0.0]),
+        "l_shoulder_orientation": [15, 0, -10],
+        "l_upper_arm_size": np.float64(0.30),
+        "l_forearm_size": np.float64(0.26),
+        "l_tip_position": np.array([0.0, 0.0, 0.09]),
+    },
+    "elbow_limit": 115,
+    "wrist_limit": np.float64(38.0),
+    "backward_limit": 0.035,
+    "singularity_offset": 0.05,
+    "singularity_limit_coeff": 0.8,
+}
+
+
+def gen_ztip_geometry(out, n_sweep=600, n_reach=300):
+    gen_custom_geometry(out, n_sweep, n_reach, geometry=ZTIP_GEOMETRY, seed=20, fname="g20_ztip_geometry.npz")
 
 
 # ----------------------------------------------------------------------------------------
@@ -1553,7 +1583,7 @@ def main():
              ("g7", gen_continuous_start), ("g8", gen_matrix_edges),
              ("g9", gen_custom_geometry), ("g10", gen_custom_urdf_control), ("g11", gen_emergency),
              ("g12", gen_continuous_modes), ("g13", gen_hostile), ("g14", gen_scale), ("g15", gen_stages), ("g16", gen_scale_continuous), ("g17", gen_scale_variants),
-             ("g18", gen_utils)]
+             ("g18", gen_utils), ("g20", gen_ztip_geometry)]
     bad = 0
     for name, fn in steps:
         if args.only and name not in args.only.split(","):  # exact names: "g1" does not select "g12"

@@ -436,6 +436,34 @@ def test_custom_geometry(golden_dir):
         assert (g[f"{arm}_reach_i0_elbow_len"] == 3).mean() > 0.1  # the projection branch runs with this geometry too
 
 
+def test_ztip_geometry(golden_dir):
+    """G20: a second arm that is not the reference's default one and whose tip stays on the goal z axis (tests/arm_pairs.ZTIP: other
+    segment lengths and limits on the default shoulder), G9's record layout and test_custom_geometry's tolerances.  The two-arm GPU
+    tests (tests/test_gpu_arm_forms.py) take the checker on this geometry as their reference."""
+    from arm_pairs import ZTIP
+
+    g = load(golden_dir, "g20_ztip_geometry.npz")
+    ar, al = orc.Arm("r_arm", **ZTIP), orc.Arm("l_arm", **ZTIP)
+    for i, (arm, a) in enumerate((("r_arm", ar), ("l_arm", al))):
+        assert a.field("upper_arm_size") == 0.30 and a.field("forearm_size") == 0.26
+        np.testing.assert_array_equal(a.field("tip_position"), [0.0, 0.0, 0.09])
+        for f in ("gripper_size", "max_arm_length", "shoulder_wrist_min_distance", "elbow_singularity_position",
+                  "wrist_singularity_position"):
+            np.testing.assert_allclose(a.field(f), g[f"{arm}_const_{f}"], rtol=0, atol=1e-15, err_msg=f"{arm} {f}")
+        n = len(g[f"{arm}_sweep_pos"])
+        res = orc.solve_batch(ar, al, g[f"{arm}_sweep_pos"], g[f"{arm}_sweep_eul"], arm_id=np.full(n, i, np.uint8), nthreads=4)
+        _check_symbolic(res, g, f"{arm}_sweep_")
+        assert set(np.unique(g[f"{arm}_sweep_state"])) >= {0, 1, 2, 3, 4}
+        n = len(g[f"{arm}_reach_pos"])
+        aid = np.full(n, i, np.uint8)
+        res = orc.solve_batch(ar, al, g[f"{arm}_reach_pos"], g[f"{arm}_reach_eul"], arm_id=aid, nthreads=4)
+        _check_symbolic(res, g, f"{arm}_reach_i0_")
+        res = orc.solve_batch(ar, al, g[f"{arm}_reach_pos"], g[f"{arm}_reach_eul"], arm_id=aid, theta_policy=2,
+                              theta_in=g[f"{arm}_reach_theta_u"], nthreads=4)
+        _check_symbolic(res, g, f"{arm}_reach_in_")
+        assert g[f"{arm}_reach_i0_reachable"].all() and (g[f"{arm}_reach_i0_elbow_len"] == 3).mean() > 0.1
+
+
 def _custom_urdf_arms(golden_dir):
     from reachy2_symbolic_ik_amd.constants import get_ik_parameters_from_urdf
 
@@ -691,8 +719,8 @@ def test_scale_variants_checker_against_reference(golden_dir):
 def test_golden_fixtures_reproduce_from_the_reference():
     """`oracle/gen_golden.py --check`: the committed fixtures are what the reference, imported from /root/reference, produces today —
     regenerated into a temporary directory and compared array by array, byte for byte.  Here G1 (the catalogue: SymbolicIK and
-    ControlIK discrete), G6 (ControlIK continuous trajectories) and G15 (the stage methods); `--check` without `--only` does all
-    eighteen sets (~15 min: G14, the BASELINE-scale digests, takes 5 of them on 7 cores, G16 1.5, G17 2.5).
+    ControlIK discrete), G6 (ControlIK continuous trajectories), G15 (the stage methods), G18 and G20 (the tip-on-z geometry); `--check` without `--only` does
+    every set (~15 min: G14, the BASELINE-scale digests, takes 5 of them on 7 cores, G16 1.5, G17 2.5).
     Skipped where the reference is not mounted (the GPU box: it never travels)."""
     import subprocess
     import sys
@@ -701,12 +729,13 @@ def test_golden_fixtures_reproduce_from_the_reference():
         pytest.skip("/root/reference is not mounted here")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1")
-    p = subprocess.run([sys.executable, os.path.join(root, "oracle", "gen_golden.py"), "--check", "--only", "g1,g6,g15,g18"],
+    p = subprocess.run([sys.executable, os.path.join(root, "oracle", "gen_golden.py"), "--check", "--only", "g1,g6,g15,g18,g20"],
                        capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
     assert "CHECK g1_catalogue.npz: identical" in p.stdout and "CHECK g6_control_continuous.npz: identical" in p.stdout
     assert "CHECK g15_stages.npz: identical" in p.stdout
     assert "CHECK g18_utils.npz: identical" in p.stdout
+    assert "CHECK g20_ztip_geometry.npz: identical" in p.stdout
 
 
 def test_utils_helpers_on_explicit_arguments(golden_dir):
