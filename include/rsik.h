@@ -764,6 +764,9 @@ int rsik_allgather(rsik_ctx *ctx, void *comm, const void *send, void *recv, size
  * 7 the solve path's table atan2 of a UNIT vector: out0 = atan2(a, b) for a^2 + b^2 = 1,
  * 8 clock monitor: n waves each wait a[0] ticks of the 100 MHz counter (clamped to 5 s); out0[w] = shader-clock ticks,
  *   out1[w] = 100 MHz ticks that passed (core clock = out0 / out1 x 100 MHz); run it on a side stream beside a load.
+ * 9-19 the widths at which the kernels evaluate N of these in lock step (ops 3, 4 and 7 are width 1): 9, 10, 11, 12 the
+ *   unit-vector atan2 of op 7 at N = 2, 3, 4, 7; 13, 14, 15, 16 the atan2 of op 3 at N = 2, 3, 4, 7; 17, 18, 19 the sincos
+ *   of op 4 at N = 2, 3, 4.  Element i is slot i mod N of group i / N; a ragged last group is padded with (0, 1) / 0.
  * Not part of the reference surface. */
 int rsik_debug_math(rsik_ctx *ctx, int op, int64_t n, const double *a, const double *b, double *out0, double *out1);
 

@@ -84,12 +84,20 @@ __device__ __forceinline__ bool all_finite(const double (&v)[N]) {
 // Python float modulo `a % (2*pi)` (result in [0, 2pi)).  CPython computes fmod(a, b) (exact) and adds b
 // when the signs differ.  For the small quotients on this path a - q*2pi is exactly representable, so one
 // fma reproduces fmod bit for bit; the two fix-ups only fire when a*(1/2pi) rounded across an integer.
+// One value leaves [0, 2pi) in Python too and must be kept: for a negative a whose distance below a multiple of 2 pi is
+// under half an ulp of 2 pi (a in (-2^-51, 0); angle_diff's (a - b) + pi one ulp below 0) fmod(a) + 2 pi ROUNDS to fl(2 pi),
+// which is what `%` returns — angle_diff then gives +pi, not -pi.  So m >= 2 pi is only taken down where the quotient
+// q + 1 leaves a non-negative (then exact) remainder.
 __device__ __forceinline__ double pymod_2pi(double a) {
     double q = floor(a * 0.15915494309189535);
     double m = fma(-q, kTwoPi, a);
-    if (RSIK_RARE(!(m >= 0 && m < kTwoPi))) {  // a / 2pi rounded across an integer (or a is not finite)
-        if (m < 0) m += kTwoPi;
-        if (m >= kTwoPi) m -= kTwoPi;
+    if (RSIK_RARE(!(m >= 0 && m < kTwoPi))) {  // a / 2pi rounded across an integer, a just below a turn (or a is not finite)
+        if (m < 0) {
+            m += kTwoPi;
+        } else if (m >= kTwoPi) {
+            const double m1 = fma(-(q + 1.0), kTwoPi, a);
+            if (m1 >= 0) m = m1;
+        }
     }
     return m;
 }

@@ -164,7 +164,7 @@ __global__ __launch_bounds__(kBlock) void fk_kernel(const FkArgs K) {
 }
 
 // Unit-test hook for rsik_math.hpp (rsik_debug_math): op 0 rcp, 1 sqrt_cr, 2 rsqrt, 3 atan2(a,b), 4 sincos(a), 5 a % 2pi, 6 fp64 FMA issue-rate calibration,
-// 7 unit_atan2(s = a, c = b) of a unit vector
+// 7 unit_atan2(s = a, c = b) of a unit vector (8: clock_monitor_kernel, 9-19: debug_math_width_kernel, both below)
 __global__ void debug_math_kernel(int op, int64_t n, const double* a, const double* b, double* o0, double* o1) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     __shared__ double utab[3][kUnitAtanRows];
@@ -204,6 +204,39 @@ __global__ void debug_math_kernel(int op, int64_t n, const double* a, const doub
     }
     o0[i] = r0;
     if (o1) o1[i] = r1;
+}
+
+// rsik_debug_math ops 9-19: the lock-step widths of the table and polynomial functions, which the products' kernels call
+// and debug_math_kernel (width 1) does not: FN 0 unit_atan2_n<N>(s = a, c = b) (ops 9-12: N = 2, 3, 4, 7), 1 fast_atan2_n<N>(a, b)
+// (ops 13-16: N = 2, 3, 4, 7), 2 fast_sincos_n<N>(a) -> sin, cos (ops 17-19: N = 2, 3, 4).  Element i of the arrays is slot
+// i mod N of group i / N, one thread per group; the slots past n of a ragged last group are evaluated on (0, 1) / 0 and not
+// stored.  A kernel of its own per width, selected on the host: debug_math_kernel's code and registers stay as they are.
+template <int FN, int N>
+__global__ void debug_math_width_kernel(int64_t n, const double* a, const double* b, double* o0, double* o1) {
+    const int64_t base = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * N;
+    __shared__ double utab[3][kUnitAtanRows];
+    stage_sincos_tab();
+    stage_unit_atan_tab(utab);
+    __syncthreads();
+    if (base >= n) return;
+    double x[N], y[N], r0[N], r1[N];
+#pragma unroll
+    for (int j = 0; j < N; j++) {
+        const bool in = base + j < n;
+        x[j] = in ? a[base + j] : 0.0;
+        if constexpr (FN != 2) y[j] = in ? b[base + j] : 1.0;
+        r1[j] = 0.0;
+    }
+    if constexpr (FN == 0) unit_atan2_n<N>((UnitAtanTab)&utab[0][0], x, y, r0);
+    if constexpr (FN == 1) fast_atan2_n<N>(x, y, r0);
+    if constexpr (FN == 2) fast_sincos_n<N>(x, r0, r1);
+#pragma unroll
+    for (int j = 0; j < N; j++) {
+        if (base + j < n) {
+            o0[base + j] = r0[j];
+            if (o1) o1[base + j] = r1[j];
+        }
+    }
 }
 
 // rsik_debug_math op 8: clock monitor.  Each wave of the launch records the shader-clock counter (s_memtime) and the

@@ -921,14 +921,32 @@ int rsik_fk_residual(rsik_ctx* ctx, int64_t n, int goal_kind, const double* cons
 
 int rsik_debug_math(rsik_ctx* ctx, int op, int64_t n, const double* a, const double* b, double* out0, double* out1) {
     if (!ctx) return RSIK_E_INVALID;
-    if (n < 0 || op < 0 || op > 8) return fail(ctx, RSIK_E_INVALID, "rsik_debug_math: bad op or n");
+    if (n < 0 || op < 0 || op > 19) return fail(ctx, RSIK_E_INVALID, "rsik_debug_math: bad op or n");
     if (n == 0) return RSIK_OK;
-    if (!a || !out0 || ((op == 3 || op == 5 || op == 6 || op == 7) && !b)) return fail(ctx, RSIK_E_INVALID, "rsik_debug_math: NULL operand");
+    if (!a || !out0 || ((op == 3 || op == 5 || op == 6 || op == 7 || (op >= 9 && op <= 16)) && !b))
+        return fail(ctx, RSIK_E_INVALID, "rsik_debug_math: NULL operand");
     RSIK_HIP(ctx, hipSetDevice(ctx->device));
     dim3 grid, block(rsik::kBlock);
     if (op == 8) {  // clock monitor: n waves, one per 64-thread workgroup so that they spread over the chip
         if (!out1 || n > 4096) return fail(ctx, RSIK_E_INVALID, "rsik_debug_math: op 8 needs out1 and n <= 4096 waves");
         hipLaunchKernelGGL(rsik::clock_monitor_kernel, dim3((unsigned)n), dim3(64), 0, ctx->stream, a, n, out0, out1);
+        return launch_end(ctx);
+    }
+    if (op >= 9) {  // a lock-step width: one thread per group of N elements
+        static const int kWidth[11] = {2, 3, 4, 7, 2, 3, 4, 7, 2, 3, 4};
+        const int N = kWidth[op - 9];
+        int rc = launch_dims(ctx, (n + N - 1) / N, &grid, "rsik_debug_math");
+        if (rc != RSIK_OK) return rc;
+        auto go = [&](auto FN, auto W) {
+            hipLaunchKernelGGL((rsik::debug_math_width_kernel<FN(), W()>), grid, block, 0, ctx->stream, n, a, b, out0, out1);
+        };
+        auto width = [&](auto FN) {
+            using std::integral_constant;
+            if (N == 2) go(FN, integral_constant<int, 2>()); else if (N == 3) go(FN, integral_constant<int, 3>());
+            else if (N == 4) go(FN, integral_constant<int, 4>());
+            else if constexpr (FN() != 2) go(FN, integral_constant<int, 7>());
+        };
+        with_int3(op < 13 ? 0 : op < 17 ? 1 : 2, width);
         return launch_end(ctx);
     }
     int rc = launch_dims(ctx, n, &grid, "rsik_debug_math");  // (not launch_begin: the device is set above, ahead of op 8's own refusal)
