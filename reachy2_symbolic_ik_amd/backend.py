@@ -173,6 +173,47 @@ class HipSolver:
                              f"{t.dtype} {tuple(t.shape)} on {t.device}{'' if t.is_contiguous() else ' (not contiguous)'}")
         return t
 
+    def _arm_ids(self, arm, n: int) -> Optional[torch.Tensor]:
+        """The optional per-row arm ids [n] u8 of every entry point (None: the launch's arm_uniform holds)."""
+        return None if arm is None else self._dev_u8(arm, n, "arm")
+
+    # what solve_sweep, solve_nearest and solve_path share: the policy, the theta grid, the weights, the per-pose outputs
+    @staticmethod
+    def _policy_code(policy: str) -> int:
+        codes = {"fraction": _abi.THETA_FRACTION, "explicit": _abi.THETA_EXPLICIT}
+        if policy not in codes:
+            raise ValueError("policy must be 'fraction' or 'explicit'")
+        return codes[policy]
+
+    def _theta_grid(self, thetas, pose_shape: Sequence[int], pose_dims: str, k_max: int, per: str):
+        """thetas [K], shared, or [K, *pose_shape], one column per pose (`pose_dims`: that shape in words) -> (device tensor, K,
+        per_pose); K is 1 ... k_max samples per `per`."""
+        if not isinstance(thetas, torch.Tensor):
+            thetas = torch.as_tensor(np.asarray(thetas, dtype=np.float64))
+        if thetas.dim() not in (1, 1 + len(pose_shape)):
+            raise ValueError(f"thetas must have shape [K] or [K, {pose_dims}]")
+        k = int(thetas.shape[0])
+        per_pose = thetas.dim() != 1
+        if not 1 <= k <= k_max:
+            raise ValueError(f"thetas: between 1 and {k_max} samples per {per}")
+        return self._dev_f64(thetas, (k, *pose_shape) if per_pose else (k,), "thetas"), k, per_pose
+
+    @staticmethod
+    def _weights7(weights: Optional[Sequence[float]]):
+        """The 7 joint weights (None: the library's ones) -> (array to keep alive, the pointer the ABI takes)."""
+        if weights is None:
+            return None, None
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        if w.shape != (7,):
+            raise ValueError("weights must have 7 entries")
+        return w, w.ctypes.data_as(C.POINTER(C.c_double))
+
+    def _reach_outs(self, res: Dict[str, torch.Tensor], out: Optional[Dict[str, torch.Tensor]], lead: Sequence[int]) -> None:
+        """The tail of a sampling result: is_reachable's interval, reachable and state for poses of shape `lead`."""
+        res["interval"] = self._out_buf(out, "interval", (*lead, 2), _F64)
+        res["reachable"] = self._out_buf(out, "reachable", lead, _U8)
+        res["state"] = self._out_buf(out, "state", lead, _U8)
+
     # ------------------------------------------------------------------ rsik_solve
     def solve(
         self,
@@ -196,8 +237,7 @@ class HipSolver:
             raise ValueError("pose_soa must have shape [6, n]")
         n = int(pose_soa.shape[1])
         pose_soa = self._dev_cols(pose_soa, 6, n, "pose_soa")
-        if arm is not None:
-            arm = self._dev_u8(arm, n, "arm")
+        arm = self._arm_ids(arm, n)
         if theta_policy in (_abi.THETA_EXPLICIT, _abi.THETA_FRACTION):
             if theta_in is None:
                 raise ValueError("theta_in is required for this theta policy")
@@ -259,22 +299,11 @@ class HipSolver:
         plan_only=True launches nothing and adds res["launch"], a zero-overhead re-launch callable (see plan())."""
         if pose_soa.dim() != 2 or pose_soa.shape[0] != 6:
             raise ValueError("pose_soa must have shape [6, n]")
-        codes = {"fraction": _abi.THETA_FRACTION, "explicit": _abi.THETA_EXPLICIT}
-        if policy not in codes:
-            raise ValueError("policy must be 'fraction' or 'explicit'")
+        code = self._policy_code(policy)
         n = int(pose_soa.shape[1])
         pose_soa = self._dev_cols(pose_soa, 6, n, "pose_soa")
-        if not isinstance(thetas, torch.Tensor):
-            thetas = torch.as_tensor(np.asarray(thetas, dtype=np.float64))
-        if thetas.dim() not in (1, 2):
-            raise ValueError("thetas must have shape [K] or [K, n]")
-        k = int(thetas.shape[0])
-        per_pose = thetas.dim() == 2
-        if not 1 <= k <= 4096:
-            raise ValueError("thetas: between 1 and 4096 samples per pose")
-        thetas = self._dev_f64(thetas, (k, n) if per_pose else (k,), "thetas")
-        if arm is not None:
-            arm = self._dev_u8(arm, n, "arm")
+        thetas, k, per_pose = self._theta_grid(thetas, (n,), "n", 4096, "pose")
+        arm = self._arm_ids(arm, n)
         if previous_joints is not None:
             previous_joints = self._dev_f64(previous_joints, (n, 7), "previous_joints")
         res = {"joints": self._out_buf(out, "joints", (k, n, 7), _F64)}
@@ -282,11 +311,9 @@ class HipSolver:
             res["elbow"] = self._out_buf(out, "elbow", (k, n, 3), _F64)
         res["projected"] = self._out_buf(out, "projected", (k, n), _U8)
         res["theta"] = self._out_buf(out, "theta", (k, n), _F64)
-        res["interval"] = self._out_buf(out, "interval", (n, 2), _F64)
-        res["reachable"] = self._out_buf(out, "reachable", (n,), _U8)
-        res["state"] = self._out_buf(out, "state", (n,), _U8)
+        self._reach_outs(res, out, (n,))
         cols = self._cols(pose_soa, 6)
-        cargs = (n, cols, _ptr(arm), int(arm_uniform), k, codes[policy], _ptr(thetas), int(per_pose),
+        cargs = (n, cols, _ptr(arm), int(arm_uniform), k, code, _ptr(thetas), int(per_pose),
                  _ptr(previous_joints), _ptr(res["joints"]), _ptr(res.get("elbow")), _ptr(res["projected"]), _ptr(res["theta"]),
                  _ptr(res["interval"]), _ptr(res["reachable"]), _ptr(res["state"]))
         return self._finish(res, "rsik_solve_sweep", cargs, plan_only, (pose_soa, arm, thetas, cols, previous_joints))
@@ -319,42 +346,24 @@ class HipSolver:
         plan_only=True launches nothing and adds res["launch"], a zero-overhead re-launch callable (see plan())."""
         if pose_soa.dim() != 2 or pose_soa.shape[0] != 6:
             raise ValueError("pose_soa must have shape [6, n]")
-        codes = {"fraction": _abi.THETA_FRACTION, "explicit": _abi.THETA_EXPLICIT}
-        if policy not in codes:
-            raise ValueError("policy must be 'fraction' or 'explicit'")
+        code = self._policy_code(policy)
         n = int(pose_soa.shape[1])
         pose_soa = self._dev_cols(pose_soa, 6, n, "pose_soa")
-        if not isinstance(thetas, torch.Tensor):
-            thetas = torch.as_tensor(np.asarray(thetas, dtype=np.float64))
-        if thetas.dim() not in (1, 2):
-            raise ValueError("thetas must have shape [K] or [K, n]")
-        k = int(thetas.shape[0])
-        per_pose = thetas.dim() == 2
-        if not 1 <= k <= 4096:
-            raise ValueError("thetas: between 1 and 4096 samples per pose")
-        thetas = self._dev_f64(thetas, (k, n) if per_pose else (k,), "thetas")
+        thetas, k, per_pose = self._theta_grid(thetas, (n,), "n", 4096, "pose")
         seed_joints = self._dev_f64(seed_joints, (n, 7), "seed_joints")
-        if arm is not None:
-            arm = self._dev_u8(arm, n, "arm")
+        arm = self._arm_ids(arm, n)
         if previous_joints is not None:
             previous_joints = self._dev_f64(previous_joints, (n, 7), "previous_joints")
-        w, wp = None, None
-        if weights is not None:
-            w = np.ascontiguousarray(weights, dtype=np.float64)
-            if w.shape != (7,):
-                raise ValueError("weights must have 7 entries")
-            wp = w.ctypes.data_as(C.POINTER(C.c_double))
+        w, wp = self._weights7(weights)
         res = {"index": self._out_buf(out, "index", (n,), torch.int32), "theta": self._out_buf(out, "theta", (n,), _F64),
                "joints": self._out_buf(out, "joints", (n, 7), _F64)}
         if want_elbow:
             res["elbow"] = self._out_buf(out, "elbow", (n, 3), _F64)
         res["cost"] = self._out_buf(out, "cost", (n,), _F64)
         res["projected"] = self._out_buf(out, "projected", (n,), _U8)
-        res["interval"] = self._out_buf(out, "interval", (n, 2), _F64)
-        res["reachable"] = self._out_buf(out, "reachable", (n,), _U8)
-        res["state"] = self._out_buf(out, "state", (n,), _U8)
+        self._reach_outs(res, out, (n,))
         cols = self._cols(pose_soa, 6)
-        cargs = (n, cols, _ptr(arm), int(arm_uniform), k, codes[policy], _ptr(thetas), int(per_pose), _ptr(previous_joints),
+        cargs = (n, cols, _ptr(arm), int(arm_uniform), k, code, _ptr(thetas), int(per_pose), _ptr(previous_joints),
                  _ptr(seed_joints), wp, _abi.NEAREST_SKIP_PROJECTED if skip_projected else 0,
                  _ptr(res["index"]), _ptr(res["theta"]), _ptr(res["joints"]), _ptr(res.get("elbow")), _ptr(res["cost"]),
                  _ptr(res["projected"]), _ptr(res["interval"]), _ptr(res["reachable"]), _ptr(res["state"]))
@@ -400,32 +409,16 @@ class HipSolver:
         plan_only=True launches nothing and adds res["launch"], a zero-overhead re-launch callable (see plan())."""
         if pose_soa.dim() != 3 or pose_soa.shape[0] != 6:
             raise ValueError("pose_soa must have shape [6, T, n]")
-        codes = {"fraction": _abi.THETA_FRACTION, "explicit": _abi.THETA_EXPLICIT}
-        if policy not in codes:
-            raise ValueError("policy must be 'fraction' or 'explicit'")
+        code = self._policy_code(policy)
         t, n = int(pose_soa.shape[1]), int(pose_soa.shape[2])
         if not 1 <= t <= 65536:
             raise ValueError("pose_soa: between 1 and 65536 waypoints per path")
         pose_soa = self._dev_cols(pose_soa.reshape(6, t * n), 6, t * n, "pose_soa")
-        if not isinstance(thetas, torch.Tensor):
-            thetas = torch.as_tensor(np.asarray(thetas, dtype=np.float64))
-        if thetas.dim() not in (1, 3):
-            raise ValueError("thetas must have shape [K] or [K, T, n]")
-        k = int(thetas.shape[0])
-        per_pose = thetas.dim() == 3
-        if not 1 <= k <= 64:
-            raise ValueError("thetas: between 1 and 64 samples per waypoint")
-        thetas = self._dev_f64(thetas, (k, t, n) if per_pose else (k,), "thetas")
+        thetas, k, per_pose = self._theta_grid(thetas, (t, n), "T, n", 64, "waypoint")
         if start_joints is not None:
             start_joints = self._dev_f64(start_joints, (n, 7), "start_joints")
-        if arm is not None:
-            arm = self._dev_u8(arm, n, "arm")
-        w, wp = None, None
-        if weights is not None:
-            w = np.ascontiguousarray(weights, dtype=np.float64)
-            if w.shape != (7,):
-                raise ValueError("weights must have 7 entries")
-            wp = w.ctypes.data_as(C.POINTER(C.c_double))
+        arm = self._arm_ids(arm, n)
+        w, wp = self._weights7(weights)
         ws_bytes = self.solve_path_workspace_bytes(n, t, k)
         workspace = torch.empty((max(ws_bytes, 1),), dtype=_U8, device=self.device)
         res = {"index": self._out_buf(out, "index", (t, n), torch.int32), "theta": self._out_buf(out, "theta", (t, n), _F64),
@@ -436,12 +429,10 @@ class HipSolver:
         res["step_cost"] = self._out_buf(out, "step_cost", (t, n), _F64)
         res["cost"] = self._out_buf(out, "cost", (n,), _F64)
         res["n_solved"] = self._out_buf(out, "n_solved", (n,), torch.int32)
-        res["interval"] = self._out_buf(out, "interval", (t, n, 2), _F64)
-        res["reachable"] = self._out_buf(out, "reachable", (t, n), _U8)
-        res["state"] = self._out_buf(out, "state", (t, n), _U8)
+        self._reach_outs(res, out, (t, n))
         cols = self._cols(pose_soa, 6)
         flags = (_abi.PATH_SKIP_PROJECTED if skip_projected else 0) | (_abi.PATH_UNWIND if unwind else 0)
-        cargs = (n, t, cols, _ptr(arm), int(arm_uniform), k, codes[policy], _ptr(thetas), int(per_pose), _ptr(start_joints), wp, flags,
+        cargs = (n, t, cols, _ptr(arm), int(arm_uniform), k, code, _ptr(thetas), int(per_pose), _ptr(start_joints), wp, flags,
                  _ptr(workspace), ws_bytes,
                  _ptr(res["index"]), _ptr(res["theta"]), _ptr(res["joints"]), _ptr(res.get("elbow")), _ptr(res["projected"]),
                  _ptr(res["step_cost"]), _ptr(res["cost"]), _ptr(res["n_solved"]),
@@ -499,8 +490,7 @@ class HipSolver:
         m12_soa = self._dev_cols(m12_soa, 12, n, "m12_soa")
         if nb_search_points < 2:
             raise ValueError("nb_search_points must be >= 2")
-        if arm is not None:
-            arm = self._dev_u8(arm, n, "arm")
+        arm = self._arm_ids(arm, n)
         if current_joints is not None:
             current_joints = self._dev_f64(current_joints, (n, 7), "current_joints")
         if previous_sol_rows is not None:
@@ -549,8 +539,7 @@ class HipSolver:
         n = int(m12_soa.shape[1])
         m12_soa = self._dev_f64(m12_soa, (12, n), "m12_soa")
         self._check_cont_state(cont_state, n)
-        if arm is not None:
-            arm = self._dev_u8(arm, n, "arm")
+        arm = self._arm_ids(arm, n)
         if timed_out is not None:
             timed_out = self._dev_u8(timed_out, n, "timed_out")
         if current_joints is not None:
@@ -598,8 +587,7 @@ class HipSolver:
         if m12_steps.dtype != _F64 or m12_steps.device != self.device or not m12_steps.is_contiguous():
             m12_steps = m12_steps.to(device=self.device, dtype=_F64).contiguous()
         self._check_cont_state(cont_state, n)
-        if arm is not None:
-            arm = self._dev_u8(arm, n, "arm")
+        arm = self._arm_ids(arm, n)
         if current_joints is not None:
             current_joints = self._dev_f64(current_joints, (n, 7), "current_joints")
         cp = None
@@ -640,8 +628,7 @@ class HipSolver:
         n = int(pose_soa.shape[1])
         pose_soa = self._dev_f64(pose_soa, (6, n), "pose_soa")
         self._check_state(solver_state, n)
-        if arm is not None:
-            arm = self._dev_u8(arm, n, "arm")
+        arm = self._arm_ids(arm, n)
         interval = torch.empty((n, 2), dtype=_F64, device=self.device)
         reachable = torch.empty((n,), dtype=_U8, device=self.device)
         state = torch.empty((n,), dtype=_U8, device=self.device)
@@ -654,8 +641,7 @@ class HipSolver:
         n = int(solver_state.shape[0])
         self._check_state(solver_state, n)
         theta = self._dev_f64(theta, (n,), "theta")
-        if arm is not None:
-            arm = self._dev_u8(arm, n, "arm")
+        arm = self._arm_ids(arm, n)
         if previous_joints is not None:
             previous_joints = self._dev_f64(previous_joints, (n, 7), "previous_joints")
         joints = torch.empty((n, 7), dtype=_F64, device=self.device)
@@ -700,8 +686,7 @@ class HipSolver:
         if isinstance(current_joints, torch.Tensor) and current_joints.dtype != _F64:
             raise ValueError(f"current_joints must be float64, got {current_joints.dtype}")
         current_joints = self._dev_f64(current_joints, (n, 7), "current_joints")
-        if arm is not None:
-            arm = self._dev_u8(arm, n, "arm")
+        arm = self._arm_ids(arm, n)
         pref, pts = self._pair(preferred_theta, "preferred_theta")
         unknown = set(want) - {"joints", "bracket", "distance", "state"}
         if unknown:
@@ -727,8 +712,7 @@ class HipSolver:
         if width not in (7, 14):
             raise ValueError("current_joints must have shape [n, 7] or [n, 14]")
         current_joints = self._dev_f64(current_joints, (n, width), "current_joints")
-        if arm is not None:
-            arm = self._dev_u8(arm, n, "arm")
+        arm = self._arm_ids(arm, n)
         pref, pts = self._pair(preferred_theta, "preferred_theta")  # (pref: alive until the call returns)
         theta = torch.empty((n,), dtype=_F64, device=self.device)
         bracket = torch.empty((n, 2), dtype=_F64, device=self.device)
@@ -785,8 +769,7 @@ class HipSolver:
         """joints [n,7] -> (goal position [n,3], goal rotation [n,3,3]) in the torso frame (rsik_forward_kinematics)."""
         n = int(joints.shape[0])
         joints = self._dev_f64(joints, (n, 7), "joints")
-        if arm is not None:
-            arm = self._dev_u8(arm, n, "arm")
+        arm = self._arm_ids(arm, n)
         pos = torch.empty((n, 3), dtype=_F64, device=self.device)
         rot = torch.empty((n, 3, 3), dtype=_F64, device=self.device)
         self._call("rsik_forward_kinematics", n, _ptr(joints), _ptr(arm), int(arm_uniform), _ptr(pos), _ptr(rot))
@@ -801,8 +784,7 @@ class HipSolver:
         rows, n = int(goal_soa.shape[0]), int(goal_soa.shape[1])
         goal_soa = self._dev_f64(goal_soa, (rows, n), "goal_soa")
         joints = self._dev_f64(joints, (n, 7), "joints")
-        if arm is not None:
-            arm = self._dev_u8(arm, n, "arm")
+        arm = self._arm_ids(arm, n)
         err = torch.empty((n, 2), dtype=_F64, device=self.device)
         kind = _abi.GOAL_M12 if rows == 12 else _abi.GOAL_POSE6
         self._call("rsik_fk_residual", n, kind, self._cols(goal_soa, rows), _ptr(joints), _ptr(arm), int(arm_uniform), _ptr(err))

@@ -210,13 +210,7 @@ __global__ __launch_bounds__(kBlock, RSIK_PATH_MIN_WAVES) void solve_path_kernel
         for (int c = 0; c < 6; c++) in[c] = ld_stream(K.in[c] + row);
         const bool invalid = !all_finite(in);  // rsik.h "Rows that are not numbers"
         const V3 pos = {in[0], in[1], in[2]};
-        Goal G;
-        if constexpr (TIPZ) {
-            G = goal_from_euler_tipz(A, in[3], in[4], in[5]);
-        } else {
-            const Rot Rg = rot_from_euler(in[3], in[4], in[5]);
-            G = make_goal(A, Rg);
-        }
+        const Goal G = goal_of_pose<TIPZ>(A, in[3], in[4], in[5]);
         Reach r = reach_g<false, false>(A, pos, G.woff);
         if (RSIK_RARE(invalid)) reach_invalid_input(r);
         if (out) store_reach(K, live, row, 0u, r);

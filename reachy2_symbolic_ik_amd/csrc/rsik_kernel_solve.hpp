@@ -247,6 +247,11 @@ __device__ __forceinline__ void branch_stores_stay() { asm volatile("" ::: "memo
 
 // ---- what solve_kernel and solve_sweep_kernel (rsik_kernel_sweep.hpp) share, templated on the argument block and the accessor type: each
 // keeps instantiations of its own (see AccSweep).  Not the tile indices and the six pose loads: in a function both kernels compile differently.
+// Nor, for the sweep and nearest kernels, the body of their sample loop: one "joints at this sample" function in place of the
+// `if constexpr (PREV_ROWS)` pair, with one "stage the row / stage a NaN row" function, compiled 48 instantiations differently (every
+// sweep and every nearest kernel: sweep PREV_ROWS 10 instructions shorter, nearest 1 to 14 longer).  What is shared below is what
+// scripts/compare_kernel_asm.py showed to leave every instantiation instruction for instruction as it was; a further helper goes
+// through the same comparison, one at a time.
 // The kernarg warm-up and the table staging.  (MIXED == 1 takes every constant from LDS: nothing to warm.  Here the warm-up goes BEFORE
 // the staging loads are issued, in the other kernels between their issue and their use (stage_tables<., WARM>): measured both ways per
 // kernel, config 2 31.1 vs 31.9 us, config 3 15.9 vs 15.7 us)
@@ -265,6 +270,13 @@ __device__ __forceinline__ ACC kernarg_acc(SharedTables& S, int slot) {
 }
 __device__ __forceinline__ void reach_invalid_input(Reach& r) {  // rsik.h "Rows that are not numbers": the reference raises (S:580) or projects an infinity
     r.ok = false; r.state = RSIK_STATE_INVALID_INPUT; r.i0 = r.i1 = __builtin_nan("");
+}
+// The goal stage of the sweep, nearest and path kernels: the goal's three vectors from the pose's Euler angles.  (solve_kernel spells
+// the same two forms out, for the RSIK_MARKs between their halves.)
+template <bool TIPZ, class ACC>
+__device__ __forceinline__ Goal goal_of_pose(const ACC& A, double roll, double pitch, double yaw) {
+    if constexpr (TIPZ) return goal_from_euler_tipz(A, roll, pitch, yaw);
+    else return make_goal(A, rot_from_euler(roll, pitch, yaw));
 }
 // the per-pose outputs of is_reachable: interval, reachable, state (each optional)
 template <class ARGS>

@@ -68,13 +68,7 @@ __global__ __launch_bounds__(kBlock, RSIK_SWEEP_MIN_WAVES) void solve_sweep_kern
 
     const bool invalid = !all_finite(in);  // rsik.h "Rows that are not numbers"
     const V3 pos = {in[0], in[1], in[2]};
-    Goal G;
-    if constexpr (TIPZ) {
-        G = goal_from_euler_tipz(A, in[3], in[4], in[5]);
-    } else {
-        const Rot Rg = rot_from_euler(in[3], in[4], in[5]);
-        G = make_goal(A, Rg);
-    }
+    const Goal G = goal_of_pose<TIPZ>(A, in[3], in[4], in[5]);
     Reach r = reach_g<false, false>(A, pos, G.woff);
     if (RSIK_RARE(invalid)) reach_invalid_input(r);
     store_reach(K, live, tile0, t, r);

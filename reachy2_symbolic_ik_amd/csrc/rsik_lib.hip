@@ -3,7 +3,8 @@
 // rsik_control_continuous_run in rsik_cont_run.hpp.
 // Every launching entry point reads: its own checks, in its own order (the return code and the message that wins are part of the
 // ABI), fill the kernel's argument block K, launch_begin, one launch line, launch_end.  What they share is below the memcpy entry
-// points: check_arms, bind_arms, copy_cols, launch_form / tip_on_z, launch_dims / launch_begin / launch_end.
+// points: check_arms, bind_arms, copy_cols, launch_form / tip_on_z, launch_dims / launch_begin / launch_end; and, for the sampling
+// family (rsik_solve_sweep, rsik_solve_nearest, rsik_solve_path), check_samples, check_sample_inputs and fill_samples.
 //
 // Kernel shape: one pose per lane, 256-thread workgroups (4 wave64), SoA float64 inputs so that
 // every global load is a fully coalesced 512-B wave access; the [n,7] / [n,3] row outputs are
@@ -325,6 +326,57 @@ static int slot_arm(const uint8_t* arm, int arm_uniform, int slot) { return arm 
 static void bind_arms(const rsik_ctx* ctx, const uint8_t* arm, int arm_uniform, rsik::ArmC (&arms)[2]) {
     for (int slot = 0; slot < 2; slot++) arms[slot] = ctx->arms[slot_arm(arm, arm_uniform, slot)];
 }
+// seven joints' worth of host values into an argument block: the caller's, or `otherwise` for each where it passed NULL
+static void fill7(double (&dst)[7], const double* src_host, double otherwise) {
+    for (int k = 0; k < 7; k++) dst[k] = src_host ? src_host[k] : otherwise;
+}
+
+// The sampling family (rsik_solve_sweep, rsik_solve_nearest, rsik_solve_path): the same poses, the same theta grid and the same
+// per-pose interval / reachable / state.  What their host side shares is here.  A check only one of them makes stays in that entry
+// point, between the shared ones: the order of the checks, and with it the fault a call with two of them reports, is part of the ABI.
+// The checks on the sample arguments, in that order: n_theta, theta_policy, flags, weights, arms.
+static int check_samples(rsik_ctx* ctx, const char* who, int n_theta, int n_theta_max, int theta_policy, int flags, int flags_mask,
+                         const double* weights_host, const uint8_t* arm, int arm_uniform) {
+    const std::string w(who);
+    if (n_theta < 1 || n_theta > n_theta_max) return fail(ctx, RSIK_E_INVALID, w + ": n_theta must be in [1, " + std::to_string(n_theta_max) + "]");
+    if (theta_policy != RSIK_THETA_EXPLICIT && theta_policy != RSIK_THETA_FRACTION)
+        return fail(ctx, RSIK_E_INVALID, w + ": theta_policy must be RSIK_THETA_EXPLICIT or RSIK_THETA_FRACTION");
+    if (flags & ~flags_mask) return fail(ctx, RSIK_E_INVALID, w + ": unknown bits in flags");
+    for (int q = 0; weights_host && q < 7; q++)
+        if (!(weights_host[q] >= 0.0 && std::isfinite(weights_host[q]))) return fail(ctx, RSIK_E_INVALID, w + ": every weight must be finite and >= 0");
+    return check_arms(ctx, arm, arm_uniform, who);
+}
+// the inputs no launch of n > 0 goes without
+static int check_sample_inputs(rsik_ctx* ctx, const char* who, const double* const pose_soa[6], const double* theta_in) {
+    if (!pose_soa) return fail(ctx, RSIK_E_INVALID, std::string(who) + ": pose_soa is NULL");
+    if (!theta_in) return fail(ctx, RSIK_E_INVALID, std::string(who) + ": theta_in is NULL");
+    return RSIK_OK;
+}
+extern "C++" {  // (templates)
+// The fields SweepArgs, NearestArgs and PathArgs have in common, by name (the structs stay apart: each is its kernel's kernarg layout)
+template <class ARGS>
+static int fill_samples(rsik_ctx* ctx, const char* who, ARGS& K, int64_t n, const double* const pose_soa[6], const uint8_t* arm, int arm_uniform,
+                        int n_theta, int theta_policy, const double* theta_in, int theta_per_pose, double* interval, uint8_t* reachable, uint8_t* state) {
+    K.n = n;
+    const int rc = copy_cols(ctx, who, "pose_soa", "a pose_soa column", pose_soa, K.in, 6);
+    if (rc != RSIK_OK) return rc;
+    K.arm = arm;
+    K.theta_policy = theta_policy;
+    K.n_theta = n_theta;
+    K.theta_per_pose = theta_per_pose != 0;
+    K.theta_in = theta_in;
+    K.interval = interval; K.reachable = reachable; K.state = state;
+    bind_arms(ctx, arm, arm_uniform, K.arms);
+    return RSIK_OK;
+}
+// get_joints' previous_joints of an argument block that holds either form (rsik_solve and rsik_solve_rows too): one device row per
+// pose, or one host row for every pose
+template <class ARGS>
+static void bind_prev(ARGS& K, const double* rows, const double* host) {
+    if (rows) K.prev_rows = rows;  // (shares its kernarg bytes with K.prev)
+    else fill7(K.prev, host, 0.0);
+}
+}
 
 // rsik_solve (previous_rows == NULL: previous_joints_host for every pose) and rsik_solve_rows (previous_rows: one device row per pose)
 static int solve_impl(rsik_ctx* ctx, const char* who, int64_t n, const double* const pose_soa[6], const uint8_t* arm, int arm_uniform,
@@ -345,8 +397,7 @@ static int solve_impl(rsik_ctx* ctx, const char* who, int64_t n, const double* c
     K.arm = arm;
     K.theta_policy = theta_policy;
     K.theta_in = theta_in;
-    if (previous_rows) K.prev_rows = previous_rows;  // (shares its kernarg bytes with K.prev)
-    else for (int k = 0; k < 7; k++) K.prev[k] = previous_joints_host ? previous_joints_host[k] : 0.0;
+    bind_prev(K, previous_rows, previous_joints_host);
     K.joints = joints; K.interval = interval; K.elbow = elbow; K.reachable = reachable; K.state = state;
     bind_arms(ctx, arm, arm_uniform, K.arms);
     dim3 grid, block(rsik::kBlock);
@@ -383,28 +434,15 @@ int rsik_solve_sweep(rsik_ctx* ctx, int64_t n, const double* const pose_soa[6], 
     const char* who = "rsik_solve_sweep";
     const std::string w(who);
     if (n < 0) return fail(ctx, RSIK_E_INVALID, w + ": n < 0");
-    if (n_theta < 1 || n_theta > 4096) return fail(ctx, RSIK_E_INVALID, w + ": n_theta must be in [1, 4096]");
-    if (theta_policy != RSIK_THETA_EXPLICIT && theta_policy != RSIK_THETA_FRACTION)
-        return fail(ctx, RSIK_E_INVALID, w + ": theta_policy must be RSIK_THETA_EXPLICIT or RSIK_THETA_FRACTION");
-    int rc = check_arms(ctx, arm, arm_uniform, who);
+    int rc = check_samples(ctx, who, n_theta, 4096, theta_policy, 0, 0, nullptr, arm, arm_uniform);
     if (rc != RSIK_OK) return rc;
     if (n == 0) return RSIK_OK;
-    if (!pose_soa) return fail(ctx, RSIK_E_INVALID, w + ": pose_soa is NULL");
-    if (!theta_in) return fail(ctx, RSIK_E_INVALID, w + ": theta_in is NULL");
+    if ((rc = check_sample_inputs(ctx, who, pose_soa, theta_in)) != RSIK_OK) return rc;
     if (!joints) return fail(ctx, RSIK_E_INVALID, w + ": joints is NULL");
     rsik::SweepArgs K;
-    K.n = n;
-    if ((rc = copy_cols(ctx, who, "pose_soa", "a pose_soa column", pose_soa, K.in, 6)) != RSIK_OK) return rc;
-    K.arm = arm;
-    K.theta_policy = theta_policy;
-    K.n_theta = n_theta;
-    K.theta_per_pose = theta_per_pose != 0;
-    K.theta_in = theta_in;
-    if (previous_joints) K.prev_rows = previous_joints;  // (shares its kernarg bytes with K.prev)
-    else for (int k = 0; k < 7; k++) K.prev[k] = 0.0;
+    if ((rc = fill_samples(ctx, who, K, n, pose_soa, arm, arm_uniform, n_theta, theta_policy, theta_in, theta_per_pose, interval, reachable, state)) != RSIK_OK) return rc;
+    bind_prev(K, previous_joints, nullptr);
     K.joints = joints; K.elbow = elbow; K.projected = projected; K.theta = theta;
-    K.interval = interval; K.reachable = reachable; K.state = state;
-    bind_arms(ctx, arm, arm_uniform, K.arms);
     dim3 grid, block(rsik::kBlock);
     if ((rc = launch_begin(ctx, n, &grid, who)) != RSIK_OK) return rc;
     with_int3(launch_form(ctx, K.arms, arm), [&](auto FORM) { with_bool(tip_on_z(ctx, K.arms), [&](auto TIPZ) { with_bool(previous_joints != nullptr, [&](auto PREV_ROWS) {
@@ -433,35 +471,19 @@ int rsik_solve_nearest(rsik_ctx* ctx, int64_t n, const double* const pose_soa[6]
     const char* who = "rsik_solve_nearest";
     const std::string w(who);
     if (n < 0) return fail(ctx, RSIK_E_INVALID, w + ": n < 0");
-    if (n_theta < 1 || n_theta > 4096) return fail(ctx, RSIK_E_INVALID, w + ": n_theta must be in [1, 4096]");
-    if (theta_policy != RSIK_THETA_EXPLICIT && theta_policy != RSIK_THETA_FRACTION)
-        return fail(ctx, RSIK_E_INVALID, w + ": theta_policy must be RSIK_THETA_EXPLICIT or RSIK_THETA_FRACTION");
-    if (flags & ~RSIK_NEAREST_SKIP_PROJECTED) return fail(ctx, RSIK_E_INVALID, w + ": unknown bits in flags");
-    for (int q = 0; weights_host && q < 7; q++)
-        if (!(weights_host[q] >= 0.0 && std::isfinite(weights_host[q]))) return fail(ctx, RSIK_E_INVALID, w + ": every weight must be finite and >= 0");
-    int rc = check_arms(ctx, arm, arm_uniform, who);
+    int rc = check_samples(ctx, who, n_theta, 4096, theta_policy, flags, RSIK_NEAREST_SKIP_PROJECTED, weights_host, arm, arm_uniform);
     if (rc != RSIK_OK) return rc;
     if (n == 0) return RSIK_OK;
-    if (!pose_soa) return fail(ctx, RSIK_E_INVALID, w + ": pose_soa is NULL");
-    if (!theta_in) return fail(ctx, RSIK_E_INVALID, w + ": theta_in is NULL");
+    if ((rc = check_sample_inputs(ctx, who, pose_soa, theta_in)) != RSIK_OK) return rc;
     if (!seed_joints) return fail(ctx, RSIK_E_INVALID, w + ": seed_joints is NULL");
     if (!index && !theta && !joints) return fail(ctx, RSIK_E_INVALID, w + ": index, theta and joints are all NULL");
     rsik::NearestArgs K;
-    K.n = n;
-    if ((rc = copy_cols(ctx, who, "pose_soa", "a pose_soa column", pose_soa, K.in, 6)) != RSIK_OK) return rc;
-    K.arm = arm;
-    K.theta_policy = theta_policy;
-    K.n_theta = n_theta;
-    K.theta_per_pose = theta_per_pose != 0;
+    if ((rc = fill_samples(ctx, who, K, n, pose_soa, arm, arm_uniform, n_theta, theta_policy, theta_in, theta_per_pose, interval, reachable, state)) != RSIK_OK) return rc;
     K.skip_projected = (flags & RSIK_NEAREST_SKIP_PROJECTED) != 0;
-    K.theta_in = theta_in;
-    if (previous_joints) K.prev_rows = previous_joints;  // (shares its kernarg bytes with K.prev)
-    else for (int k = 0; k < 7; k++) K.prev[k] = 0.0;
+    bind_prev(K, previous_joints, nullptr);
     K.seed = seed_joints;
-    for (int q = 0; q < 7; q++) K.weights[q] = weights_host ? weights_host[q] : 1.0;
+    fill7(K.weights, weights_host, 1.0);
     K.index = index; K.theta = theta; K.joints = joints; K.elbow = elbow; K.cost = cost; K.projected = projected;
-    K.interval = interval; K.reachable = reachable; K.state = state;
-    bind_arms(ctx, arm, arm_uniform, K.arms);
     const int lanes = ctx->options[RSIK_OPT_NEAREST_LANES] ? ctx->options[RSIK_OPT_NEAREST_LANES] : nearest_lanes(n, n_theta);
     dim3 grid, block(rsik::kBlock);
     if ((rc = launch_begin(ctx, n, &grid, who, rsik::kBlock / lanes)) != RSIK_OK) return rc;
@@ -496,40 +518,25 @@ int rsik_solve_path(rsik_ctx* ctx, int64_t n, int64_t n_steps, const double* con
     const std::string w(who);
     if (n < 0) return fail(ctx, RSIK_E_INVALID, w + ": n < 0");
     if (n_steps < 1 || n_steps > 65536) return fail(ctx, RSIK_E_INVALID, w + ": n_steps must be in [1, 65536]");
-    if (n_theta < 1 || n_theta > 64) return fail(ctx, RSIK_E_INVALID, w + ": n_theta must be in [1, 64]");
-    if (theta_policy != RSIK_THETA_EXPLICIT && theta_policy != RSIK_THETA_FRACTION)
-        return fail(ctx, RSIK_E_INVALID, w + ": theta_policy must be RSIK_THETA_EXPLICIT or RSIK_THETA_FRACTION");
-    if (flags & ~(RSIK_PATH_SKIP_PROJECTED | RSIK_PATH_UNWIND)) return fail(ctx, RSIK_E_INVALID, w + ": unknown bits in flags");
-    for (int q = 0; weights_host && q < 7; q++)
-        if (!(weights_host[q] >= 0.0 && std::isfinite(weights_host[q]))) return fail(ctx, RSIK_E_INVALID, w + ": every weight must be finite and >= 0");
-    int rc = check_arms(ctx, arm, arm_uniform, who);
+    int rc = check_samples(ctx, who, n_theta, 64, theta_policy, flags, RSIK_PATH_SKIP_PROJECTED | RSIK_PATH_UNWIND, weights_host, arm, arm_uniform);
     if (rc != RSIK_OK) return rc;
     if (n == 0) return RSIK_OK;
-    if (!pose_soa) return fail(ctx, RSIK_E_INVALID, w + ": pose_soa is NULL");
-    if (!theta_in) return fail(ctx, RSIK_E_INVALID, w + ": theta_in is NULL");
+    if ((rc = check_sample_inputs(ctx, who, pose_soa, theta_in)) != RSIK_OK) return rc;
     if (!index && !theta && !joints) return fail(ctx, RSIK_E_INVALID, w + ": index, theta and joints are all NULL");
     size_t need = 0;
     if (!path_workspace_bytes(n, n_steps, n_theta, &need)) return fail(ctx, RSIK_E_INVALID, w + ": n * n_steps too large");
     if (!workspace || workspace_bytes < need) return fail(ctx, RSIK_E_INVALID, w + ": workspace is NULL or smaller than rsik_solve_path_workspace_bytes");
     rsik::PathArgs K;
-    K.n = n;
+    if ((rc = fill_samples(ctx, who, K, n, pose_soa, arm, arm_uniform, n_theta, theta_policy, theta_in, theta_per_pose, interval, reachable, state)) != RSIK_OK) return rc;
     K.n_steps = n_steps;
-    if ((rc = copy_cols(ctx, who, "pose_soa", "a pose_soa column", pose_soa, K.in, 6)) != RSIK_OK) return rc;
-    K.arm = arm;
-    K.theta_policy = theta_policy;
-    K.n_theta = n_theta;
-    K.theta_per_pose = theta_per_pose != 0;
     K.skip_projected = (flags & RSIK_PATH_SKIP_PROJECTED) != 0;
     K.unwind = (flags & RSIK_PATH_UNWIND) != 0;
-    K.theta_in = theta_in;
-    for (int k = 0; k < 7; k++) K.prev[k] = 0.0;
+    fill7(K.prev, nullptr, 0.0);
     K.start = start_joints;
-    for (int q = 0; q < 7; q++) K.weights[q] = weights_host ? weights_host[q] : 1.0;
+    fill7(K.weights, weights_host, 1.0);
     K.back = static_cast<uint8_t*>(workspace);
     K.index = index; K.theta = theta; K.joints = joints; K.elbow = elbow; K.projected = projected;
     K.step_cost = step_cost; K.cost = cost; K.n_solved = n_solved;
-    K.interval = interval; K.reachable = reachable; K.state = state;
-    bind_arms(ctx, arm, arm_uniform, K.arms);
     dim3 grid, block(rsik::kBlock);
     if ((rc = launch_begin(ctx, n, &grid, who, rsik::kBlock / 64)) != RSIK_OK) return rc;
     with_int3(launch_form(ctx, K.arms, arm), [&](auto FORM) { with_bool(tip_on_z(ctx, K.arms), [&](auto TIPZ) {

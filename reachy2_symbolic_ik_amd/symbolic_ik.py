@@ -307,18 +307,7 @@ class SymbolicIK:
         one launch, rsik_solve_rows).
         Returns device tensors: joints [n,7], interval [n,2], elbow [n,3], reachable [n] u8, state [n] u8.
         """
-        soa = poses_to_soa(poses, self._solver.device)
-        theta_in = None
-        if isinstance(theta, str):
-            policy = _THETA_POLICIES[theta]
-        else:
-            policy = _THETA_POLICIES[theta[0]]
-            theta_in = theta[1]
-        self._upload()
-        previous_joints, rows = _split_previous_joints(previous_joints)
-        return self._solver.solve(soa, arm_uniform=self.arm_id, theta_policy=policy, theta_in=theta_in,
-                                  previous_joints=previous_joints, want_elbow=want_elbow, out=out, plan_only=plan_only,
-                                  previous_joints_rows=rows)
+        return _solve_batch(self, {"arm_uniform": self.arm_id}, poses, theta, previous_joints, want_elbow, out, plan_only)
 
     def sweep_batch(self, poses: Any, thetas: Any = None, n_theta: int = 16, policy: str = "fraction",
                     previous_joints: Any = None, want_elbow: bool = True,
@@ -332,12 +321,7 @@ class SymbolicIK:
         Returns device tensors, sample-major: joints [K,n,7], elbow [K,n,3], projected [K,n] u8 (1: the elbow projection moved
         the goal, the joints reach the moved goal), theta [K,n], interval [n,2], reachable [n] u8, state [n] u8.
         joints.permute(1, 0, 2) is the per-pose view [n,K,7]."""
-        soa = poses_to_soa(poses, self._solver.device)
-        if thetas is None:
-            thetas = torch.linspace(0.0, 1.0, int(n_theta), dtype=torch.float64)
-        self._upload()
-        return self._solver.solve_sweep(soa, thetas, policy=policy, arm_uniform=self.arm_id, previous_joints=previous_joints,
-                                        want_elbow=want_elbow, out=out)
+        return _sweep_batch(self, {"arm_uniform": self.arm_id}, poses, thetas, n_theta, policy, previous_joints, want_elbow, out)
 
     def nearest_batch(self, poses: Any, seed_joints: Any, n_theta: int = 64, thetas: Any = None, policy: str = "fraction",
                       weights: Optional[Sequence[float]] = None, skip_projected: bool = False, previous_joints: Any = None,
@@ -352,13 +336,8 @@ class SymbolicIK:
         squared joint differences (None: ones).  skip_projected: samples whose elbow projection moved the goal cannot win.
         Returns device tensors: index [n] int32 (-1: no candidate), theta [n], joints [n,7], elbow [n,3], projected [n] u8,
         cost [n], interval [n,2], reachable [n] u8, state [n] u8."""
-        soa = poses_to_soa(poses, self._solver.device)
-        if thetas is None:
-            thetas = torch.linspace(0.0, 1.0, int(n_theta), dtype=torch.float64)
-        self._upload()
-        return self._solver.solve_nearest(soa, thetas, seed_joints, policy=policy, weights=weights, skip_projected=skip_projected,
-                                          arm_uniform=self.arm_id, previous_joints=previous_joints, want_elbow=want_elbow,
-                                          out=out, plan_only=plan_only)
+        return _nearest_batch(self, {"arm_uniform": self.arm_id}, poses, seed_joints, n_theta, thetas, policy, weights, skip_projected,
+                              previous_joints, want_elbow, out, plan_only)
 
     def path_batch(self, poses: Any, start_joints: Any = None, n_theta: int = 16, thetas: Any = None, policy: str = "fraction",
                    weights: Optional[Sequence[float]] = None, skip_projected: bool = False, unwind: bool = False,
@@ -375,12 +354,8 @@ class SymbolicIK:
         Returns device tensors: index [T, n] int32 (-1: a waypoint without a candidate, skipped), theta [T,n], joints [T,n,7],
         elbow [T,n,3], projected [T,n] u8, step_cost [T,n], cost [n], n_solved [n] int32, interval [T,n,2], reachable [T,n] u8,
         state [T,n] u8."""
-        soa = _path_soa(poses, self._solver.device)
-        if thetas is None:
-            thetas = torch.linspace(0.0, 1.0, int(n_theta), dtype=torch.float64) if int(n_theta) > 1 else torch.tensor([0.5], dtype=torch.float64)
-        self._upload()
-        return self._solver.solve_path(soa, thetas, start_joints, policy=policy, weights=weights, skip_projected=skip_projected,
-                                       unwind=unwind, arm_uniform=self.arm_id, want_elbow=want_elbow, out=out, plan_only=plan_only)
+        return _path_batch(self, {"arm_uniform": self.arm_id}, poses, start_joints, n_theta, thetas, policy, weights, skip_projected,
+                           unwind, want_elbow, out, plan_only)
 
     def theta_from_joints_batch(self, poses: Any, current_joints: Any, preferred_theta: Optional[float] = None,
                                 out: Optional[Dict[str, torch.Tensor]] = None, plan_only: bool = False) -> Dict[str, torch.Tensor]:
@@ -389,12 +364,9 @@ class SymbolicIK:
         one launch.  poses: [n,2,3] or SoA [6,n] (the pose each arm is in); current_joints: [n,7]; preferred_theta: tried
         first (default: ControlIK's for this arm, -4 pi / 6 for r and its mirror image for l).
         Returns device tensors theta [n], joints [n,7], bracket [n,2], distance [n], state [n] u8 (HipSolver.theta_from_joints)."""
-        soa = poses_to_soa(poses, self._solver.device)
         if preferred_theta is None:
             preferred_theta = default_preferred_theta(self.arm_id)
-        self._upload()
-        return self._solver.theta_from_joints(soa, current_joints, [float(preferred_theta)] * 2, arm_uniform=self.arm_id,
-                                              out=out, plan_only=plan_only)
+        return _theta_from_joints_batch(self, {"arm_uniform": self.arm_id}, poses, current_joints, [float(preferred_theta)] * 2, out, plan_only)
 
     def is_reachable_batch(self, poses: Any) -> Dict[str, torch.Tensor]:
         return self.solve_batch(poses, theta="none")
@@ -493,6 +465,58 @@ def _split_previous_joints(previous_joints: Any):
     return previous_joints, None
 
 
+# ---- the batch methods of SymbolicIK and DualArmIK: one implementation each.  `ik` is either object (its solver, its _upload());
+# `arm` is what tells the backend whose rows these are: {"arm_uniform": id} for one arm, {"arm": arm_ids} for rows of both.
+def _default_grid(thetas: Any, n_theta: int, single: Optional[float]) -> Any:
+    """The caller's thetas, or `n_theta` evenly spaced fractions from 0 to 1 inclusive.  `single`: what stands for a grid of fewer
+    than two samples (path_batch: the middle of the interval); None: linspace's own answer (sweep_batch, nearest_batch)."""
+    if thetas is not None:
+        return thetas
+    if single is None or int(n_theta) > 1:
+        return torch.linspace(0.0, 1.0, int(n_theta), dtype=torch.float64)
+    return torch.tensor([single], dtype=torch.float64)
+
+
+def _solve_batch(ik, arm, poses, theta, previous_joints, want_elbow, out, plan_only):
+    soa = poses_to_soa(poses, ik._solver.device)
+    name, theta_in = (theta, None) if isinstance(theta, str) else (theta[0], theta[1])  # a policy name, or (name, tensor[n])
+    policy = _THETA_POLICIES[name]
+    ik._upload()
+    previous_joints, rows = _split_previous_joints(previous_joints)
+    return ik._solver.solve(soa, theta_policy=policy, theta_in=theta_in, previous_joints=previous_joints, want_elbow=want_elbow,
+                            out=out, plan_only=plan_only, previous_joints_rows=rows, **arm)
+
+
+def _sweep_batch(ik, arm, poses, thetas, n_theta, policy, previous_joints, want_elbow, out):
+    soa = poses_to_soa(poses, ik._solver.device)
+    thetas = _default_grid(thetas, n_theta, None)
+    ik._upload()
+    return ik._solver.solve_sweep(soa, thetas, policy=policy, previous_joints=previous_joints, want_elbow=want_elbow, out=out, **arm)
+
+
+def _nearest_batch(ik, arm, poses, seed_joints, n_theta, thetas, policy, weights, skip_projected, previous_joints, want_elbow, out,
+                   plan_only):
+    soa = poses_to_soa(poses, ik._solver.device)
+    thetas = _default_grid(thetas, n_theta, None)
+    ik._upload()
+    return ik._solver.solve_nearest(soa, thetas, seed_joints, policy=policy, weights=weights, skip_projected=skip_projected,
+                                    previous_joints=previous_joints, want_elbow=want_elbow, out=out, plan_only=plan_only, **arm)
+
+
+def _path_batch(ik, arm, poses, start_joints, n_theta, thetas, policy, weights, skip_projected, unwind, want_elbow, out, plan_only):
+    soa = _path_soa(poses, ik._solver.device)
+    thetas = _default_grid(thetas, n_theta, 0.5)
+    ik._upload()
+    return ik._solver.solve_path(soa, thetas, start_joints, policy=policy, weights=weights, skip_projected=skip_projected,
+                                 unwind=unwind, want_elbow=want_elbow, out=out, plan_only=plan_only, **arm)
+
+
+def _theta_from_joints_batch(ik, arm, poses, current_joints, preferred_theta, out, plan_only):
+    soa = poses_to_soa(poses, ik._solver.device)
+    ik._upload()
+    return ik._solver.theta_from_joints(soa, current_joints, preferred_theta, out=out, plan_only=plan_only, **arm)
+
+
 class DualArmIK:
     """Mixed r/l batches in one launch (BASELINE config 4): two SymbolicIK objects sharing one device context, the arm
     of every pose given by a uint8 array (0 = r_arm, 1 = l_arm)."""
@@ -506,34 +530,21 @@ class DualArmIK:
     def solver(self) -> HipSolver:
         return self._solver
 
+    def _upload(self) -> None:
+        self.r_arm._upload()
+        self.l_arm._upload()
+
     def solve_batch(self, arm_ids: Any, poses: Any, theta: Any = "interval0", previous_joints: Optional[Sequence[float]] = None,
                     want_elbow: bool = True, out: Optional[Dict[str, torch.Tensor]] = None,
                     plan_only: bool = False) -> Dict[str, torch.Tensor]:
-        soa = poses_to_soa(poses, self._solver.device)
-        theta_in = None
-        if isinstance(theta, str):
-            policy = _THETA_POLICIES[theta]
-        else:
-            policy = _THETA_POLICIES[theta[0]]
-            theta_in = theta[1]
-        self.r_arm._upload()
-        self.l_arm._upload()
-        previous_joints, rows = _split_previous_joints(previous_joints)
-        return self._solver.solve(soa, arm=arm_ids, theta_policy=policy, theta_in=theta_in, previous_joints=previous_joints,
-                                  want_elbow=want_elbow, out=out, plan_only=plan_only, previous_joints_rows=rows)
+        return _solve_batch(self, {"arm": arm_ids}, poses, theta, previous_joints, want_elbow, out, plan_only)
 
     def sweep_batch(self, arm_ids: Any, poses: Any, thetas: Any = None, n_theta: int = 16, policy: str = "fraction",
                     previous_joints: Any = None, want_elbow: bool = True,
                     out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
         """SymbolicIK.sweep_batch for rows of both arms (arm_ids [n] uint8): K elbow angles per pose in one launch.  Returns
         sample-major tensors (joints [K,n,7] ...); joints.permute(1, 0, 2) is the per-pose view [n,K,7]."""
-        soa = poses_to_soa(poses, self._solver.device)
-        if thetas is None:
-            thetas = torch.linspace(0.0, 1.0, int(n_theta), dtype=torch.float64)
-        self.r_arm._upload()
-        self.l_arm._upload()
-        return self._solver.solve_sweep(soa, thetas, policy=policy, arm=arm_ids, previous_joints=previous_joints,
-                                        want_elbow=want_elbow, out=out)
+        return _sweep_batch(self, {"arm": arm_ids}, poses, thetas, n_theta, policy, previous_joints, want_elbow, out)
 
     def nearest_batch(self, arm_ids: Any, poses: Any, seed_joints: Any, n_theta: int = 64, thetas: Any = None, policy: str = "fraction",
                       weights: Optional[Sequence[float]] = None, skip_projected: bool = False, previous_joints: Any = None,
@@ -541,14 +552,8 @@ class DualArmIK:
                       plan_only: bool = False) -> Dict[str, torch.Tensor]:
         """SymbolicIK.nearest_batch for rows of both arms (arm_ids [n] uint8): of K elbow angles per pose, the one whose solution
         is nearest to the row's seed joints, one row per pose (index [n] int32, theta, joints [n,7] ...)."""
-        soa = poses_to_soa(poses, self._solver.device)
-        if thetas is None:
-            thetas = torch.linspace(0.0, 1.0, int(n_theta), dtype=torch.float64)
-        self.r_arm._upload()
-        self.l_arm._upload()
-        return self._solver.solve_nearest(soa, thetas, seed_joints, policy=policy, weights=weights, skip_projected=skip_projected,
-                                          arm=arm_ids, previous_joints=previous_joints, want_elbow=want_elbow, out=out,
-                                          plan_only=plan_only)
+        return _nearest_batch(self, {"arm": arm_ids}, poses, seed_joints, n_theta, thetas, policy, weights, skip_projected,
+                              previous_joints, want_elbow, out, plan_only)
 
     def path_batch(self, arm_ids: Any, poses: Any, start_joints: Any = None, n_theta: int = 16, thetas: Any = None,
                    policy: str = "fraction", weights: Optional[Sequence[float]] = None, skip_projected: bool = False,
@@ -556,21 +561,13 @@ class DualArmIK:
                    plan_only: bool = False) -> Dict[str, torch.Tensor]:
         """SymbolicIK.path_batch for paths of both arms (arm_ids [n] uint8, one byte per path): the least-motion sequence of elbow
         angles along every path (index [T, n] int32, theta, joints [T,n,7], step_cost, cost [n] ...)."""
-        soa = _path_soa(poses, self._solver.device)
-        if thetas is None:
-            thetas = torch.linspace(0.0, 1.0, int(n_theta), dtype=torch.float64) if int(n_theta) > 1 else torch.tensor([0.5], dtype=torch.float64)
-        self.r_arm._upload()
-        self.l_arm._upload()
-        return self._solver.solve_path(soa, thetas, start_joints, policy=policy, weights=weights, skip_projected=skip_projected,
-                                       unwind=unwind, arm=arm_ids, want_elbow=want_elbow, out=out, plan_only=plan_only)
+        return _path_batch(self, {"arm": arm_ids}, poses, start_joints, n_theta, thetas, policy, weights, skip_projected, unwind,
+                           want_elbow, out, plan_only)
 
     def theta_from_joints_batch(self, arm_ids: Any, poses: Any, current_joints: Any, preferred_theta: Optional[Sequence[float]] = None,
                                 out: Optional[Dict[str, torch.Tensor]] = None, plan_only: bool = False) -> Dict[str, torch.Tensor]:
         """SymbolicIK.theta_from_joints_batch for rows of both arms (arm_ids [n] uint8).  preferred_theta: (r, l), default
         ControlIK's pair."""
-        soa = poses_to_soa(poses, self._solver.device)
         if preferred_theta is None:
             preferred_theta = (default_preferred_theta(0), default_preferred_theta(1))
-        self.r_arm._upload()
-        self.l_arm._upload()
-        return self._solver.theta_from_joints(soa, current_joints, preferred_theta, arm=arm_ids, out=out, plan_only=plan_only)
+        return _theta_from_joints_batch(self, {"arm": arm_ids}, poses, current_joints, preferred_theta, out, plan_only)

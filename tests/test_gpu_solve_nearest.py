@@ -371,7 +371,7 @@ def test_rows_that_are_not_numbers_stay_where_they_are(torch_mod):
 
 # ------------------------------------------------------------------------------------------ 8. arguments
 def test_arguments(torch_mod):
-    """What is refused (with the refusing entry point's name in rsik_last_error, nothing written) — RSIK_OPT_NEAREST_LANES = 3 is
+    """What is refused (with the whole text of rsik_last_error, also where a call has two faults; nothing written) — RSIK_OPT_NEAREST_LANES = 3 is
     refused by rsik_set_option, the entry point that takes it —, a context without an arm, n = 0, and every optional output left
     out in turn."""
     torch = torch_mod
@@ -399,23 +399,26 @@ def test_arguments(torch_mod):
     FR = _abi.THETA_FRACTION
     no_main = {key: v for key, v in outs.items() if key not in ("index", "theta", "joints")}
     calls = {
-        "n_theta 0": lambda: raw_nearest(solver, n, p, 0, FR, th, 0, seed, **outs),
-        "n_theta 4097": lambda: raw_nearest(solver, n, p, 4097, FR, big, 0, seed, **outs),
-        "interval0": lambda: raw_nearest(solver, n, p, k, _abi.THETA_INTERVAL0, th, 0, seed, **outs),
-        "none": lambda: raw_nearest(solver, n, p, k, _abi.THETA_NONE, th, 0, seed, **outs),
-        "theta_in NULL": lambda: raw_nearest(solver, n, p, k, FR, None, 0, seed, **outs),
-        "seed_joints NULL": lambda: raw_nearest(solver, n, p, k, FR, th, 0, None, **outs),
-        "index, theta and joints NULL": lambda: raw_nearest(solver, n, p, k, FR, th, 0, seed, **no_main),
-        "flags 2": lambda: raw_nearest(solver, n, p, k, FR, th, 0, seed, flags=2, **outs),
-        "flags 3": lambda: raw_nearest(solver, n, p, k, FR, th, 0, seed, flags=3, **outs),
-        "flags -1": lambda: raw_nearest(solver, n, p, k, FR, th, 0, seed, flags=-1, **outs),
-        "pose_soa NULL": lambda: raw_nearest(solver, n, None, k, FR, th, 0, seed, **outs),
-        "n -1": lambda: raw_nearest(solver, -1, p, k, FR, th, 0, seed, **outs),
+        "n_theta 0": (lambda: raw_nearest(solver, n, p, 0, FR, th, 0, seed, **outs), "n_theta must be in [1, 4096]"),
+        "n_theta 4097": (lambda: raw_nearest(solver, n, p, 4097, FR, big, 0, seed, **outs), "n_theta must be in [1, 4096]"),
+        "interval0": (lambda: raw_nearest(solver, n, p, k, _abi.THETA_INTERVAL0, th, 0, seed, **outs), "theta_policy must be RSIK_THETA_EXPLICIT or RSIK_THETA_FRACTION"),
+        "none": (lambda: raw_nearest(solver, n, p, k, _abi.THETA_NONE, th, 0, seed, **outs), "theta_policy must be RSIK_THETA_EXPLICIT or RSIK_THETA_FRACTION"),
+        "theta_in NULL": (lambda: raw_nearest(solver, n, p, k, FR, None, 0, seed, **outs), "theta_in is NULL"),
+        "seed_joints NULL": (lambda: raw_nearest(solver, n, p, k, FR, th, 0, None, **outs), "seed_joints is NULL"),
+        "index, theta and joints NULL": (lambda: raw_nearest(solver, n, p, k, FR, th, 0, seed, **no_main), "index, theta and joints are all NULL"),
+        "flags 2": (lambda: raw_nearest(solver, n, p, k, FR, th, 0, seed, flags=2, **outs), "unknown bits in flags"),
+        "flags 3": (lambda: raw_nearest(solver, n, p, k, FR, th, 0, seed, flags=3, **outs), "unknown bits in flags"),
+        "flags -1": (lambda: raw_nearest(solver, n, p, k, FR, th, 0, seed, flags=-1, **outs), "unknown bits in flags"),
+        "pose_soa NULL": (lambda: raw_nearest(solver, n, None, k, FR, th, 0, seed, **outs), "pose_soa is NULL"),
+        "n -1": (lambda: raw_nearest(solver, -1, p, k, FR, th, 0, seed, **outs), "n < 0"),
+        # two faults in one call: the one the entry point tests first is the one it reports
+        "n_theta 0 and interval0": (lambda: raw_nearest(solver, n, p, 0, _abi.THETA_INTERVAL0, th, 0, seed, **outs), "n_theta must be in [1, 4096]"),
+        "theta_in NULL and pose_soa NULL": (lambda: raw_nearest(solver, n, None, k, FR, None, 0, seed, **outs), "pose_soa is NULL"),
     }
-    for name, call in calls.items():
+    for name, (call, text) in calls.items():
         rc = call()
         assert rc == _abi.RSIK_E_INVALID, (name, rc)
-        assert "rsik_solve_nearest" in last_error(solver), (name, last_error(solver))
+        assert last_error(solver) == "rsik_solve_nearest: " + text, (name, last_error(solver))
     for value in (3, 2, 7, 9, 63, 65, 128, -1):
         with pytest.raises(_abi.RsikError) as e:
             solver.set_option(_abi.OPT_NEAREST_LANES, value)
@@ -426,8 +429,9 @@ def test_arguments(torch_mod):
         assert bool((t == (777.0 if t.dtype == f64 else 77)).all()), key
     bare = HipSolver(0)  # no arm uploaded
     assert raw_nearest(bare, n, p, k, FR, th, 0, seed, **outs) == _abi.RSIK_E_NOT_SET
-    assert "rsik_solve_nearest" in last_error(bare)
+    assert last_error(bare) == "rsik_solve_nearest: constants of the requested arm were not uploaded"
     assert raw_nearest(bare, n, p, k, FR, th, 0, seed, arm=T(arm, torch), **outs) == _abi.RSIK_E_NOT_SET
+    assert last_error(bare) == "rsik_solve_nearest: per-pose arm ids need both arms' constants (rsik_set_arm)"
     bare.close()
     # n = 0
     assert raw_nearest(solver, 0, None, k, FR, th, 0, None) == _abi.RSIK_OK
@@ -513,3 +517,16 @@ def test_python_surface(torch_mod):
     raw = to_np(solver.solve_nearest(soa(pos, eul, torch), grid, T(seed, torch), arm=T(arm, torch)))
     assert d["joints"].shape == (n, 7) and d["index"].dtype == np.int32
     same_outputs(d, raw, "DualArmIK.nearest_batch")
+    # what the Python driver refuses before any launch, by its whole text
+    seedT = T(seed, torch)
+    refused = {
+        "policy must be 'fraction' or 'explicit'": lambda: solver.solve_nearest(p, grid, seedT, policy="interval0"),
+        "thetas must have shape [K] or [K, n]": lambda: solver.solve_nearest(p, torch.zeros((k, n, 1), dtype=torch.float64), seedT),
+        "thetas: between 1 and 4096 samples per pose": lambda: solver.solve_nearest(p, torch.zeros(4097, dtype=torch.float64), seedT),
+        f"thetas: expected shape {(k, n)}, got {(k, n + 1)}": lambda: solver.solve_nearest(p, torch.zeros((k, n + 1), dtype=torch.float64), seedT),
+        "weights must have 7 entries": lambda: solver.solve_nearest(p, grid, seedT, weights=(1,) * 6),
+    }
+    for text, call in refused.items():
+        with pytest.raises(ValueError) as e:
+            call()
+        assert str(e.value) == text

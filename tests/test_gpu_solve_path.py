@@ -355,7 +355,7 @@ def raw_path(solver, n, t, p, k, policy, thetas, per_pose, start=None, weights=N
 
 
 def test_arguments(torch_mod):
-    """What is refused (RSIK_E_INVALID, the entry point's name in rsik_last_error, nothing written), n = 0, a workspace of exactly
+    """What is refused (RSIK_E_INVALID, the whole text of rsik_last_error, also where a call has two faults; nothing written), n = 0, a workspace of exactly
     the helper's size with guard bytes behind it, and every output left out in turn."""
     torch = torch_mod
     _abi = abi()
@@ -389,26 +389,29 @@ def test_arguments(torch_mod):
     outs = fresh()
     no_main = {key: v for key, v in outs.items() if key not in ("index", "theta", "joints")}
     calls = {
-        "n_theta 0": lambda: raw_path(solver, n, t, p, 0, FR, th, 0, start, workspace=ws, **outs),
-        "n_theta 65": lambda: raw_path(solver, n, t, p, 65, FR, big, 0, start, workspace=ws, **outs),
-        "interval0": lambda: raw_path(solver, n, t, p, k, _abi.THETA_INTERVAL0, th, 0, start, workspace=ws, **outs),
-        "a negative weight": lambda: raw_path(solver, n, t, p, k, FR, th, 0, start, weights=(1, 1, 1, -0.5, 1, 1, 1), workspace=ws, **outs),
-        "a NaN weight": lambda: raw_path(solver, n, t, p, k, FR, th, 0, start, weights=(1, 1, 1, 1, 1, 1, float("nan")), workspace=ws, **outs),
-        "flags 4": lambda: raw_path(solver, n, t, p, k, FR, th, 0, start, flags=4, workspace=ws, **outs),
-        "flags -1": lambda: raw_path(solver, n, t, p, k, FR, th, 0, start, flags=-1, workspace=ws, **outs),
-        "workspace NULL": lambda: raw_path(solver, n, t, p, k, FR, th, 0, start, workspace=None, workspace_bytes=need, **outs),
-        "workspace one byte short": lambda: raw_path(solver, n, t, p, k, FR, th, 0, start, workspace=ws, workspace_bytes=need - 1, **outs),
-        "index, theta and joints NULL": lambda: raw_path(solver, n, t, p, k, FR, th, 0, start, workspace=ws, **no_main),
-        "n_steps 0": lambda: raw_path(solver, n, 0, p, k, FR, th, 0, start, workspace=ws, **outs),
-        "n_steps 65537": lambda: raw_path(solver, n, 65537, p, k, FR, th, 0, start, workspace=ws, **outs),
-        "theta_in NULL": lambda: raw_path(solver, n, t, p, k, FR, None, 0, start, workspace=ws, **outs),
-        "pose_soa NULL": lambda: raw_path(solver, n, t, None, k, FR, th, 0, start, workspace=ws, **outs),
-        "n -1": lambda: raw_path(solver, -1, t, p, k, FR, th, 0, start, workspace=ws, **outs),
+        "n_theta 0": (lambda: raw_path(solver, n, t, p, 0, FR, th, 0, start, workspace=ws, **outs), "n_theta must be in [1, 64]"),
+        "n_theta 65": (lambda: raw_path(solver, n, t, p, 65, FR, big, 0, start, workspace=ws, **outs), "n_theta must be in [1, 64]"),
+        "interval0": (lambda: raw_path(solver, n, t, p, k, _abi.THETA_INTERVAL0, th, 0, start, workspace=ws, **outs), "theta_policy must be RSIK_THETA_EXPLICIT or RSIK_THETA_FRACTION"),
+        "a negative weight": (lambda: raw_path(solver, n, t, p, k, FR, th, 0, start, weights=(1, 1, 1, -0.5, 1, 1, 1), workspace=ws, **outs), "every weight must be finite and >= 0"),
+        "a NaN weight": (lambda: raw_path(solver, n, t, p, k, FR, th, 0, start, weights=(1, 1, 1, 1, 1, 1, float("nan")), workspace=ws, **outs), "every weight must be finite and >= 0"),
+        "flags 4": (lambda: raw_path(solver, n, t, p, k, FR, th, 0, start, flags=4, workspace=ws, **outs), "unknown bits in flags"),
+        "flags -1": (lambda: raw_path(solver, n, t, p, k, FR, th, 0, start, flags=-1, workspace=ws, **outs), "unknown bits in flags"),
+        "workspace NULL": (lambda: raw_path(solver, n, t, p, k, FR, th, 0, start, workspace=None, workspace_bytes=need, **outs), "workspace is NULL or smaller than rsik_solve_path_workspace_bytes"),
+        "workspace one byte short": (lambda: raw_path(solver, n, t, p, k, FR, th, 0, start, workspace=ws, workspace_bytes=need - 1, **outs), "workspace is NULL or smaller than rsik_solve_path_workspace_bytes"),
+        "index, theta and joints NULL": (lambda: raw_path(solver, n, t, p, k, FR, th, 0, start, workspace=ws, **no_main), "index, theta and joints are all NULL"),
+        "n_steps 0": (lambda: raw_path(solver, n, 0, p, k, FR, th, 0, start, workspace=ws, **outs), "n_steps must be in [1, 65536]"),
+        "n_steps 65537": (lambda: raw_path(solver, n, 65537, p, k, FR, th, 0, start, workspace=ws, **outs), "n_steps must be in [1, 65536]"),
+        "theta_in NULL": (lambda: raw_path(solver, n, t, p, k, FR, None, 0, start, workspace=ws, **outs), "theta_in is NULL"),
+        "pose_soa NULL": (lambda: raw_path(solver, n, t, None, k, FR, th, 0, start, workspace=ws, **outs), "pose_soa is NULL"),
+        "n -1": (lambda: raw_path(solver, -1, t, p, k, FR, th, 0, start, workspace=ws, **outs), "n < 0"),
+        # two faults in one call: the one the entry point tests first is the one it reports
+        "n_theta 0 and interval0": (lambda: raw_path(solver, n, t, p, 0, _abi.THETA_INTERVAL0, th, 0, start, workspace=ws, **outs), "n_theta must be in [1, 64]"),
+        "theta_in NULL and pose_soa NULL": (lambda: raw_path(solver, n, t, None, k, FR, None, 0, start, workspace=ws, **outs), "pose_soa is NULL"),
     }
-    for name, call in calls.items():
+    for name, (call, text) in calls.items():
         rc = call()
         assert rc == _abi.RSIK_E_INVALID, (name, rc)
-        assert "rsik_solve_path" in last_error(solver), (name, last_error(solver))
+        assert last_error(solver) == "rsik_solve_path: " + text, (name, last_error(solver))
     untouched(outs)
     # n = 0 launches nothing
     assert raw_path(solver, 0, t, None, k, FR, th, 0, None) == _abi.RSIK_OK
@@ -488,3 +491,15 @@ def test_python_layers(torch_mod):
     raw = to_np(solver.solve_path(path_soa(pos, eul, torch), grid, T(start, torch), arm=T(arm, torch)))
     assert d["joints"].shape == (t, n, 7) and d["index"].dtype == np.int32
     same_outputs(d, raw, "DualArmIK.path_batch")
+    # what the Python driver refuses before any launch, by its whole text
+    refused = {
+        "policy must be 'fraction' or 'explicit'": lambda: solver.solve_path(p, grid, policy="interval0"),
+        "thetas must have shape [K] or [K, T, n]": lambda: solver.solve_path(p, torch.zeros((k, n), dtype=torch.float64)),
+        "thetas: between 1 and 64 samples per waypoint": lambda: solver.solve_path(p, torch.zeros(65, dtype=torch.float64)),
+        f"thetas: expected shape {(k, t, n)}, got {(k, t, n + 1)}": lambda: solver.solve_path(p, torch.zeros((k, t, n + 1), dtype=torch.float64)),
+        "weights must have 7 entries": lambda: solver.solve_path(p, grid, weights=(1,) * 6),
+    }
+    for text, call in refused.items():
+        with pytest.raises(ValueError) as e:
+            call()
+        assert str(e.value) == text

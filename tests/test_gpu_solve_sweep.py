@@ -312,7 +312,8 @@ def test_rows_that_are_not_numbers_stay_where_they_are(torch_mod):
 
 # ------------------------------------------------------------------------------------------ 6. arguments
 def test_arguments(torch_mod):
-    """What the entry point refuses (with its name in rsik_last_error, nothing written), n = 0, and optional outputs left out."""
+    """What the entry point refuses (with the whole text of rsik_last_error, also where a call has two faults; nothing written),
+    n = 0, and optional outputs left out."""
     torch = torch_mod
     _abi = abi()
     from reachy2_symbolic_ik_amd import HipSolver
@@ -332,26 +333,30 @@ def test_arguments(torch_mod):
     FR = _abi.THETA_FRACTION
     no_joints = {key: v for key, v in outs.items() if key != "joints"}
     calls = {
-        "n_theta 0": lambda: raw_sweep(solver, n, p, 0, FR, th, 0, **outs),
-        "n_theta 4097": lambda: raw_sweep(solver, n, p, 4097, FR, big, 0, **outs),
-        "interval0": lambda: raw_sweep(solver, n, p, k, _abi.THETA_INTERVAL0, th, 0, **outs),
-        "none": lambda: raw_sweep(solver, n, p, k, _abi.THETA_NONE, th, 0, **outs),
-        "theta_in NULL": lambda: raw_sweep(solver, n, p, k, FR, None, 0, **outs),
-        "joints NULL": lambda: raw_sweep(solver, n, p, k, FR, th, 0, **no_joints),
-        "pose_soa NULL": lambda: raw_sweep(solver, n, None, k, FR, th, 0, **outs),
-        "n -1": lambda: raw_sweep(solver, -1, p, k, FR, th, 0, **outs),
+        "n_theta 0": (lambda: raw_sweep(solver, n, p, 0, FR, th, 0, **outs), "n_theta must be in [1, 4096]"),
+        "n_theta 4097": (lambda: raw_sweep(solver, n, p, 4097, FR, big, 0, **outs), "n_theta must be in [1, 4096]"),
+        "interval0": (lambda: raw_sweep(solver, n, p, k, _abi.THETA_INTERVAL0, th, 0, **outs), "theta_policy must be RSIK_THETA_EXPLICIT or RSIK_THETA_FRACTION"),
+        "none": (lambda: raw_sweep(solver, n, p, k, _abi.THETA_NONE, th, 0, **outs), "theta_policy must be RSIK_THETA_EXPLICIT or RSIK_THETA_FRACTION"),
+        "theta_in NULL": (lambda: raw_sweep(solver, n, p, k, FR, None, 0, **outs), "theta_in is NULL"),
+        "joints NULL": (lambda: raw_sweep(solver, n, p, k, FR, th, 0, **no_joints), "joints is NULL"),
+        "pose_soa NULL": (lambda: raw_sweep(solver, n, None, k, FR, th, 0, **outs), "pose_soa is NULL"),
+        "n -1": (lambda: raw_sweep(solver, -1, p, k, FR, th, 0, **outs), "n < 0"),
+        # two faults in one call: the one the entry point tests first is the one it reports
+        "n_theta 0 and interval0": (lambda: raw_sweep(solver, n, p, 0, _abi.THETA_INTERVAL0, th, 0, **outs), "n_theta must be in [1, 4096]"),
+        "theta_in NULL and pose_soa NULL": (lambda: raw_sweep(solver, n, None, k, FR, None, 0, **outs), "pose_soa is NULL"),
     }
-    for name, call in calls.items():
+    for name, (call, text) in calls.items():
         rc = call()
         assert rc == _abi.RSIK_E_INVALID, (name, rc)
-        assert "rsik_solve_sweep" in last_error(solver), (name, last_error(solver))
+        assert last_error(solver) == "rsik_solve_sweep: " + text, (name, last_error(solver))
     torch.cuda.synchronize()
     for key, t in outs.items():
         assert bool((t == (777.0 if t.dtype == f64 else 77)).all()), key
     bare = HipSolver(0)  # no arm uploaded
     assert raw_sweep(bare, n, p, k, FR, th, 0, **outs) == _abi.RSIK_E_NOT_SET
-    assert "rsik_solve_sweep" in last_error(bare)
+    assert last_error(bare) == "rsik_solve_sweep: constants of the requested arm were not uploaded"
     assert raw_sweep(bare, n, p, k, FR, th, 0, arm=T(arm, torch), **outs) == _abi.RSIK_E_NOT_SET
+    assert last_error(bare) == "rsik_solve_sweep: per-pose arm ids need both arms' constants (rsik_set_arm)"
     bare.close()
     # n = 0
     assert raw_sweep(solver, 0, None, k, FR, th, 0) == _abi.RSIK_OK
@@ -413,3 +418,15 @@ def test_python_surface(torch_mod):
     assert d["joints"].shape == (k, n, 7)
     for key in d:
         assert np.array_equal(d[key].view(np.uint8), raw[key].view(np.uint8)), key
+    # what the Python driver refuses before any launch, by its whole text
+    p = soa(pos_r, eul_r, torch)
+    refused = {
+        "policy must be 'fraction' or 'explicit'": lambda: solver.solve_sweep(p, grid, policy="interval0"),
+        "thetas must have shape [K] or [K, n]": lambda: solver.solve_sweep(p, torch.zeros((k, n, 1), dtype=torch.float64)),
+        "thetas: between 1 and 4096 samples per pose": lambda: solver.solve_sweep(p, torch.zeros(4097, dtype=torch.float64)),
+        f"thetas: expected shape {(k, n)}, got {(k, n + 1)}": lambda: solver.solve_sweep(p, torch.zeros((k, n + 1), dtype=torch.float64)),
+    }
+    for text, call in refused.items():
+        with pytest.raises(ValueError) as e:
+            call()
+        assert str(e.value) == text
