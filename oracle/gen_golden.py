@@ -1557,6 +1557,63 @@ def gen_utils(out):
     np.savez_compressed(os.path.join(out, "g18_utils.npz"), **data)
 
 
+# ----------------------------------------------------------------------------------------
+# G21: is_elbow_ok and get_best_discrete_theta (utils.py:334-396, 443-465) on the two non-default geometries, the way G18 records
+# them for the default arm: on the circle real poses leave on the solver, with explicit arguments.  The poses are G9's and G20's
+# first reachable draws, read from the committed sets.  Inputs and recorded results only.
+# ----------------------------------------------------------------------------------------
+G21_NB = (10, 20, 64)
+G21_PREFERRED = (-4 * np.pi / 6, 0.5)
+G21_N_THETA = 64
+
+
+def gen_discrete_theta_geometry(out, n=200):
+    import reachy2_symbolic_ik.utils as U
+
+    golden = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden")
+    rng = np.random.default_rng(21)
+    grid = np.linspace(-np.pi, np.pi, G21_N_THETA, endpoint=False)
+    data = {"theta_grid": grid, "nb": np.array(G21_NB), "preferred": np.array(G21_PREFERRED)}
+    for tag, geometry, fname in (("custom", CUSTOM_GEOMETRY, "g9_custom_geometry.npz"), ("ztip", ZTIP_GEOMETRY, "g20_ztip_geometry.npz")):
+        src = np.load(os.path.join(golden, fname))
+        # the geometry's own singularity plane, and the non-DVT one of the default arm
+        planes = np.array([[geometry["singularity_offset"], geometry["singularity_limit_coeff"]], [-1.01, 1.0]])
+        data[f"{tag}_planes"] = planes
+        for arm in ARMS:
+            pre = f"{tag}_{arm}_"
+            sv = quiet(SymbolicIK, arm=arm, **geometry)
+            side = 1 if arm == "r_arm" else -1
+            pos, eul = src[f"{arm}_reach_pos"][:n], src[f"{arm}_reach_eul"][:n]
+            assert len(pos) == n
+            prev_t = rng.uniform(-np.pi, np.pi, size=n)
+            ok = np.zeros((n, len(planes), G21_N_THETA), dtype=np.uint8)
+            found = np.zeros((n, len(planes), len(G21_NB), len(G21_PREFERRED)), dtype=np.uint8)
+            worked = np.zeros_like(found)
+            theta = np.zeros(found.shape)
+            interval = np.zeros((n, 2))
+            for k, (p_, e_) in enumerate(zip(pos, eul)):
+                reach, itv, fn, st = sv.is_reachable(np.array([p_, e_]))
+                assert reach
+                interval[k] = itv
+                elbows = [sv.get_elbow_position(float(t)) for t in grid]
+                for q, (so, coeff) in enumerate(planes):
+                    ok[k, q] = [U.is_elbow_ok(e, side, float(so), float(coeff), sv.elbow_singularity_position) for e in elbows]
+                    for a, nb in enumerate(G21_NB):
+                        for b, pref in enumerate(G21_PREFERRED):
+                            f, t, text = U.get_best_discrete_theta(float(prev_t[k]), itv, sv.get_elbow_position, nb, pref, arm, float(so),
+                                                                   float(coeff), sv.elbow_singularity_position)
+                            found[k, q, a, b], theta[k, q, a, b] = bool(f), float(t)
+                            worked[k, q, a, b] = "preferred_theta worked!" in text
+            data[pre + "pos"], data[pre + "eul"], data[pre + "previous_theta"], data[pre + "interval"] = pos, eul, prev_t, interval
+            data[pre + "elbow_ok"], data[pre + "found"], data[pre + "worked"], data[pre + "theta"] = ok, found, worked, theta
+            # both outcomes of the predicate and of the search, and the shortcut taken and not, on each plane of each arm
+            for q in range(len(planes)):
+                assert 0.02 < ok[:, q].mean() < 0.98, (pre, q, ok[:, q].mean())
+                assert 0 < worked[:, q].mean() < 1 and found[:, q].any(), (pre, q)
+            assert (found[:, 0] == 0).any(), pre
+    np.savez_compressed(os.path.join(out, "g21_discrete_theta_geometry.npz"), **data)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(os.path.dirname(__file__), "..", "tests", "golden"))
@@ -1583,7 +1640,7 @@ def main():
              ("g7", gen_continuous_start), ("g8", gen_matrix_edges),
              ("g9", gen_custom_geometry), ("g10", gen_custom_urdf_control), ("g11", gen_emergency),
              ("g12", gen_continuous_modes), ("g13", gen_hostile), ("g14", gen_scale), ("g15", gen_stages), ("g16", gen_scale_continuous), ("g17", gen_scale_variants),
-             ("g18", gen_utils), ("g20", gen_ztip_geometry)]
+             ("g18", gen_utils), ("g20", gen_ztip_geometry), ("g21", gen_discrete_theta_geometry)]
     bad = 0
     for name, fn in steps:
         if args.only and name not in args.only.split(","):  # exact names: "g1" does not select "g12"

@@ -1,5 +1,7 @@
 """Arm pairs for the launches that read an arm byte per row (tests/test_arm_pairs_checker.py pins their inputs on the checker alone,
-tests/test_gpu_arm_forms.py launches them on the GPU).  No test in this file.
+tests/test_gpu_arm_forms.py launches them on the GPU).  No test in this file.  The control launches (rsik_control_discrete(_rows),
+rsik_control_continuous_step / _run) and rsik_theta_from_joints have pairs of their own further down: CONTROL_PAIRS and threshold_family()
+(tests/test_control_pairs_checker.py on the checker alone, tests/test_gpu_control_arm_pairs.py on the GPU).
 
 rsik_solve / rsik_solve_rows, rsik_solve_sweep, rsik_solve_nearest and rsik_solve_path pick their kernel with launch_form() and
 tip_on_z() (csrc/rsik_lib.hip): FORM 0 one arm for the launch; FORM 2 an arm byte per row and every constant without a handedness
@@ -38,10 +40,19 @@ NON_MIRROR = tuple(pair for pair, (form, _, _) in PAIRS.items() if form == 1)
 ARM_NAMES = ("r_arm", "l_arm")
 
 
+def geometry_of(name):
+    """The geometry of a slot name: a key of GEOMETRY, or "<key>@<offset>" for that geometry with another singularity_offset, the
+    offset a number ("default@-1.01") or a label of threshold_offsets() ("default@s*-1e-3")."""
+    base, at, so = name.partition("@")
+    if not at:
+        return GEOMETRY[base]
+    return dict(GEOMETRY[base], singularity_offset=threshold_offsets()[so] if so in THRESHOLD_LABELS else float(so))
+
+
 def checker_arms(pair):
     """The checker's two arms of a pair: (orc.Arm of the r slot, orc.Arm of the l slot)."""
     r, l = pair.split("/")
-    return orc.Arm("r_arm", **GEOMETRY[r]), orc.Arm("l_arm", **GEOMETRY[l])
+    return orc.Arm("r_arm", **geometry_of(r)), orc.Arm("l_arm", **geometry_of(l))
 
 
 def is_sided(i):
@@ -68,7 +79,7 @@ def packed_blocks(pair):
 
     out = []
     for arm, name in zip(ARM_NAMES, pair.split("/")):
-        kw = dict(GEOMETRY[name])
+        kw = dict(geometry_of(name))
         out.append(ArmGeometry(arm, kw.pop("ik_parameters", None) or default_ik_parameters(), **kw).pack())
     return out
 
@@ -92,7 +103,7 @@ def check_blocks(pair, blocks):
     assert launch_of(blocks, no_tipz=1) == (form, False), pair
 
 
-def upload(pair):
+def upload(pair, check=check_blocks):
     """A fresh HipSolver with the pair's two geometries uploaded, each slot from a SymbolicIK(arm, solver=..., **geometry)._upload();
     the uploaded blocks are checked against the pair's name before the solver is handed out."""
     from reachy2_symbolic_ik_amd import HipSolver, SymbolicIK
@@ -100,9 +111,9 @@ def upload(pair):
     solver = HipSolver(0)
     with contextlib.redirect_stdout(io.StringIO()):
         for arm, name in zip(ARM_NAMES, pair.split("/")):
-            SymbolicIK(arm, solver=solver, **GEOMETRY[name])._upload()
+            SymbolicIK(arm, solver=solver, **geometry_of(name))._upload()
     blocks = list(solver._arm_blocks)
-    check_blocks(pair, blocks)
+    check(pair, blocks)
     for got, want in zip(blocks, packed_blocks(pair)):
         assert got.tobytes() == want.tobytes(), f"{pair}: the uploaded block is not the geometry's"
     return solver
@@ -111,3 +122,105 @@ def upload(pair):
 def solve_fractions(k, n):
     """One fraction of the interval per row for rsik_solve(RSIK_THETA_FRACTION): uniform in [0, 1]."""
     return np.random.default_rng(650 + k).uniform(0.0, 1.0, size=n)
+
+
+# ------------------------------------------------------------------------------------------ the control launches
+# rsik_control_discrete(_rows), rsik_control_continuous_step / _run and rsik_theta_from_joints on arm pairs (tests/test_control_pairs_checker.py
+# pins their inputs on the checker alone, tests/test_gpu_control_arm_pairs.py launches them).  The control kernels compile the singularity-plane
+# half of is_elbow_ok out of a launch (PLANE = false) when singularity_plane_binds (csrc/rsik_lib.hip) says it cannot fail on either arm;
+# rsik_theta_from_joints picks its kernel with launch_form().  pair -> (FORM of rsik_theta_from_joints, PLANE of the control kernels):
+CONTROL_PAIRS = {
+    "default/custom": (1, True),              # both planes bind, non-mirror, the l tip off the z axis
+    "ztip/default": (1, True),                # both planes bind, non-mirror, both tips on z
+    "custom/custom": (2, True),               # mirror, non-default: slope 0.8, offset 0.05, other shoulder offsets, tip with x / y
+    "default@-1.01/ztip@-1.01": (1, False),   # non-mirror, no plane on either arm
+    "default@-1.01/default@0.03": (1, True),  # the same arm but for the plane: PLANE = true although r never binds
+}
+
+
+def plane_margin(block):
+    """rhs - reach_max of singularity_plane_binds (csrc/rsik_lib.hip) for one constant block: the plane half of is_elbow_ok cannot
+    fail on this arm when this exceeds 1e-6."""
+    from reachy2_symbolic_ik_amd import constants as K
+
+    c = np.asarray(block, dtype=np.float64)
+    sc = c[K.C_SING_COEFF]
+    rhs = c[K.C_ES + 2] - c[K.C_SING_OFFSET] - sc * c[K.C_ES]
+    reach_max = c[K.C_SHOULDER + 2] - sc * c[K.C_SHOULDER] + c[K.C_UPPER_ARM] * np.sqrt(1.0 + sc * sc)
+    return float(rhs - reach_max)
+
+
+def plane_binds(blocks):
+    """singularity_plane_binds restated: PLANE of a control launch on these two constant blocks."""
+    return any(not (plane_margin(b) > 1e-6) for b in blocks)
+
+
+def threshold_offset():
+    """s*: the singularity_offset of the default mirror pair at which rhs == reach_max in singularity_plane_binds, from the packed
+    blocks (the smaller of the two slots' values: they agree to rounding).  About -0.3705."""
+    from reachy2_symbolic_ik_amd import constants as K
+
+    return float(min(b[K.C_SING_OFFSET] + plane_margin(b) for b in packed_blocks("default/default")))
+
+
+S3 = -0.30
+THRESHOLD_LABELS = ("s*-1e-3", "s*+1e-3", "s3")
+
+
+def threshold_offsets():
+    """The offsets behind THRESHOLD_LABELS: s* - 1e-3, s* + 1e-3 and S3, s* resolved from the packed blocks when asked for."""
+    s = threshold_offset()
+    return dict(zip(THRESHOLD_LABELS, (s - 1e-3, s + 1e-3, S3)))
+
+
+def threshold_family():
+    """The default mirror pair at the three offsets of THRESHOLD_LABELS, pair name -> (FORM, PLANE): s* - 1e-3 must come out
+    PLANE = false, s* + 1e-3 PLANE = true, and s3 = S3 = -0.30 PLANE = true.  s3 was chosen on the checker alone so that the plane half
+    of is_elbow_ok fails on between 1 % and 10 % of the grid points the discrete search evaluates on control_workload's 1000 rows
+    (nb_search_points 64, preferred angle -4 pi / 6).  Measured share: 0.0418 (r rows 0.0462, l rows 0.0375);
+    tests/test_control_pairs_checker.py::test_threshold_family measures it again and asserts it."""
+    return {f"default@{label}/default@{label}": (2, plane) for label, plane in zip(THRESHOLD_LABELS, (False, True, True))}
+
+
+def control_expectation(pair):
+    return CONTROL_PAIRS[pair] if pair in CONTROL_PAIRS else threshold_family()[pair]
+
+
+def upload_control(pair):
+    """upload() for a pair of CONTROL_PAIRS or threshold_family(): the uploaded blocks are checked with check_control_blocks, and with
+    check_blocks too where the pair is also one of PAIRS."""
+    def check(pair, blocks):
+        check_control_blocks(pair, blocks)
+        if pair in PAIRS:
+            check_blocks(pair, blocks)
+
+    return upload(pair, check=check)
+
+
+def check_control_blocks(pair, blocks):
+    """A control pair is what its name says, on the constant blocks themselves: FORM, PLANE, and what the slots differ in."""
+    from reachy2_symbolic_ik_amd import constants as K
+
+    form, plane = control_expectation(pair)
+    r, l = blocks
+    assert r is not None and l is not None and r.shape == l.shape == (K.ARM_CONSTS_COUNT,), pair
+    assert r[K.C_SIDE] == 1.0 and l[K.C_SIDE] == -1.0, pair
+    assert launch_of(blocks)[0] == form and launch_of(blocks, no_mirror=1)[0] == 1, pair
+    assert plane_binds(blocks) == plane, (pair, [plane_margin(b) for b in blocks])
+    differ = {i for i in range(K.ARM_CONSTS_COUNT) if not is_sided(i) and r[i:i + 1].tobytes() != l[i:i + 1].tobytes()}
+    if pair == "default@-1.01/default@0.03":
+        # the same arm but for the plane: the offset, and the two constants without a handedness that are derived from it
+        assert {K.C_SING_OFFSET, K.C_PLANE_K} <= differ <= {K.C_SING_OFFSET, K.C_PLANE_K, K.C_PROJ_RADIUS}, (pair, sorted(differ))
+        assert plane_margin(r) > 0.5 and plane_margin(l) < -0.3, pair  # r never binds, l does
+    elif pair == "default@-1.01/ztip@-1.01":
+        assert min(plane_margin(b) for b in blocks) > 0.5 and r[K.C_UPPER_ARM] != l[K.C_UPPER_ARM], pair
+    elif form == 1:
+        assert abs(r[K.C_UPPER_ARM] - l[K.C_UPPER_ARM]) > 0.01 and r[K.C_ELBOW_LIMIT] != l[K.C_ELBOW_LIMIT], pair
+        assert r[K.C_SING_COEFF] != l[K.C_SING_COEFF] and r[K.C_SING_OFFSET] != l[K.C_SING_OFFSET], pair
+    else:
+        assert not differ, (pair, sorted(differ))
+    if pair in threshold_family():
+        so = geometry_of(pair.split("/")[0])["singularity_offset"]
+        assert r[K.C_SING_OFFSET] == l[K.C_SING_OFFSET] == so and r[K.C_UPPER_ARM] == 0.28, (pair, so)
+    if pair == "custom/custom":
+        assert r[K.C_SING_COEFF] == 0.8 and r[K.C_SING_OFFSET] == 0.05 and r[K.C_TIPL] != 0.0 and r[K.C_SHOULDER] != 0.0, pair

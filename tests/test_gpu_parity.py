@@ -13,6 +13,8 @@ pytestmark = pytest.mark.gpu
 
 TOL = 1e-9          # asserted (north-star bar: 1e-6 rad)
 NORTH_STAR_TOL = 1e-6
+CONT_JOINT_TOL = 1e-7   # continuous control step by step: joints
+CONT_THETA_TOL = 1e-9   # continuous control step by step: the carried theta
 URDF = "config_files/reachy2_ik_minimal.urdf"
 
 
@@ -713,25 +715,14 @@ def test_control_continuous_scalar_api(golden_dir, torch_mod, monkeypatch):
 def test_control_continuous_against_checker_dvt_and_emergency(torch_mod, orc):
     """Random jumpy goal sequences (DVT singularity offset, so the elbow projection and the emergency stop both fire),
     step by step against the CPU checker's state machine."""
+    from control_workload import jumpy_goals
+
     c = make_control(is_dvt=True)
     rng = np.random.default_rng(77)
     ntraj, nsteps = 96, 25
     for ai, arm in enumerate(("r_arm", "l_arm")):
         a = orc.Arm(arm, 0.03)
-        y = -0.2 if arm == "r_arm" else 0.2
-        base = np.array([0.35, y, -0.25])
-        from scipy.spatial.transform import Rotation as R
-        Ms = np.zeros((ntraj, nsteps, 4, 4))
-        for k in range(ntraj):
-            p = base + rng.uniform(-0.15, 0.15, 3)
-            e = np.array([0.0, -np.pi / 2, 0.0]) + rng.uniform(-0.5, 0.5, 3)
-            for i in range(nsteps):
-                jump = 0.2 if (k % 4 == 0 and i == 12) else 0.004   # a few trajectories jump -> continuity emergency stop
-                p = p + rng.uniform(-jump, jump, 3)
-                e = e + rng.uniform(-jump, jump, 3)
-                Ms[k, i] = np.eye(4)
-                Ms[k, i, :3, :3] = R.from_euler("xyz", e).as_matrix()
-                Ms[k, i, :3, 3] = p
+        Ms = jumpy_goals(rng, arm, ntraj, nsteps)   # a few trajectories jump -> continuity emergency stop
         st = c.new_continuous_state(arm, ntraj)
         states = [orc.ContinuousState(c.previous_theta[arm], c.previous_sol[arm]) for _ in range(ntraj)]
         start_j = rng.uniform(-0.6, 0.6, size=(ntraj, 7))   # generic start: no tie in the start-up search
@@ -749,7 +740,7 @@ def test_control_continuous_against_checker_dvt_and_emergency(torch_mod, orc):
                                                           current_joints=(start_j[k] if i == 0 else cs.previous_sol),
                                                           current_pose=prev[k])
                 assert ok == bool(res["reachable"][k]) and code == res["state"][k], (arm, k, i)
-                assert np.max(np.abs(j - res["joints"][k])) < 1e-7, (arm, k, i)
+                assert np.max(np.abs(j - res["joints"][k])) < CONT_JOINT_TOL, (arm, k, i)
             prev = Ms[:, i]
         n_em = int(st[9].sum().item())
         assert n_em == sum(s.emergency_stop for s in states) and n_em > 0
@@ -797,8 +788,8 @@ def test_control_continuous_every_mode_step_kernel(golden_dir, torch_mod, is_dvt
                 tag = (arm, dvt, mode, dth, pref, i)
                 np.testing.assert_array_equal(res["reachable"], F[:, i], err_msg=str(tag))
                 np.testing.assert_array_equal(res["state"], S[:, i], err_msg=str(tag))
-                assert np.max(np.abs(st[0].cpu().numpy() - TH[:, i])) < 1e-9, tag
-                assert np.max(np.abs(res["joints"] - J[:, i])) < 1e-7, tag
+                assert np.max(np.abs(st[0].cpu().numpy() - TH[:, i])) < CONT_THETA_TOL, tag
+                assert np.max(np.abs(res["joints"] - J[:, i])) < CONT_JOINT_TOL, tag
                 np.testing.assert_array_equal(st[9].cpu().numpy() != 0.0, ES[:, i].astype(bool), err_msg=str(tag))
 
 

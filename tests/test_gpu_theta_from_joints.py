@@ -39,8 +39,9 @@ def kind_workload(kind, n, seed=W.SEED, so=0.03):
     return W.theta_workload(seed + KINDS.index(kind), n, arm={"r": 0, "l": 1, "mixed": None}[kind], so=so)
 
 
-def check_against_checker(got, ref, so, pos, eul, arm, cur, what, pref=W.PREFERRED):
-    """theta / bracket / joints / distance / state of a fused launch against checker_batch's answer; returns the near ties."""
+def check_against_checker(got, ref, so, pos, eul, arm, cur, what, pref=W.PREFERRED, arms=None):
+    """theta / bracket / joints / distance / state of a fused launch against checker_batch's answer; returns the near ties.
+    arms: the checker's (r, l) arms of the launch, the default arms with offset `so` where None."""
     n = len(pos)
     assert ref["ok"].all()
     np.testing.assert_array_equal(got["state"], np.zeros(n, dtype=np.uint8), err_msg=what)
@@ -48,7 +49,7 @@ def check_against_checker(got, ref, so, pos, eul, arm, cur, what, pref=W.PREFERR
     print(f"{what}: theta max diff {np.nanmax(dth):.3e}, rows beyond 1e-12: {int((dth > EXACT).sum())} of {n}")
     odd = np.flatnonzero(~(dth <= EXACT))
     assert len(odd) <= n // 10000, (what, len(odd))
-    arms = (orc_mod().Arm("r_arm", so), orc_mod().Arm("l_arm", so))
+    arms = arms or (orc_mod().Arm("r_arm", so), orc_mod().Arm("l_arm", so))
     for i in odd:  # a mismatch that is not a near tie fails
         p = pref[int(arm[i])]
         base = W.replay_row(arms, pos[i], eul[i], arm[i], cur[i], p)

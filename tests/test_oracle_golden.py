@@ -719,7 +719,7 @@ def test_scale_variants_checker_against_reference(golden_dir):
 def test_golden_fixtures_reproduce_from_the_reference():
     """`oracle/gen_golden.py --check`: the committed fixtures are what the reference, imported from /root/reference, produces today —
     regenerated into a temporary directory and compared array by array, byte for byte.  Here G1 (the catalogue: SymbolicIK and
-    ControlIK discrete), G6 (ControlIK continuous trajectories), G15 (the stage methods), G18 and G20 (the tip-on-z geometry); `--check` without `--only` does
+    ControlIK discrete), G6 (ControlIK continuous trajectories), G15 (the stage methods), G18, G20 (the tip-on-z geometry) and G21 (the theta search on the non-default geometries); `--check` without `--only` does
     every set (~15 min: G14, the BASELINE-scale digests, takes 5 of them on 7 cores, G16 1.5, G17 2.5).
     Skipped where the reference is not mounted (the GPU box: it never travels)."""
     import subprocess
@@ -729,13 +729,14 @@ def test_golden_fixtures_reproduce_from_the_reference():
         pytest.skip("/root/reference is not mounted here")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1")
-    p = subprocess.run([sys.executable, os.path.join(root, "oracle", "gen_golden.py"), "--check", "--only", "g1,g6,g15,g18,g20"],
+    p = subprocess.run([sys.executable, os.path.join(root, "oracle", "gen_golden.py"), "--check", "--only", "g1,g6,g15,g18,g20,g21"],
                        capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
     assert "CHECK g1_catalogue.npz: identical" in p.stdout and "CHECK g6_control_continuous.npz: identical" in p.stdout
     assert "CHECK g15_stages.npz: identical" in p.stdout
     assert "CHECK g18_utils.npz: identical" in p.stdout
     assert "CHECK g20_ztip_geometry.npz: identical" in p.stdout
+    assert "CHECK g21_discrete_theta_geometry.npz: identical" in p.stdout
 
 
 def test_utils_helpers_on_explicit_arguments(golden_dir):
@@ -790,3 +791,44 @@ def test_utils_helpers_on_explicit_arguments(golden_dir):
             n = L.orc_intersection_circle_line(D(row[0:3]), float(row[12]), D(g["np_v"][k]), D(g["np_q"][k]), D(pts))
             assert n == int(g["np_cl_count"][k])
             assert np.max(np.abs(pts[: 3 * n] - g["np_cl_points"][k][: 3 * n]), initial=0.0) < 1e-9
+
+
+def test_discrete_theta_on_non_default_geometries(golden_dir):
+    """G21: the reference's utils.is_elbow_ok at 64 theta per pose and utils.get_best_discrete_theta with 10, 20 and 64 search points,
+    preferred angles -4 pi / 6 and 0.5, on 200 reachable poses of each arm of CUSTOM (G9) and ZTIP (G20), with the geometry's own
+    singularity plane and with offset -1.01 / slope 1.0, against orc.Solver.best_discrete_theta and the checker's elbow predicate on
+    the checker's own is_reachable and get_elbow_position: flags exact, theta to 1e-12 (G18's bar).  The two-arm GPU tests of the
+    control kernels (tests/test_gpu_control_arm_pairs.py) take the checker's theta search on these geometries as their reference."""
+    import ctypes as C
+
+    from arm_pairs import CUSTOM, ZTIP
+
+    g = load(golden_dir, "g21_discrete_theta_geometry.npz")
+    L = orc.lib()
+    D = lambda a: np.ascontiguousarray(a, dtype=np.float64).ctypes.data_as(C.POINTER(C.c_double))  # noqa: E731
+    grid, nbs, prefs = g["theta_grid"], g["nb"], g["preferred"]
+    assert len(grid) == 64 and list(nbs) == [10, 20, 64] and list(prefs) == [-4 * np.pi / 6, 0.5]
+    for tag, geometry in (("custom", CUSTOM), ("ztip", ZTIP)):
+        planes = g[f"{tag}_planes"]
+        assert planes[0].tolist() == [geometry["singularity_offset"], geometry["singularity_limit_coeff"]] and planes[1].tolist() == [-1.01, 1.0]
+        for arm in ("r_arm", "l_arm"):
+            pre = f"{tag}_{arm}_"
+            arms = [orc.Arm(arm, **dict(geometry, singularity_offset=so, singularity_limit_coeff=c)) for so, c in planes]
+            side, esp = arms[0].field("side"), arms[0].field("elbow_singularity_position")
+            n = len(g[pre + "pos"])
+            assert n == 200 and g[pre + "elbow_ok"].shape == (n, 2, 64) and g[pre + "theta"].shape == (n, 2, 3, 2)
+            for k in range(n):
+                for q, (so, c) in enumerate(planes):
+                    sv = orc.Solver(arms[q])
+                    ok, itv, st = sv.is_reachable(g[pre + "pos"][k], g[pre + "eul"][k])
+                    assert ok and np.max(np.abs(itv - g[pre + "interval"][k])) < TOL, (pre, k)
+                    flags = [bool(L.orc_is_elbow_ok_args(D(sv.get_elbow_position(t)), side, float(so), float(c), D(esp))) for t in grid]
+                    np.testing.assert_array_equal(flags, g[pre + "elbow_ok"][k, q] != 0, err_msg=f"{pre}{k} plane {q}")
+                    for a, nb in enumerate(nbs):
+                        for b, pref in enumerate(prefs):
+                            found, theta = sv.best_discrete_theta(g[pre + "interval"][k], int(nb), float(pref), float(g[pre + "previous_theta"][k]))
+                            assert found == bool(g[pre + "found"][k, q, a, b]), (pre, k, q, nb, pref)
+                            assert abs(theta - g[pre + "theta"][k, q, a, b]) < 1e-12, (pre, k, q, nb, pref, theta)
+                            if g[pre + "worked"][k, q, a, b]:
+                                assert theta == pref
+            assert 0 < g[pre + "worked"].mean() < 1 and 0 < g[pre + "found"][:, 0].mean() < 1

@@ -35,11 +35,12 @@ def distance(joints, cur):
     return float(np.sqrt(np.sum(d * d)))
 
 
-def theta_workload(seed, n, arm=None, so=0.03, shortcut_every=16, far_every=8):
+def theta_workload(seed, n, arm=None, so=0.03, shortcut_every=16, far_every=8, arms=None):
     """pos [n,3], eul [n,3], arm [n] uint8, cur [n,7]: start poses an arm can be in (a box in front of the row's own shoulder,
     hand pointing forward within +-0.7 rad, as G7's), the joints it measured uniform in +-0.6 as G7 draws them, every
     `far_every`-th row up to +-5 pi (angle_diff's wrap), and every `shortcut_every`-th row within 1e-3 of the solution at the
-    arm's preferred theta (the shortcut of utils.py:296-300), half of those moved by whole turns."""
+    arm's preferred theta (the shortcut of utils.py:296-300), half of those moved by whole turns.  arms: the checker's (r, l) arms the
+    shortcut rows are built on, the default arms with offset `so` where None."""
     rng = np.random.default_rng(seed)
     byte = (rng.uniform(size=n) < 0.5).astype(np.uint8)
     if arm is not None:
@@ -55,7 +56,7 @@ def theta_workload(seed, n, arm=None, so=0.03, shortcut_every=16, far_every=8):
     short = np.flatnonzero(np.arange(n) % shortcut_every == 5)
     noise = rng.uniform(-1e-3, 1e-3, size=(len(short), 7))
     turns = rng.integers(-2, 3, size=(len(short), 7)) * (rng.uniform(size=(len(short), 1)) < 0.5)
-    arms = (orc.Arm("r_arm", so), orc.Arm("l_arm", so))
+    arms = arms or (orc.Arm("r_arm", so), orc.Arm("l_arm", so))
     for k, i in enumerate(short):
         sv = orc.Solver(arms[byte[i]])
         if sv.is_reachable_no_limits(pos[i], eul[i]):
@@ -109,17 +110,18 @@ def near_ties(arms, pos, eul, arm, cur, pref=PREFERRED, rows=None):
     return found
 
 
-def checker_batch(so, pos, eul, arm, cur, pref=PREFERRED):
+def checker_batch(so, pos, eul, arm, cur, pref=PREFERRED, arms=None):
     """The checker's answer row by row (orc_get_best_theta_to_current_joints on one solver object per row, threads over
     chunks): ok [n] (is_reachable_no_limits), theta [n], shortcut [n], moved [n] (a projection moved the solver state during
     the search), joints [n,7] and distance [n] of the last evaluation for the rows that did not move (get_joints at the
-    returned theta is then the same computation again), solver [n,19] (the object after the search)."""
+    returned theta is then the same computation again), solver [n,19] (the object after the search).  arms: the checker's (r, l)
+    arms, the default arms with offset `so` where None."""
     n = len(pos)
     out = dict(ok=np.zeros(n, dtype=bool), theta=np.full(n, np.nan), shortcut=np.zeros(n, dtype=bool), moved=np.zeros(n, dtype=bool),
                joints=np.full((n, 7), np.nan), distance=np.full(n, np.nan), solver=np.zeros((n, 19)))
 
-    def work(lo, hi):
-        arms = (orc.Arm("r_arm", so), orc.Arm("l_arm", so))
+    def work(lo, hi, arms=arms):
+        arms = arms or (orc.Arm("r_arm", so), orc.Arm("l_arm", so))
         sv = [orc.Solver(a) for a in arms]
         for i in range(lo, hi):
             s = sv[int(arm[i])]
