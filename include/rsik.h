@@ -86,7 +86,23 @@ extern "C" {
  *  anything else that is not a number — theta_in, previous_joints, current_joints, current_pose, a row of cont_state or of a
  *  solver state: IEEE arithmetic as the reference would do it: the outputs of THAT row which depend on the value are NaN or
  *  what comparisons that are all false select (a NaN never trips an emergency stop, a NaN previous_theta stays NaN); the state
- *  code is one of the codes above.  A poisoned cont_state row stays poisoned until the caller re-initialises it (timed_out). */
+ *  code is one of the codes above.  A poisoned cont_state row stays poisoned until the caller re-initialises it (timed_out).
+ *
+ * Rows that ARE numbers, of any size.  Every finite double is a value, as in the reference (whose libm reduces any angle by pi
+ * exactly): the Euler angles of a pose goal, theta_in and the theta grids (RSIK_THETA_EXPLICIT and a fraction that leaves
+ * [0, 1]), the theta of rsik_joints_from_state / rsik_elbow_from_state, the preferred_theta of rsik_theta_from_joints and of
+ * rsik_control_discrete(_rows), and previous joints read at an exact singularity may be wound up to DBL_MAX: an angle of
+ * magnitude >= 2^27 is first reduced to the angle of [-pi, pi] it is congruent to (a rare, wave-skipped branch; a few 1e-16
+ * rad), and the row is answered like its reduced twin — flags, states and the projected bit exactly, numbers to 1e-9.  Outputs
+ * that echo an angle (theta of the sampling entry points, the shoulder pitch kept at a singularity, theta == preferred_theta)
+ * return it as it came.  A position may be anything up to DBL_MAX and down to the smallest denormal: where the squared distance
+ * from the shoulder overflows (beyond 1.34e154) the reference's norm is infinite, its direction zero and the projected goal the
+ * shoulder itself, and so it is here ("Backward pose" on the default arms).  tests/test_gpu_far_inputs.py, G22.
+ * The CONTINUOUS entry points refuse a finite preferred_theta / preferred_theta_self of magnitude >= 2^27 with RSIK_E_INVALID,
+ * before anything is launched or written: their serial phases wrap angles with a modulo written for bounded values, and a
+ * wrong start theta would be carried from step to step.  Below the bound they answer as the reference does.  Not covered:
+ * a caller-written previous_theta in a cont_state row (the library itself keeps it inside the control interval; it is
+ * assumed below 2^27 in magnitude), and huge or scaled rotation entries of a goal matrix (the nearest-rotation path). */
 
 /* ---- why an emergency stop tripped: one bit per message the reference appends to ControlIK.emergency_state
  * (utils.multiturn_safety_check utils.py:544-566, utils.continuity_check utils.py:584-586) ---- */
@@ -191,7 +207,8 @@ int rsik_set_arm(rsik_ctx *ctx, int arm, const double *consts_host, int count);
 /* Kernel-variant selectors.  Every value gives the same results (to rounding where a comment says so); the defaults
  * (0) let the library choose.  They exist so that tests can force each variant in turn and A/B timings can pin one.
  *   RSIK_OPT_SWEEP_MODE     rsik_control_discrete's grid search (utils.py:366-396): 0 = chosen per wave, 1 = always the
- *                           exhaustive wave-cooperative sweep, 2 = always the per-lane search
+ *                           exhaustive wave-cooperative sweep, 2 = always the per-lane search (a launch whose preferred_theta is
+ *                           2^27 or more in magnitude takes 1 whatever is set here: "Rows that are numbers, of any size")
  *   RSIK_OPT_NO_TIPZ        non-zero: never use the goal stage specialised for tip_x = tip_y = 0
  *   RSIK_OPT_NO_MIRROR      non-zero: mixed r/l launches read every constant per lane (no mirror-image shortcut)
  *   RSIK_OPT_CONT_RUN_MODE  rsik_control_continuous_run: 0 = chosen by the library, 1 = the phased trajectory pipeline

@@ -1614,6 +1614,101 @@ def gen_discrete_theta_geometry(out, n=200):
     np.savez_compressed(os.path.join(out, "g21_discrete_theta_geometry.npz"), **data)
 
 
+# ----------------------------------------------------------------------------------------
+# G22: finite goals far outside the usual ranges (tests/far_inputs.py): Euler angles wound up to DBL_MAX, positions up to DBL_MAX
+# and down to the smallest denormal.  The inputs are rebuilt from tests/far_inputs.py by whoever reads the set (a digest of
+# them is recorded); recorded are the reference's answers, and the exception's kind where it raises.
+# ----------------------------------------------------------------------------------------
+G22_THETAS = (0.3, -2.0)
+G22_THETA_EVERY = 4
+
+
+def gen_far_inputs(out):
+    import hashlib
+    import warnings
+
+    import far_inputs as F
+
+    def digest(*arrays):
+        h = hashlib.sha256()
+        for a in arrays:
+            h.update(np.ascontiguousarray(a).tobytes())
+        return np.frombuffer(h.digest(), dtype=np.uint8).copy()
+
+    solvers = {arm: make_solver(arm, F.SINGULARITY_OFFSET) for arm in ARMS}
+
+    def pose_rows(pos, eul, arm, thetas_every):
+        n = len(pos)
+        res = {"outcome": np.zeros(n, dtype=np.uint8), "reachable": np.zeros(n, dtype=np.uint8), "state": np.full(n, 255, dtype=np.uint8),
+               "interval": np.full((n, 2), NAN), "joints": np.full((n, 7), NAN), "elbow": np.full((n, 3), NAN),
+               "elbow_len": np.zeros(n, dtype=np.uint8)}
+        sub = np.arange(0, n, thetas_every)
+        tj = np.full((len(sub), len(G22_THETAS), 7), NAN)
+        te = np.full((len(sub), len(G22_THETAS), 3), NAN)
+        for i in range(n):
+            sv = solvers[ARMS[arm[i]]]
+            oc, ret = _outcome(lambda i=i, sv=sv: solve_symbolic(sv, pos[i], eul[i]))
+            res["outcome"][i] = oc
+            if ret is None:
+                continue
+            for k in ("reachable", "state", "interval", "joints", "elbow", "elbow_len"):
+                res[k][i] = ret[k]
+            if i % thetas_every == 0 and ret["reachable"]:
+                for q, th in enumerate(G22_THETAS):
+                    r2 = solve_symbolic(sv, pos[i], eul[i], theta=th)
+                    tj[i // thetas_every, q], te[i // thetas_every, q] = r2["joints"], r2["elbow"]
+        res["theta_joints"], res["theta_elbow"] = tj, te
+        return res
+
+    data = {"thetas": np.array(G22_THETAS), "theta_every": np.array(G22_THETA_EVERY)}
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")  # (overflow in the squared distance: the behaviour on record)
+        w = F.wound_rows()
+        data["wound_digest"] = digest(w["pos"], w["eul"], w["twin_eul"], w["arm"])
+        for k, v in pose_rows(w["pos"], w["eul"], w["arm"], G22_THETA_EVERY).items():
+            data["wound_" + k] = v
+        assert (data["wound_outcome"] == OUTCOME_RETURNED).all()
+        ctrl = quiet(ControlIK, urdf_path="../config_files/reachy2.urdf")
+        for tag, rows in (("far", F.far_position_rows()), ("tiny", F.tiny_position_rows())):
+            pos, eul, arm, val, entry = rows
+            data[f"{tag}_digest"] = digest(pos, eul, arm)
+            for k, v in pose_rows(pos, eul, arm, 1 if tag == "tiny" else 10 ** 9).items():
+                if tag == "tiny" or not k.startswith("theta_"):
+                    data[f"{tag}_{k}"] = v
+            # the same positions as the translation column of proper goal matrices, through ControlIK discrete
+            Ms = F.goal_matrices(pos, eul)
+            n = len(Ms)
+            J, OC = np.full((n, 7), NAN), np.zeros(n, dtype=np.uint8)
+            FL, ST = np.zeros(n, dtype=np.uint8), np.full(n, 255, dtype=np.uint8)
+            for i in range(n):
+                ctrl.nb_search_points = 20
+                OC[i], ret = _outcome(lambda i=i: ctrl.symbolic_inverse_kinematics(ARMS[arm[i]], Ms[i], "discrete"))
+                assert not ctrl.emergency_stop
+                if ret is not None:
+                    FL[i], ST[i] = bool(ret[1]), STATE_CODES.get(ret[2], 255)
+                    if len(ret[0]) == 7:
+                        J[i] = np.array(ret[0], dtype=float)
+            data[f"{tag}_ctrl_outcome"], data[f"{tag}_ctrl_joints"] = OC, J
+            data[f"{tag}_ctrl_reachable"], data[f"{tag}_ctrl_state"] = FL, ST
+        # ControlIK discrete with a far preferred_theta (compared unwrapped, utils.py:357-388), on ordinary goals
+        th = F.far_thetas()[0]
+        pos, eul, arm = F.preferred_theta_goals()
+        Ms = F.goal_matrices(pos, eul)
+        J = np.full((len(th), len(Ms), 7), NAN)
+        FL, ST = np.zeros(J.shape[:2], dtype=np.uint8), np.full(J.shape[:2], 255, dtype=np.uint8)
+        for q, t in enumerate(th):
+            for i in range(len(Ms)):
+                ctrl.nb_search_points = 20
+                oc, ret = _outcome(lambda i=i, t=t: ctrl.symbolic_inverse_kinematics(ARMS[arm[i]], Ms[i], "discrete", preferred_theta=float(t)))
+                assert oc == OUTCOME_RETURNED and not ctrl.emergency_stop
+                FL[q, i], ST[q, i] = bool(ret[1]), STATE_CODES.get(ret[2], 255)
+                if len(ret[0]) == 7:
+                    J[q, i] = np.array(ret[0], dtype=float)
+        data["pref_digest"] = digest(th, pos, eul, arm)
+        data["pref_joints"], data["pref_reachable"], data["pref_state"] = J, FL, ST
+    np.savez_compressed(os.path.join(out, "g22_far_inputs.npz"), **data)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(os.path.dirname(__file__), "..", "tests", "golden"))
@@ -1640,7 +1735,7 @@ def main():
              ("g7", gen_continuous_start), ("g8", gen_matrix_edges),
              ("g9", gen_custom_geometry), ("g10", gen_custom_urdf_control), ("g11", gen_emergency),
              ("g12", gen_continuous_modes), ("g13", gen_hostile), ("g14", gen_scale), ("g15", gen_stages), ("g16", gen_scale_continuous), ("g17", gen_scale_variants),
-             ("g18", gen_utils), ("g20", gen_ztip_geometry), ("g21", gen_discrete_theta_geometry)]
+             ("g18", gen_utils), ("g20", gen_ztip_geometry), ("g21", gen_discrete_theta_geometry), ("g22", gen_far_inputs)]
     bad = 0
     for name, fn in steps:
         if args.only and name not in args.only.split(","):  # exact names: "g1" does not select "g12"

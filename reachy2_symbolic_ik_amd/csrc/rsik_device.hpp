@@ -81,6 +81,49 @@ __device__ __forceinline__ bool all_finite(const double (&v)[N]) {
     return ok;
 }
 
+// Angles a caller supplies (the Euler angles of a pose, an explicit theta, previous joints) may be any finite double, and the
+// reference answers all of them (libm reduces by pi exactly).  fast_sincos is accurate to a few 1e-16 up to 2e8 and wrong from
+// 2^31 pi/32 = 2.108e8 on (its table row is taken from a 32-bit integer), so an angle of magnitude >= 2^27 is first replaced by
+// the angle of [-pi, pi] it is congruent to: sin and cos from the device library, whose reduction carries 2/pi to as many bits
+// as the argument needs, then the angle of that unit vector (a few 1e-16 rad in all).  Lanes with such an angle are rare:
+// the branch is skipped by every wave that holds none.  An infinity comes back as NaN, a NaN never gets here.
+constexpr double kFarAngle = 134217728.0;  // 2^27
+__device__ inline double reduce_far_angle(double x) {
+    double s, c;
+    ::sincos(x, &s, &c);
+    return ::atan2(s, c);
+}
+__device__ __forceinline__ double near_angle(double x) {
+    if (RSIK_RARE(fabs(x) >= kFarAngle)) x = reduce_far_angle(x);
+    return x;
+}
+// The three angles of one goal, through ONE copy of the reduction (the values rotate through it)
+__device__ __forceinline__ void near_angles3(double& a, double& b, double& c) {
+    if (RSIK_RARE(fmax(fmax(fabs(a), fabs(b)), fabs(c)) >= kFarAngle)) {
+#pragma clang loop unroll(disable)
+        for (int q = 0; q < 3; q++) {
+            const double t = a;
+            a = b; b = c; c = near_angle(t);
+        }
+    }
+}
+// A pose row [x, y, z, roll, pitch, yaw] as it arrives: true when it is not numbers (include/rsik.h "Rows that are not numbers"),
+// and the far angles of a row that is numbers are reduced in place.  The common path pays what all_finite paid: one compare
+// per entry — the angles against 2^27 instead of infinity.
+__device__ __forceinline__ bool settle_pose(double (&v)[6]) {
+    bool plain = true;
+#pragma unroll
+    for (int k = 0; k < 3; k++) plain = plain && (fabs(v[k]) < __builtin_inf());
+#pragma unroll
+    for (int k = 3; k < 6; k++) plain = plain && (fabs(v[k]) < kFarAngle);
+    bool invalid = false;
+    if (RSIK_RARE(!plain)) {
+        invalid = !all_finite(v);
+        if (!invalid) near_angles3(v[3], v[4], v[5]);
+    }
+    return invalid;
+}
+
 // Python float modulo `a % (2*pi)` (result in [0, 2pi)).  CPython computes fmod(a, b) (exact) and adds b
 // when the signs differ.  For the small quotients on this path a - q*2pi is exactly representable, so one
 // fma reproduces fmod bit for bit; the two fix-ups only fire when a*(1/2pi) rounded across an integer.
@@ -88,6 +131,15 @@ __device__ __forceinline__ bool all_finite(const double (&v)[N]) {
 // under half an ulp of 2 pi (a in (-2^-51, 0); angle_diff's (a - b) + pi one ulp below 0) fmod(a) + 2 pi ROUNDS to fl(2 pi),
 // which is what `%` returns — angle_diff then gives +pi, not -pi.  So m >= 2 pi is only taken down where the quotient
 // q + 1 leaves a non-negative (then exact) remainder.
+// pymod_2pi below is Python's `%` while its quotient is within one of the true one: |a| < 2^50 (q is a rounded product of relative
+// error 2^-52).  A caller's angle beyond that — the preferred theta of a discrete launch, handed to limit_theta_to_interval when its
+// shortcut is taken — is first taken into [0, 2 pi) with the device library's exact fmod, as CPython does (out of line, rare):
+constexpr double kExactQuotient = 1125899906842624.0;  // 2^50
+__device__ inline double pymod_2pi_far(double a) {
+    double m = ::fmod(a, kTwoPi);
+    if (m < 0) m += kTwoPi;
+    return m;
+}
 __device__ __forceinline__ double pymod_2pi(double a) {
     double q = floor(a * 0.15915494309189535);
     double m = fma(-q, kTwoPi, a);
@@ -175,6 +227,11 @@ __device__ __forceinline__ Rot rot_from_euler(double roll, double pitch, double 
     r.m[3] = sc * cb; r.m[4] = fma(scsb, sa, cc * ca);    r.m[5] = fma(scsb, ca, -(cc * sa));
     r.m[6] = -sb;     r.m[7] = cb * sa;                r.m[8] = cb * ca;
     return r;
+}
+// ... of angles as a caller gave them (any finite double), for the kernels off the hot path: one more compare than settle_pose
+__device__ __forceinline__ Rot rot_from_caller_euler(double roll, double pitch, double yaw) {
+    near_angles3(roll, pitch, yaw);
+    return rot_from_euler(roll, pitch, yaw);
 }
 
 // utils.get_euler_from_homogeneous_matrix (U:84-90): Rotation.from_matrix(R).as_euler("xyz").  Follows the two
@@ -388,6 +445,10 @@ __device__ Reach reach_impl(const Acc& A, V3 pos_in, const V3 woff, const NL no_
     if (RSIK_RARE(ss0 > A(RSIK_C_MAX_LEN_SQ))) {
         double nd = sqrt_cr(ss0) + pm;
         gp = madd(dv * fast_rcp(nd), A(RSIK_C_MAX_LEN), s);
+        // a finite position whose squared distance overflows (|dv| beyond 1.34e154): the reference's norm is inf, its
+        // direction dv / inf is 0 and the goal becomes the shoulder itself (sqrt_cr(inf) is inf * 0, not a number)
+        // (an infinite ENTRY is a row that is not numbers: its NaN stays, as before)
+        if (ss0 == __builtin_inf() && fmax(fmax(fabs(dv.x), fabs(dv.y)), fabs(dv.z)) < __builtin_inf()) gp = s;
         st = RSIK_STATE_POSE_OUT_OF_REACH;
     }
     if (RSIK_RARE(gp.x < bl)) {
@@ -736,7 +797,9 @@ struct JointsOut {
 typedef const __attribute__((address_space(1))) double* GConst;  // a global-memory row (per-row previous joints)
 // Prev: the pointer type of previous_joints — the per-row entries pass a global-address-space row (GConst), which keeps
 // their instantiations apart from the launch-constant ones (sharing one changes how the uniform kernels are compiled).
-template <bool FRESH, bool TIPZ = false, class Acc, class Prev = const double*>
+// FAR_PREV: previous_joints can be a caller's row of any size (near_angle before its sine and cosine are taken at an exact
+// singularity); false where it is the trajectory state the library itself carries (the pipeline's chain, registers as before).
+template <bool FRESH, bool TIPZ = false, bool FAR_PREV = true, class Acc, class Prev = const double*>
 __device__ JointsOut joints_from_theta_g(const Acc& A, Reach& r, const Goal& G, double ct, double st, Prev prev) {
     RSIK_MARK("joints_elbow");
     JointsOut o;
@@ -779,7 +842,7 @@ __device__ JointsOut joints_from_theta_g(const Acc& A, Reach& r, const Goal& G, 
     const bool sing_sp = RSIK_RARE(q.x == 0 && q.z == 0);
     if (sing_sp) {  // [D] exact singularity: keep the previous pitch
         double s_, c_;
-        fast_sincos(prev[0], &s_, &c_);
+        fast_sincos(FAR_PREV ? near_angle(prev[0]) : prev[0], &s_, &c_);
         cphi = c_; sphi = -s_; rho = 0.0;
     } else {
         const double rho2 = fma(q.x, q.x, q.z * q.z);
@@ -806,7 +869,7 @@ __device__ JointsOut joints_from_theta_g(const Acc& A, Reach& r, const Goal& G, 
     double sigma, ca, sa;
     const bool sing_ey = RSIK_RARE(pw.y == 0 && pw.z == 0);
     if (sing_ey) {  // [D] exact singularity
-        fast_sincos(prev[2], &sa, &ca);
+        fast_sincos(FAR_PREV ? near_angle(prev[2]) : prev[2], &sa, &ca);
         sigma = 0.0;
     } else {
         const double sig2 = fma(pw.y, pw.y, pw.z * pw.z);

@@ -284,6 +284,8 @@ __global__ __launch_bounds__(kDiscBlock, RSIK_DISC_MIN_WAVES) RSIK_DISC_ATTR voi
     double jv[7];
     double c4, s4, c5, s5, c6, s6;
     if (found) {  // C:454-456
+        // (theta can be the caller's preferred theta itself, any finite double: `theta % 2 pi` of U:93 must stay exact)
+        if (RSIK_RARE(!(fabs(theta) < kExactQuotient))) theta = pymod_2pi_far(theta);
         theta = limit_theta_to_interval(theta, K.lim[slot][0], K.lim[slot][1]);
         double st, ct;
         fast_sincos(theta, &st, &ct);

@@ -208,7 +208,7 @@ __global__ __launch_bounds__(kBlock, RSIK_PATH_MIN_WAVES) void solve_path_kernel
         double in[6];
 #pragma unroll
         for (int c = 0; c < 6; c++) in[c] = ld_stream(K.in[c] + row);
-        const bool invalid = !all_finite(in);  // rsik.h "Rows that are not numbers"
+        const bool invalid = settle_pose(in);  // rsik.h "Rows that are not numbers"
         const V3 pos = {in[0], in[1], in[2]};
         const Goal G = goal_of_pose<TIPZ>(A, in[3], in[4], in[5]);
         Reach r = reach_g<false, false>(A, pos, G.woff);
@@ -230,7 +230,7 @@ __global__ __launch_bounds__(kBlock, RSIK_PATH_MIN_WAVES) void solve_path_kernel
                 theta = fa + th_in * (fb - fa);
             }
             double ct, st;
-            fast_sincos(theta, &st, &ct);
+            fast_sincos(near_angle(theta), &st, &ct);
             o = joints_from_theta_g<true, TIPZ>(A, r, G, ct, st, (const double*)K.prev);
             cand = !(skip_projected && o.projected);
 #pragma unroll

@@ -391,7 +391,7 @@ __device__ __forceinline__ void step_joints(const Acc& A, const ContRunArgs& K, 
                                             const double* prev, double (&jv)[7], bool& sing) {
     double sn, cs;
     fast_sincos(theta, &sn, &cs);
-    JointsOut o = joints_from_theta_g<true>(A, r, G, cs, sn, prev);
+    JointsOut o = joints_from_theta_g<true, false, false>(A, r, G, cs, sn, prev);
 #pragma unroll
     for (int k = 0; k < 7; k++) jv[k] = o.j[k];
     sing = o.sing;

@@ -335,7 +335,7 @@ __global__ __launch_bounds__(kBlock, RSIK_SOLVE_MIN_WAVES) void solve_kernel(con
     double* lds_wave = lds[wave];
 
     // rsik.h "Rows that are not numbers": judged here, while the six values are at hand (further down it would keep them all alive)
-    const bool invalid = !all_finite(in);
+    const bool invalid = settle_pose(in);
     const V3 pos = {in[0], in[1], in[2]};
     Goal G;
     if constexpr (TIPZ) {
@@ -370,7 +370,7 @@ __global__ __launch_bounds__(kBlock, RSIK_SOLVE_MIN_WAVES) void solve_kernel(con
                     if (a > b) b += kTwoPi;
                     theta = a + th_in * (b - a);
                 }
-                fast_sincos(theta, &st, &ct);
+                fast_sincos(near_angle(theta), &st, &ct);
             }
             // Two statements chosen at compile time: a pointer that could be either the kernarg array or a global row would
             // turn the uniform kernels' loads into flat loads, and any shared local changes how the uniform kernels are

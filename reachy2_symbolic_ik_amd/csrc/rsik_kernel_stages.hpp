@@ -236,7 +236,7 @@ __global__ __launch_bounds__(kBlock) void stage_kernel(const StageArgs K) {
         break;
     }
     case RSIK_STAGE_WRIST_POSITION: {  // S:418-425.  in: position 3, euler 3; out: wrist 3
-        const Rot Rg = rot_from_euler(x[3], x[4], x[5]);
+        const Rot Rg = rot_from_caller_euler(x[3], x[4], x[5]);
         put(0, wrist_position(make_goal(A, Rg).woff, V3{x[0], x[1], x[2]}));
         break;
     }

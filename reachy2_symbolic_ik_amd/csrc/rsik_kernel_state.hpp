@@ -39,7 +39,7 @@ __global__ __launch_bounds__(kBlock) void reach_state_kernel(const StateArgs K) 
     double e0 = K.in[3][i], e1 = K.in[4][i], e2 = K.in[5][i];
     const double in6[6] = {pos.x, pos.y, pos.z, e0, e1, e2};
     const bool invalid = !all_finite(in6);
-    Rot Rg = rot_from_euler(e0, e1, e2);
+    Rot Rg = rot_from_caller_euler(e0, e1, e2);
     Reach r = K.no_limits ? reach<true>(A, pos, Rg) : reach<false>(A, pos, Rg);
     if (RSIK_RARE(invalid)) { reach_invalid_input(r); r.stage = 0; }  // (stage 0: the solver object stays as it was)
     double* S = K.solver_state + i * RSIK_SOLVER_STATE_STRIDE;
@@ -80,12 +80,12 @@ __global__ __launch_bounds__(kBlock) void joints_state_kernel(const StateArgs K)
     const Acc<MIXED> A = make_acc<MIXED>(K.arms, MIXED ? (K.arm[i] != 0) : false, lds_tab);
     double* S = K.solver_state + i * RSIK_SOLVER_STATE_STRIDE;
     Reach r = reach_from_state(S);
-    Rot Rg = rot_from_euler(S[3], S[4], S[5]);
+    Rot Rg = rot_from_caller_euler(S[3], S[4], S[5]);  // (the row keeps the angles as they came)
     double prev[7];
 #pragma unroll
     for (int k = 0; k < 7; k++) prev[k] = K.prev ? K.prev[i * 7 + k] : 0.0;
     double st, ct;
-    fast_sincos(K.theta[i], &st, &ct);
+    fast_sincos(near_angle(K.theta[i]), &st, &ct);
     JointsOut o = joints_from_theta<false>(A, r, Rg, ct, st, prev);
     if (K.joints) {
 #pragma unroll
@@ -108,7 +108,7 @@ __global__ __launch_bounds__(kBlock) void elbow_state_kernel(const StateArgs K) 
     const double* S = K.solver_state + i * RSIK_SOLVER_STATE_STRIDE;
     Reach r = reach_from_state(S);
     double st, ct;
-    fast_sincos(K.theta[i], &st, &ct);
+    fast_sincos(near_angle(K.theta[i]), &st, &ct);
     V3 e = elbow_on_circle(r, ct, st);
     K.elbow[3 * i] = e.x; K.elbow[3 * i + 1] = e.y; K.elbow[3 * i + 2] = e.z;
 }
@@ -151,7 +151,7 @@ __global__ __launch_bounds__(kBlock) void fk_kernel(const FkArgs K) {
             gp = {K.goal[9][i], K.goal[10][i], K.goal[11][i]};
         } else {
             gp = {K.goal[0][i], K.goal[1][i], K.goal[2][i]};
-            Rg = rot_from_euler(K.goal[3][i], K.goal[4][i], K.goal[5][i]);
+            Rg = rot_from_caller_euler(K.goal[3][i], K.goal[4][i], K.goal[5][i]);
         }
         const V3 d = o.pos - gp;
         double fro = 0.0;

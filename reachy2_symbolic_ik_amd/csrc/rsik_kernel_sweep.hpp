@@ -66,7 +66,7 @@ __global__ __launch_bounds__(kBlock, RSIK_SWEEP_MIN_WAVES) void solve_sweep_kern
     const AccSweep<MIXED> A = kernarg_acc<AccSweep<MIXED>, SweepArgs>(lds_tab, (MIXED != 0 && K.arm[tile0 + tt] != 0) ? 1 : 0);
     double* lds_wave = lds[wave];
 
-    const bool invalid = !all_finite(in);  // rsik.h "Rows that are not numbers"
+    const bool invalid = settle_pose(in);  // rsik.h "Rows that are not numbers"
     const V3 pos = {in[0], in[1], in[2]};
     const Goal G = goal_of_pose<TIPZ>(A, in[3], in[4], in[5]);
     Reach r = reach_g<false, false>(A, pos, G.woff);
@@ -109,7 +109,7 @@ __global__ __launch_bounds__(kBlock, RSIK_SWEEP_MIN_WAVES) void solve_sweep_kern
         bool projected = false;
         if (r.ok) {
             double ct, st;
-            fast_sincos(theta, &st, &ct);
+            fast_sincos(near_angle(theta), &st, &ct);
             r.w = wrist;
             if constexpr (PREV_ROWS) {
                 JointsOut o = joints_from_theta_g<true, TIPZ>(A, r, G, ct, st, (GConst)(K.prev_rows + (tile0 + tt) * 7));

@@ -42,7 +42,7 @@ __device__ __forceinline__ ThetaSearchOut theta_search(const Acc& A, Reach& r, c
     ThetaSearchOut S;
     auto eval = [&](double th, bool keep) -> double {
         double st, ct;
-        fast_sincos(th, &st, &ct);
+        fast_sincos(near_angle(th), &st, &ct);  // (th can be the caller's preferred theta: any finite double)
         const JointsOut o = joints_from_theta_g<false>(A, r, G, ct, st, zeros);
         double acc = 0.0;
         if (RSIK_RARE(n14)) {
@@ -133,7 +133,7 @@ __global__ __launch_bounds__(kBlock) void theta_from_joints_kernel(const ThetaFr
         for (int k = 0; k < 6; k++) p[k] = K.goal[k][ii];
         invalid = invalid || !all_finite(p);
         pos = {p[0], p[1], p[2]};
-        Rg = rot_from_euler(p[3], p[4], p[5]);
+        Rg = rot_from_caller_euler(p[3], p[4], p[5]);
     }
     const Goal G = make_goal(A, Rg);
     Reach r = reach_g<true>(A, pos, G.woff);  // is_reachable_no_limits (S:85-119)
@@ -167,7 +167,7 @@ __global__ __launch_bounds__(kBlock) void theta_from_joints_state_kernel(const T
     const int slot = MIXED ? (A.isl ? 1 : 0) : 0;
     double* Sr = K.solver_state + i * RSIK_SOLVER_STATE_STRIDE;
     Reach r = reach_from_state(Sr);
-    const Goal G = make_goal(A, rot_from_euler(Sr[3], Sr[4], Sr[5]));
+    const Goal G = make_goal(A, rot_from_caller_euler(Sr[3], Sr[4], Sr[5]));
     const bool n14 = K.n_current == 14;
     double cur[14];
 #pragma unroll

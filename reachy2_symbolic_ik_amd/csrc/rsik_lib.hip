@@ -605,6 +605,12 @@ static int control_discrete_impl(rsik_ctx* ctx, const char* who, int64_t n, cons
         control_limits(a, constrained_mode, preferred_theta, K.lim[slot], &K.pref[slot]);
         K.pref_cs[slot] = std::cos(K.pref[slot]);  // np.cos / np.sin of the reference (U:359-360), once per launch
         K.pref_sn[slot] = std::sin(K.pref[slot]);
+        // The arc-end candidates of the per-lane search take |angle_diff(theta_k, preferred)| for a function of the wrapped
+        // preferred angle.  For a huge preferred angle theta_k - preferred rounds to its ulp (0.125 at 1e15, everything from 2^53
+        // on) and the reference's first strict minimum is decided by that staircase: such a launch evaluates every grid point,
+        // in the reference's own arithmetic (the cooperative sweep).
+        // (This overrides RSIK_OPT_SWEEP_MODE for such a launch, 2 included: the per-lane search is not the reference there.)
+        if (!(std::fabs(K.pref[slot]) < rsik::kFarAngle)) K.sweep_mode = 1;
         if (previous_sol_host) {  // (the PREV_ROWS kernels read neither: prev_rows takes prev_sol's bytes, prev_cs / prev_sn stay unset)
             for (int k = 0; k < 7; k++) K.prev_sol[slot][k] = previous_sol_host[7 * a + k];
             for (int k = 0; k < 3; k++) {
@@ -661,6 +667,14 @@ static int fill_continuous(rsik_ctx* ctx, const char* who, rsik::ContinuousArgs&
     int rc = check_arms(ctx, arm, arm_uniform, who);
     if (rc != RSIK_OK) return rc;
     if (!m12_soa || !cont_state || !joints) return fail(ctx, RSIK_E_INVALID, std::string(who) + ": m12_soa / cont_state / joints is NULL");
+    // include/rsik.h "Rows that are numbers, of any size": the continuous kernels take the sine and cosine of the preferred thetas
+    // (the start theta of a timed-out row) and wrap them with the branch-free modulo of the serial phases, both written for
+    // bounded angles, and the theta they would start is carried from step to step.  A finite preferred theta of magnitude >= 2^27
+    // is refused here, before anything is launched or written (a NaN / an infinity propagates as IEEE arithmetic, as before).
+    auto far_angle = [](double x) { return std::isfinite(x) && !(std::fabs(x) < rsik::kFarAngle); };
+    bool far_pref = far_angle(preferred_theta);
+    for (int slot = 0; slot < 2; slot++) far_pref = far_pref || far_angle(preferred_theta_self_host[slot_arm(arm, arm_uniform, slot)]);
+    if (far_pref) return fail(ctx, RSIK_E_INVALID, std::string(who) + ": |preferred_theta| / |preferred_theta_self| must be below 2^27 (134217728)");
     std::memset(&K, 0, sizeof K);
     K.n = n;
     K.first_timed_out = first_timed_out;

@@ -719,7 +719,7 @@ def test_scale_variants_checker_against_reference(golden_dir):
 def test_golden_fixtures_reproduce_from_the_reference():
     """`oracle/gen_golden.py --check`: the committed fixtures are what the reference, imported from /root/reference, produces today —
     regenerated into a temporary directory and compared array by array, byte for byte.  Here G1 (the catalogue: SymbolicIK and
-    ControlIK discrete), G6 (ControlIK continuous trajectories), G15 (the stage methods), G18, G20 (the tip-on-z geometry) and G21 (the theta search on the non-default geometries); `--check` without `--only` does
+    ControlIK discrete), G6 (ControlIK continuous trajectories), G15 (the stage methods), G18, G20 (the tip-on-z geometry), G21 (the theta search on the non-default geometries) and G22 (far inputs); `--check` without `--only` does
     every set (~15 min: G14, the BASELINE-scale digests, takes 5 of them on 7 cores, G16 1.5, G17 2.5).
     Skipped where the reference is not mounted (the GPU box: it never travels)."""
     import subprocess
@@ -729,7 +729,7 @@ def test_golden_fixtures_reproduce_from_the_reference():
         pytest.skip("/root/reference is not mounted here")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1")
-    p = subprocess.run([sys.executable, os.path.join(root, "oracle", "gen_golden.py"), "--check", "--only", "g1,g6,g15,g18,g20,g21"],
+    p = subprocess.run([sys.executable, os.path.join(root, "oracle", "gen_golden.py"), "--check", "--only", "g1,g6,g15,g18,g20,g21,g22"],
                        capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
     assert "CHECK g1_catalogue.npz: identical" in p.stdout and "CHECK g6_control_continuous.npz: identical" in p.stdout
@@ -737,6 +737,7 @@ def test_golden_fixtures_reproduce_from_the_reference():
     assert "CHECK g18_utils.npz: identical" in p.stdout
     assert "CHECK g20_ztip_geometry.npz: identical" in p.stdout
     assert "CHECK g21_discrete_theta_geometry.npz: identical" in p.stdout
+    assert "CHECK g22_far_inputs.npz: identical" in p.stdout
 
 
 def test_utils_helpers_on_explicit_arguments(golden_dir):
@@ -832,3 +833,67 @@ def test_discrete_theta_on_non_default_geometries(golden_dir):
                             if g[pre + "worked"][k, q, a, b]:
                                 assert theta == pref
             assert 0 < g[pre + "worked"].mean() < 1 and 0 < g[pre + "found"][:, 0].mean() < 1
+
+
+def test_far_inputs_checker_against_reference(golden_dir, arms):
+    """G22: finite goals far outside the usual ranges (tests/far_inputs.py) — Euler angles wound up to DBL_MAX, positions up to
+    DBL_MAX and down to the smallest denormal.  The reference answers every one of them without raising; the checker answers
+    the same: flags, states and the projected bit exactly, numbers within the bars of this file."""
+    import hashlib
+
+    import far_inputs as F
+
+    g = load(golden_dir, "g22_far_inputs.npz")
+    ar, al = arms[("r_arm", F.SINGULARITY_OFFSET)], arms[("l_arm", F.SINGULARITY_OFFSET)]
+
+    def digest(*arrays):
+        h = hashlib.sha256()
+        for a in arrays:
+            h.update(np.ascontiguousarray(a).tobytes())
+        return np.frombuffer(h.digest(), dtype=np.uint8)
+
+    w = F.wound_rows()
+    assert np.array_equal(digest(w["pos"], w["eul"], w["twin_eul"], w["arm"]), g["wound_digest"]), "tests/far_inputs.py changed: regenerate G22"
+    sets = [("wound_", w["pos"], w["eul"], w["arm"])]
+    for tag, rows in (("far", F.far_position_rows()), ("tiny", F.tiny_position_rows())):
+        pos, eul, arm = rows[:3]
+        assert np.array_equal(digest(pos, eul, arm), g[f"{tag}_digest"]), "tests/far_inputs.py changed: regenerate G22"
+        sets.append((tag + "_", pos, eul, arm))
+    every = int(g["theta_every"])
+    for pre, pos, eul, arm in sets:
+        assert (g[pre + "outcome"] == 0).all(), pre   # the reference returned on every row
+        res = orc.solve_batch(ar, al, pos, eul, arm_id=arm)
+        _check_symbolic(res, g, pre)
+        if pre + "theta_joints" in g:
+            step = every if pre == "wound_" else 1
+            sub = np.arange(0, len(pos), step)
+            m = g[pre + "reachable"][sub].astype(bool)
+            for q, th in enumerate(g["thetas"]):
+                r2 = orc.solve_batch(ar, al, pos[sub], eul[sub], arm_id=arm[sub], theta_policy=1, theta_in=np.full(len(sub), th))
+                assert np.max(np.abs(r2["joints"][m] - g[pre + "theta_joints"][sub // step, q][m])) < TOL, (pre, th)
+                assert np.max(np.abs(r2["elbow"][m] - g[pre + "theta_elbow"][sub // step, q][m])) < TOL, (pre, th)
+    for g_idx in range(len(F.RUNGS)):
+        assert g["wound_reachable"][w["rung"] == g_idx].mean() >= 0.9, F.RUNGS[g_idx]
+    # ControlIK discrete on the same positions as translation columns
+    cr, cl = _ctrl_arms()
+    for tag, rows in (("far", F.far_position_rows()), ("tiny", F.tiny_position_rows())):
+        pos, eul, arm = rows[:3]
+        assert (g[f"{tag}_ctrl_outcome"] == 0).all(), tag
+        res = orc.control_discrete_batch(cr, cl, F.goal_matrices(pos, eul), arm_id=arm)
+        np.testing.assert_array_equal(res["reachable"], g[f"{tag}_ctrl_reachable"], err_msg=tag)
+        np.testing.assert_array_equal(res["state"], g[f"{tag}_ctrl_state"], err_msg=tag)
+        m = g[f"{tag}_ctrl_reachable"].astype(bool)
+        assert tag == "far" or m.mean() > 0.3   # (x next to 0 is a backward pose: a third of the tiny rows)
+        assert not m.any() or np.max(np.abs(res["joints"][m] - g[f"{tag}_ctrl_joints"][m])) < 1e-7, tag
+    assert not g["far_ctrl_reachable"].any() and set(g["far_ctrl_state"]) == {1, 2}
+    # ... and with a far preferred_theta on ordinary goals
+    th = F.far_thetas()[0]
+    pos, eul, arm = F.preferred_theta_goals()
+    assert np.array_equal(digest(th, pos, eul, arm), g["pref_digest"]), "tests/far_inputs.py changed: regenerate G22"
+    M = F.goal_matrices(pos, eul)
+    for q, t in enumerate(th):
+        res = orc.control_discrete_batch(cr, cl, M, arm_id=arm, preferred_theta=float(t))
+        np.testing.assert_array_equal(res["reachable"], g["pref_reachable"][q], err_msg=repr(t))
+        np.testing.assert_array_equal(res["state"], g["pref_state"][q], err_msg=repr(t))
+        m = g["pref_reachable"][q].astype(bool)
+        assert m.mean() > 0.8 and np.max(np.abs(res["joints"][m] - g["pref_joints"][q][m])) < 1e-7, t
