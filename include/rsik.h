@@ -479,6 +479,51 @@ int rsik_solve_path(rsik_ctx *ctx, int64_t n, int64_t n_steps, const double *con
                     double *interval, uint8_t *reachable, uint8_t *state);
 
 /*
+ * rsik_reach_map — a reachability map (capability map): for each of n_pos positions, over one set of n_rot hand orientations, how
+ * many of the orientations are reachable, which ones, with which is_reachable outcome, and how much elbow freedom is left.  What the
+ * reference's task_space_test builds pose by pose (src/benchmark/ik_comparison.py:137-181), from one launch and with a few bytes of
+ * output per POSITION.  Added within ABI version 8: a new symbol, nothing else changed.
+ *
+ *   n_pos            positions, >= 0; n_pos == 0 launches nothing
+ *   pos_soa          three device arrays of n_pos doubles: px, py, pz
+ *   arm              [n_pos], one byte per POSITION (0 = r, 1 = l), or NULL with arm_uniform; rsik_solve's checks and error codes
+ *                    (RSIK_E_NOT_SET where an arm's constants were not uploaded)
+ *   n_rot            orientations, 1 ... 4096 (anything else: RSIK_E_INVALID)
+ *   euler_soa        three device arrays of n_rot doubles: roll, pitch, yaw, the convention of rsik_solve
+ *
+ * Definition (the result does not depend on how the kernel is laid out): pose (i, j) is position i with orientation j.  Its
+ * reachable, state and interval are, bit for bit, what rsik_solve returns under RSIK_THETA_NONE for that pose with arm byte arm[i].
+ *
+ * Outputs, one row per position, any of them NULL (all four NULL: RSIK_E_INVALID):
+ *   count            [n_pos] uint32: the number of j with reachable == 1
+ *   state_count      [n_pos][RSIK_REACH_MAP_STATES] uint32: entry c is the number of j whose state code is c (RSIK_STATE_*, indexed by
+ *                    the code); every row sums to n_rot
+ *   theta_measure    [n_pos]: the sum over the reachable j of the interval's width, i1 - i0, plus 2 pi where i0 > i1 (radians of
+ *                    elbow angle left, summed over the orientations); 0.0, not NaN, where no orientation is reachable.  The order of
+ *                    the sum is the kernel's own: the value is defined to rounding, n_rot^2 * 2 pi * 2^-53.  It is reproducible:
+ *                    two launches on the same inputs give the same bits (no floating-point atomics, nothing accumulates into the
+ *                    caller's memory).
+ *   mask             [n_pos][ceil(n_rot / 64)] uint64: bit (j % 64) of word (j / 64) is pose (i, j)'s reachable flag; the padding
+ *                    bits of the last word are 0
+ *
+ * "Rows that are not numbers" applies pose by pose, and follows from the definition:
+ *   a position with a NaN or an infinity puts all n_rot of its poses in bin RSIK_STATE_INVALID_INPUT: count 0, theta_measure 0.0,
+ *   mask 0; no other position changes;
+ *   an orientation with a NaN or an infinity puts that one pose of every position in that bin, and nothing else changes.
+ * Rows that are numbers, of any size, are answered as rsik_solve answers them: angles of magnitude 2^27 and above, positions up to
+ * DBL_MAX.
+ *
+ * The parallelism comes from the POSITIONS: a position is owned by one wave, whose lanes are 64 orientations at a time.  A launch
+ * with few positions and many orientations is correct but not fast (a few thousand positions fill an MI355X).
+ * Enqueued on the context's stream; allocates nothing, needs no workspace and never waits for the device.
+ */
+#define RSIK_REACH_MAP_STATES 11 /* one bin per RSIK_STATE_* code, indexed by the code */
+int rsik_reach_map(rsik_ctx *ctx, int64_t n_pos, const double *const pos_soa[3],
+                   const uint8_t *arm, int arm_uniform,
+                   int n_rot, const double *const euler_soa[3],
+                   uint32_t *count, uint32_t *state_count, double *theta_measure, uint64_t *mask);
+
+/*
  * rsik_control_discrete_rows — rsik_control_discrete with previous_sol [n,7]: row i is ControlIK.previous_sol[name] of the
  *   caller that owns goal i, for that row's own arm (no 2x7 split).  It is get_joints' previous_joints (control_ik.py:454-456),
  *   the fallback joints when no theta is found and current_joints is NULL (:237-238, :457-458), and safety_checks'

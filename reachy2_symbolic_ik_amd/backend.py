@@ -440,6 +440,50 @@ class HipSolver:
         # (the workspace: torch allocated it on the launch's stream and hands it out again in stream order; a plan keeps it)
         return self._finish(res, "rsik_solve_path", cargs, plan_only, (pose_soa, arm, thetas, cols, start_joints, w, workspace))
 
+    # ------------------------------------------------------------------ rsik_reach_map
+    REACH_MAP_OUTPUTS = ("count", "state_count", "theta_measure", "mask")
+
+    def reach_map(
+        self,
+        pos_soa: torch.Tensor,
+        euler_soa: torch.Tensor,
+        arm: Optional[torch.Tensor] = None,
+        arm_uniform: int = 0,
+        want: Sequence[str] = REACH_MAP_OUTPUTS,
+        out: Optional[Dict[str, torch.Tensor]] = None,
+        plan_only: bool = False,
+    ) -> Dict[str, torch.Tensor]:
+        """A reachability map from one launch (rsik_reach_map): every position of pos_soa [3, n_pos] with every orientation of
+        euler_soa [3, n_rot] (rows roll, pitch, yaw; 1 ... 4096 of them), reduced per position on the device.  Pose (i, j) is judged
+        bit for bit as solve() judges it under THETA_NONE with arm byte arm[i] (`arm`: [n_pos] u8, one per POSITION, or None
+        with arm_uniform).
+        `want`: which of the four outputs to compute, at least one.  Returns device tensors, one row per position:
+        count [n_pos] int32 (reachable orientations), state_count [n_pos, 11] int32 (orientations per state code),
+        theta_measure [n_pos] float64 (summed interval width of the reachable ones, 0.0 where there is none),
+        mask [n_pos, ceil(n_rot / 64)] int64 (the words' bits: bit j % 64 of word j // 64 is pose (i, j)'s flag; see
+        unpack_reach_mask).  The parallelism comes from the positions: few positions with many orientations are correct, not fast.
+        plan_only=True launches nothing and adds res["launch"], a zero-overhead re-launch callable (see plan())."""
+        if pos_soa.dim() != 2 or pos_soa.shape[0] != 3:
+            raise ValueError("pos_soa must have shape [3, n_pos]")
+        if euler_soa.dim() != 2 or euler_soa.shape[0] != 3:
+            raise ValueError("euler_soa must have shape [3, n_rot]")
+        n_pos, n_rot = int(pos_soa.shape[1]), int(euler_soa.shape[1])
+        if not 1 <= n_rot <= 4096:
+            raise ValueError("euler_soa: between 1 and 4096 orientations")
+        want = tuple(want)
+        if not want or any(name not in self.REACH_MAP_OUTPUTS for name in want):
+            raise ValueError(f"want must name at least one of {self.REACH_MAP_OUTPUTS}")
+        pos_soa = self._dev_cols(pos_soa, 3, n_pos, "pos_soa")
+        euler_soa = self._dev_cols(euler_soa, 3, n_rot, "euler_soa")
+        arm = self._arm_ids(arm, n_pos)
+        shapes = {"count": ((n_pos,), torch.int32), "state_count": ((n_pos, 11), torch.int32),
+                  "theta_measure": ((n_pos,), _F64), "mask": ((n_pos, (n_rot + 63) // 64), torch.int64)}
+        res = {name: self._out_buf(out, name, *shapes[name]) for name in self.REACH_MAP_OUTPUTS if name in want}
+        pcols, ecols = self._cols(pos_soa, 3), self._cols(euler_soa, 3)
+        cargs = (n_pos, pcols, _ptr(arm), int(arm_uniform), n_rot, ecols,
+                 _ptr(res.get("count")), _ptr(res.get("state_count")), _ptr(res.get("theta_measure")), _ptr(res.get("mask")))
+        return self._finish(res, "rsik_reach_map", cargs, plan_only, (pos_soa, euler_soa, arm, pcols, ecols))
+
     def plan(self, fn_name: str, *args):
         """Binds one C-ABI call with all its arguments once; the returned callable re-issues exactly that launch (a few
         microseconds of host time per call — the hot loop of a caller that re-solves resident buffers, e.g. bench.py).

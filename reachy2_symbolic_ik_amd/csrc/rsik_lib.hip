@@ -17,6 +17,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <algorithm>
 #include <cstring>
 #include <new>
 #include <string>
@@ -36,6 +37,7 @@
 #include "rsik_kernel_sweep.hpp"
 #include "rsik_kernel_nearest.hpp"
 #include "rsik_kernel_path.hpp"
+#include "rsik_kernel_reach_map.hpp"
 
 // =====================================================================================
 // C ABI
@@ -541,6 +543,47 @@ int rsik_solve_path(rsik_ctx* ctx, int64_t n, int64_t n_steps, const double* con
     if ((rc = launch_begin(ctx, n, &grid, who, rsik::kBlock / 64)) != RSIK_OK) return rc;
     with_int3(launch_form(ctx, K.arms, arm), [&](auto FORM) { with_bool(tip_on_z(ctx, K.arms), [&](auto TIPZ) {
         hipLaunchKernelGGL((rsik::solve_path_kernel<FORM(), TIPZ()>), grid, block, 0, ctx->stream, K); }); });
+    return launch_end(ctx);
+}
+
+// Positions per wave of reach_map_kernel: as many (16, 8, 4, 2, 1) as still leave eight workgroups per compute unit, so that positions which
+// end early ("Pose out of reach" is a scalar branch) do not leave compute units idle; above that, more positions per workgroup
+// spread the orientation stage and the table staging over more poses.
+static int reach_map_pos_per_wave(const rsik_ctx* ctx, int64_t n_pos) {
+    for (int ppw = rsik::kReachMapMaxPosPerWave; ppw > 1; ppw >>= 1)
+        if (n_pos >= (int64_t)ctx->compute_units * 8 * rsik::kReachMapWaves * ppw) return ppw;
+    return 1;
+}
+
+// rsik_reach_map: is_reachable of n_pos positions x n_rot orientations, reduced per position on the device (rsik_kernel_reach_map.hpp)
+int rsik_reach_map(rsik_ctx* ctx, int64_t n_pos, const double* const pos_soa[3], const uint8_t* arm, int arm_uniform,
+                   int n_rot, const double* const euler_soa[3],
+                   uint32_t* count, uint32_t* state_count, double* theta_measure, uint64_t* mask) {
+    if (!ctx) return RSIK_E_INVALID;
+    const char* who = "rsik_reach_map";
+    const std::string w(who);
+    if (n_pos < 0) return fail(ctx, RSIK_E_INVALID, w + ": n_pos < 0");
+    if (n_rot < 1 || n_rot > 4096) return fail(ctx, RSIK_E_INVALID, w + ": n_rot must be in [1, 4096]");
+    int rc = check_arms(ctx, arm, arm_uniform, who);
+    if (rc != RSIK_OK) return rc;
+    if (!count && !state_count && !theta_measure && !mask) return fail(ctx, RSIK_E_INVALID, w + ": count, state_count, theta_measure and mask are all NULL");
+    if (n_pos == 0) return RSIK_OK;
+    rsik::ReachMapArgs K;
+    K.n_pos = n_pos;
+    if ((rc = copy_cols(ctx, who, "pos_soa", "a pos_soa column", pos_soa, K.pos, 3)) != RSIK_OK) return rc;
+    if ((rc = copy_cols(ctx, who, "euler_soa", "a euler_soa column", euler_soa, K.eul, 3)) != RSIK_OK) return rc;
+    K.arm = arm;
+    K.n_rot = n_rot;
+    K.tile = std::min((n_rot + 63) & ~63, rsik::kReachMapTile);
+    K.pos_per_wave = reach_map_pos_per_wave(ctx, n_pos);
+    K.count = count; K.state_count = state_count; K.theta_measure = theta_measure; K.mask = mask;
+    bind_arms(ctx, arm, arm_uniform, K.arms);
+    const int form = launch_form(ctx, K.arms, arm);
+    const size_t lds_bytes = rsik::reach_map_lds_bytes(form != 0 ? 2 : 1, K.tile);  // at most 49 KiB: no attribute to raise
+    dim3 grid, block(rsik::kBlock);
+    if ((rc = launch_begin(ctx, n_pos, &grid, who, rsik::kReachMapWaves * K.pos_per_wave)) != RSIK_OK) return rc;
+    with_int3(form, [&](auto FORM) { with_bool(tip_on_z(ctx, K.arms), [&](auto TIPZ) {
+        hipLaunchKernelGGL((rsik::reach_map_kernel<FORM(), TIPZ()>), grid, block, lds_bytes, ctx->stream, K); }); });
     return launch_end(ctx);
 }
 

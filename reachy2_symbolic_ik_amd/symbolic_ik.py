@@ -357,6 +357,20 @@ class SymbolicIK:
         return _path_batch(self, {"arm_uniform": self.arm_id}, poses, start_joints, n_theta, thetas, policy, weights, skip_projected,
                            unwind, want_elbow, out, plan_only)
 
+    def reach_map_batch(self, positions: Any, orientations: Any, want: Sequence[str] = HipSolver.REACH_MAP_OUTPUTS,
+                        out: Optional[Dict[str, torch.Tensor]] = None, plan_only: bool = False) -> Dict[str, torch.Tensor]:
+        """A reachability map (capability map) of this arm in one launch: every position with every orientation of one set,
+        is_reachable per pair, reduced per position on the device — a few bytes back per position instead of a row per pose
+        (HipSolver.reach_map, rsik_reach_map).  Pose (i, j) is judged bit for bit as solve_batch(theta="none") judges it.
+
+        positions: [n_pos,3] or SoA [3,n_pos].  orientations: [n_rot,3] or SoA [3,n_rot] (roll, pitch, yaw), 1 ... 4096 of them.
+        want: which outputs to compute.
+        Returns device tensors, one row per position: count [n_pos] int32 (reachable orientations), state_count [n_pos,11] int32
+        (orientations per state code), theta_measure [n_pos] (summed interval width of the reachable ones: elbow freedom left),
+        mask [n_pos, ceil(n_rot/64)] int64 (bit j % 64 of word j // 64: pose (i, j) reachable; unpack_reach_mask gives the
+        bool [n_pos,n_rot] view).  The parallelism comes from the positions: few positions with many orientations are not fast."""
+        return _reach_map_batch(self, {"arm_uniform": self.arm_id}, positions, orientations, want, out, plan_only)
+
     def theta_from_joints_batch(self, poses: Any, current_joints: Any, preferred_theta: Optional[float] = None,
                                 out: Optional[Dict[str, torch.Tensor]] = None, plan_only: bool = False) -> Dict[str, torch.Tensor]:
         """For every row, the theta whose solution is closest to that row's measured joints: is_reachable_no_limits(pose),
@@ -511,6 +525,31 @@ def _path_batch(ik, arm, poses, start_joints, n_theta, thetas, policy, weights, 
                                  unwind=unwind, want_elbow=want_elbow, out=out, plan_only=plan_only, **arm)
 
 
+def _xyz_soa(rows: Any, device: Any, name: str) -> torch.Tensor:
+    """[n,3] rows or SoA [3,n] -> SoA [3,n] float64 on the device (a [3,3] input is taken as rows)."""
+    t = rows if isinstance(rows, torch.Tensor) else torch.as_tensor(np.asarray(rows, dtype=np.float64))
+    t = t.to(device=device, dtype=torch.float64)
+    if t.dim() != 2 or 3 not in t.shape:
+        raise ValueError(f"{name} must have shape [n,3] or [3,n]")
+    return t.t().contiguous() if t.shape[1] == 3 else t
+
+
+def _reach_map_batch(ik, arm, positions, orientations, want, out, plan_only):
+    pos = _xyz_soa(positions, ik._solver.device, "positions")
+    eul = _xyz_soa(orientations, ik._solver.device, "orientations")
+    ik._upload()
+    return ik._solver.reach_map(pos, eul, want=want, out=out, plan_only=plan_only, **arm)
+
+
+def unpack_reach_mask(mask: torch.Tensor, n_rot: int) -> torch.Tensor:
+    """The `mask` of reach_map_batch / HipSolver.reach_map, [n_pos, ceil(n_rot/64)] int64, as a bool tensor [n_pos, n_rot]:
+    entry (i, j) is pose (i, j)'s reachable flag."""
+    if mask.dim() != 2 or mask.shape[1] != (int(n_rot) + 63) // 64:
+        raise ValueError("mask must have shape [n_pos, ceil(n_rot / 64)]")
+    bits = torch.arange(64, dtype=torch.int64, device=mask.device)
+    return (((mask.unsqueeze(-1) >> bits) & 1) != 0).reshape(mask.shape[0], -1)[:, : int(n_rot)]
+
+
 def _theta_from_joints_batch(ik, arm, poses, current_joints, preferred_theta, out, plan_only):
     soa = poses_to_soa(poses, ik._solver.device)
     ik._upload()
@@ -563,6 +602,12 @@ class DualArmIK:
         angles along every path (index [T, n] int32, theta, joints [T,n,7], step_cost, cost [n] ...)."""
         return _path_batch(self, {"arm": arm_ids}, poses, start_joints, n_theta, thetas, policy, weights, skip_projected, unwind,
                            want_elbow, out, plan_only)
+
+    def reach_map_batch(self, arm_ids: Any, positions: Any, orientations: Any, want: Sequence[str] = HipSolver.REACH_MAP_OUTPUTS,
+                        out: Optional[Dict[str, torch.Tensor]] = None, plan_only: bool = False) -> Dict[str, torch.Tensor]:
+        """SymbolicIK.reach_map_batch for positions of both arms (arm_ids [n_pos] uint8, one byte per POSITION): every position
+        with every orientation, reduced per position (count [n_pos] int32, state_count [n_pos,11], theta_measure, mask)."""
+        return _reach_map_batch(self, {"arm": arm_ids}, positions, orientations, want, out, plan_only)
 
     def theta_from_joints_batch(self, arm_ids: Any, poses: Any, current_joints: Any, preferred_theta: Optional[Sequence[float]] = None,
                                 out: Optional[Dict[str, torch.Tensor]] = None, plan_only: bool = False) -> Dict[str, torch.Tensor]:
