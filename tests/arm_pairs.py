@@ -13,11 +13,11 @@ import io
 
 import numpy as np
 
+from checker_support import CUSTOM_GEOMETRY
 from oracle import oracle as orc
-from test_oracle_golden import CUSTOM_GEOMETRY
 
 DEFAULT = dict(singularity_offset=0.03)
-CUSTOM = CUSTOM_GEOMETRY  # G9: the tip has x / y components, u != f, other shoulder offsets and limits
+CUSTOM = CUSTOM_GEOMETRY  # G9 (tests/checker_support.py): the tip has x / y components, u != f, other shoulder offsets and limits
 ZTIP = dict(  # G20 (must match oracle/gen_golden.py ZTIP_GEOMETRY): other segment lengths and limits, the tip still on z
     ik_parameters={
         "r_shoulder_position": np.array([0.0, -0.2, 0.0]), "r_shoulder_orientation": [-15, 0, 10],

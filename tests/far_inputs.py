@@ -8,6 +8,8 @@ import math
 import mpmath as mp
 import numpy as np
 
+from rotations import euler_to_matrix
+
 DBL_MAX = float(np.finfo(np.float64).max)
 # fast_sincos takes its table row from (int)rint(x * 32 / pi): the integer leaves 32 bits at |x| = 2^31 pi / 32 = 2^26 pi.  The double
 # nearest to that real number is 2^26 fl(pi), which lies BELOW it (fl(pi) < pi): EDGE itself is the last double in range.
@@ -201,21 +203,9 @@ def preferred_theta_goals(per_arm=16):
     return pos, eul, np.tile(np.array([0, 1], dtype=np.uint8), per_arm)
 
 
-def rotation_xyz(eul):
-    """Rz(yaw) Ry(pitch) Rx(roll) for rows of [roll, pitch, yaw] (scipy's from_euler("xyz")), [n,3,3]."""
-    eul = np.asarray(eul, dtype=np.float64)
-    sa, sb, sc = (np.sin(eul[:, k]) for k in range(3))
-    ca, cb, cc = (np.cos(eul[:, k]) for k in range(3))
-    Rm = np.empty((len(eul), 3, 3))
-    Rm[:, 0, 0] = cc * cb; Rm[:, 0, 1] = cc * sb * sa - sc * ca; Rm[:, 0, 2] = cc * sb * ca + sc * sa
-    Rm[:, 1, 0] = sc * cb; Rm[:, 1, 1] = sc * sb * sa + cc * ca; Rm[:, 1, 2] = sc * sb * ca - cc * sa
-    Rm[:, 2, 0] = -sb; Rm[:, 2, 1] = cb * sa; Rm[:, 2, 2] = cb * ca
-    return Rm
-
-
 def goal_matrices(pos, eul):
     """Proper goal matrices [n,4,4]: the rotation of the (ordinary) Euler angles, pos as the translation column."""
     M = np.tile(np.eye(4), (len(pos), 1, 1))
-    M[:, :3, :3] = rotation_xyz(eul)
+    M[:, :3, :3] = euler_to_matrix(eul)
     M[:, :3, 3] = pos
     return M

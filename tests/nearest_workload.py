@@ -6,7 +6,8 @@ the expected value is built from a sweep's outputs (the library's own on the GPU
 d = (a - b + pi) % 2 pi - pi, c = sum_q w_q d_q d_q, the first argmin over the candidates."""
 import numpy as np
 
-from sweep_workload import sweep_poses, sweep_thetas  # noqa: F401  (the poses and theta arrays are the sweep tests')
+from checker_support import reachable_rich
+from sweep_workload import expected_tiled, sweep_poses, sweep_thetas  # noqa: F401  (the poses and theta arrays are the sweep tests')
 
 GAP = 1e-9          # best and second-best cost further apart than this: the device's argmin must be NumPy's
 COST_TOL = 1e-12    # c <= 7 pi^2; about 25 roundings of 1.1e-16 relative give <= 2e-13: a 5 x margin
@@ -74,9 +75,6 @@ def skip_projected_case(orc, n=300, k=4):
     """The inputs of the RSIK_NEAREST_SKIP_PROJECTED tests, steered with the checker: per-pose explicit thetas such that sample 0
     of at least 20 poses projects while a later sample of the same pose does not (`mixed`), and at least one pose projects in
     every sample (`all_projected`).  Returns pos, eul, arm, thetas [k, n], the checker's tiled sweep, and the two row masks."""
-    from sweep_workload import expected_tiled
-    from test_gpu_solver_state import reachable_rich
-
     arm = np.zeros(n, dtype=np.uint8)
     pos, eul = reachable_rich(31, n, arm)
     arms = (orc.Arm("r_arm", 0.03), orc.Arm("l_arm", 0.03))

@@ -9,7 +9,7 @@ path, and `gap` is that minus the optimum."""
 import numpy as np
 
 from nearest_workload import COST_TOL, GAP  # noqa: F401  (nearest's derived per-cost bound, and its gap)
-from test_gpu_solver_state import reachable_rich
+from checker_support import reachable_rich
 
 N_MAIN = 37  # four paths per workgroup: ten workgroups, a ragged last one
 # (T, K, seed, arm): 70 waypoints give the output pass a second, ragged trip of 64; K = 64 uses every lane

@@ -2,8 +2,7 @@
 the checker alone, tests/test_gpu_solve_sweep.py uses it on the GPU).  No test in this file."""
 import numpy as np
 
-from test_gpu_solver_state import reachable_rich
-from test_solver_state_checker import state_workload
+from checker_support import reachable_rich, state_workload
 
 THETA_EXPLICIT, THETA_FRACTION = 1, 2
 POLICY = {"explicit": THETA_EXPLICIT, "fraction": THETA_FRACTION}

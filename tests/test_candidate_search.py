@@ -8,21 +8,10 @@ tests/test_gpu_parity.py (-m gpu); this test pins the ARGUMENT the kernel relies
 import numpy as np
 import pytest
 
+from compare import angle_diff, is_valid_angle
 from oracle import oracle as O
 
 TWO_PI = 2 * np.pi
-
-
-def _angle_diff(a, b):
-    return ((a - b) + np.pi) % TWO_PI - np.pi
-
-
-def _is_valid(angle, i0, i1):  # utils.py:468-474
-    if i0 % TWO_PI == i1 % TWO_PI:
-        return True
-    if i0 < i1:
-        return i0 <= angle <= i1
-    return i0 <= angle or angle <= i1
 
 
 def _elbow_ok(arm, e):  # utils.py:443-465 (effective predicate)
@@ -33,7 +22,7 @@ def _elbow_ok(arm, e):  # utils.py:443-465 (effective predicate)
 
 def candidate_search(arm, sv, i0, i1, nb, pref):
     """(found, theta, fast_ok) as the kernel's per-lane search decides them; None when the shortcut applies."""
-    valid = _is_valid(pref, i0, i1)
+    valid = is_valid_angle(pref, i0, i1)
     if valid and _elbow_ok(arm, sv.get_elbow_position(pref)):
         return None
     pref_free = (not valid) and abs(pref) > np.pi
@@ -81,7 +70,7 @@ def candidate_search(arm, sv, i0, i1, nb, pref):
     for k in cand:
         th = b if k == last else k * step + a
         if _elbow_ok(arm, sv.get_elbow_position(th)):
-            d = abs(_angle_diff(th, pref))
+            d = abs(angle_diff(th, pref))
             if d < best_d or (d == best_d and k < best_k):
                 best_d, best_k = d, k
     theta = None if best_k is None else (b if best_k == last else best_k * step + a)

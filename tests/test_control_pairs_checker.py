@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import control_workload as W
+import theta_workload as TW
 from arm_pairs import (CONTROL_PAIRS, PAIRS, S3, check_blocks, check_control_blocks, checker_arms, control_expectation, packed_blocks,
                        plane_binds, plane_margin, threshold_family, threshold_offset, threshold_offsets)
 from oracle import oracle as orc
@@ -146,8 +147,6 @@ THETA_PAIRS = ("default/custom", "ztip/default", "default@-1.01/ztip@-1.01", "de
 def test_theta_from_joints_inputs(pair):
     """theta_workload's rows at n = 300 on the pair's arms: is_reachable_no_limits accepts every row, both arms hold a third of the
     rows at least, shortcut rows and searched rows both occur, and no comparison of any row's search is a near tie."""
-    from tests import theta_workload as TW
-
     arms = checker_arms(pair)
     pos, eul, arm, cur = TW.theta_workload(TW.SEED + 7, 300, arms=arms)
     ref = TW.checker_batch(None, pos, eul, arm, cur, arms=arms)

@@ -5,12 +5,9 @@ a huge argument, and no row sits on a decision margin."""
 import numpy as np
 
 import far_inputs as F
+from checker_support import default_arms
+from compare import TOL
 from oracle import oracle as orc
-from test_solver_state_checker import TOL
-
-
-def _arms():
-    return orc.Arm("r_arm", F.SINGULARITY_OFFSET), orc.Arm("l_arm", F.SINGULARITY_OFFSET)
 
 
 def test_every_rung_sign_and_slot_is_present():
@@ -70,7 +67,7 @@ def test_reduction_is_the_angle():
 
 def test_wound_rows_are_reachable_and_equal_their_reduced_twins():
     w = F.wound_rows()
-    ar, al = _arms()
+    ar, al = default_arms(F.SINGULARITY_OFFSET)
     th = np.tile(np.array([0.3, -2.0]), len(w["pos"]) // 2)
     for policy, theta_in in ((0, None), (1, th)):
         a = orc.solve_batch(ar, al, w["pos"], w["eul"], arm_id=w["arm"], theta_policy=policy, theta_in=theta_in)
@@ -89,7 +86,7 @@ def test_far_thetas_equal_their_reduced_twins():
     """An explicit theta of any size is the theta it is congruent to (get_joints takes its sine and cosine only)."""
     th, tw, rg = F.far_thetas()
     pos0, eul0 = F.base_poses("r_arm")
-    ar, al = _arms()
+    ar, al = default_arms(F.SINGULARITY_OFFSET)
     k = len(th)
     pos, eul = np.repeat(pos0[:8], k, axis=0), np.repeat(eul0[:8], k, axis=0)
     a = orc.solve_batch(ar, al, pos, eul, theta_policy=1, theta_in=np.tile(th, 8))
@@ -103,7 +100,7 @@ def test_far_positions_are_answered_in_their_row():
     """A position whose squared distance from the shoulder overflows: the norm is infinite, the direction 0 and the goal the
     shoulder itself, which lies behind the backward limit of the default arm; below that it is projected onto the sphere."""
     pos, eul, arm, val, entry = F.far_position_rows()
-    ar, al = _arms()
+    ar, al = default_arms(F.SINGULARITY_OFFSET)
     ref = orc.solve_batch(ar, al, pos, eul, arm_id=arm)
     assert (ref["reachable"] == 0).all() and np.isnan(ref["joints"]).all()
     over = np.abs(val) >= 2e154

@@ -28,12 +28,13 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import scale_inputs as SC
+import theta_workload as W
+from checker_support import load, reachable_rich
+from compare import bits, same_bits
+from gpu_support import T, _eventful_trajectories, abi, last_error, make_control, make_symbolic, ptr, raw_call, soa, torch_mod  # noqa: F401
+from gpu_support import cols as table  # (the tests below call the table of a launch `cols`)
 from sweep_workload import sweep_poses
-from test_gpu_parity import _abi_mod, _eventful_trajectories, load, make_control, make_symbolic, soa, torch_mod  # noqa: F401
-from test_gpu_solver_state import T, last_error, ptr, reachable_rich, same_bits
-from test_solver_state_checker import bits
-from tests import scale_inputs as SC
-from tests import theta_workload as W
 
 pytestmark = pytest.mark.gpu
 
@@ -44,20 +45,6 @@ RUN_SEED = 7126  # trajectories of the continuous run: on the CPU checker 24 of 
 
 
 # ------------------------------------------------------------------------------------------ helpers
-def raw(solver, fn_name, *args):
-    """One entry point of the C ABI on the caller's own buffers (as test_gpu_solve_sweep.raw_sweep): returns the ABI's code."""
-    import torch
-
-    with torch.cuda.device(solver.device):
-        solver._bind_stream()
-        return getattr(solver.lib, fn_name)(solver._h, *args)
-
-
-def table(t, rows):
-    """The ABI's column table of an SoA tensor [rows, n]."""
-    return (C.c_void_p * rows)(*[t[k].data_ptr() for k in range(rows)])
-
-
 def host_doubles(a):
     a = np.ascontiguousarray(a, dtype=np.float64)
     return a, a.ctypes.data_as(C.POINTER(C.c_double))
@@ -142,7 +129,7 @@ def test_solve_outputs_left_out(torch_mod, sym, kind, entry):
     joints, then all but state, under RSIK_THETA_FRACTION and RSIK_THETA_INTERVAL0.  RSIK_THETA_NONE with joints and elbow GIVEN
     leaves them untouched and answers the interval, reachable and state of the fraction launch.  rsik_solve: a NULL
     previous_joints_host is seven zeros."""
-    torch, A, solver, n = torch_mod, _abi_mod(), sym, 321
+    torch, A, solver, n = torch_mod, abi(), sym, 321
     pos, eul, arm = sweep_poses(kind, 900, n)
     p = soa(pos, eul, torch)
     cols = table(p, 6)
@@ -157,8 +144,8 @@ def test_solve_outputs_left_out(torch_mod, sym, kind, entry):
     def launch(policy, theta, drop=(), prev=prev):
         what = f"{entry} {kind} policy {policy} without {drop}"
         o = Outputs(torch, spec, drop)
-        rc = raw(solver, entry, n, cols, ptr(arm_t), arm_uniform, policy, ptr(theta), prev, o.p("joints"), o.p("interval"),
-                 o.p("elbow"), o.p("reachable"), o.p("state"))
+        rc = raw_call(solver, entry, n, cols, ptr(arm_t), arm_uniform, policy, ptr(theta), prev, o.p("joints"), o.p("interval"),
+                      o.p("elbow"), o.p("reachable"), o.p("state"))
         assert rc == A.RSIK_OK, (what, rc, last_error(solver))
         solver.synchronize()
         return o.host(what), what
@@ -197,7 +184,7 @@ def test_control_discrete_outputs_left_out(torch_mod, golden_dir, kind, entry):
     rsik_control_discrete: a NULL current_joints is the previous_sol_host row of each pose's arm."""
     from reachy2_symbolic_ik_amd.control_ik import matrices_to_m12_soa
 
-    torch, A, n = torch_mod, _abi_mod(), 321
+    torch, A, n = torch_mod, abi(), 321
     c = make_control()
     solver = c._solver
     c._upload_arms()
@@ -216,8 +203,8 @@ def test_control_discrete_outputs_left_out(torch_mod, golden_dir, kind, entry):
     def launch(drop=(), current_joints=None):
         what = f"{entry} {kind} without {drop}"
         o = Outputs(torch, spec, drop)
-        rc = raw(solver, entry, n, cols, ptr(arm_t), arm_uniform, 20, PREFERRED_THETA, A.MODE_UNCONSTRAINED, prev,
-                 ptr(current_joints), MAX_ANGLE, o.p("joints"), o.p("reachable"), o.p("state"), o.p("emergency"))
+        rc = raw_call(solver, entry, n, cols, ptr(arm_t), arm_uniform, 20, PREFERRED_THETA, A.MODE_UNCONSTRAINED, prev,
+                      ptr(current_joints), MAX_ANGLE, o.p("joints"), o.p("reachable"), o.p("state"), o.p("emergency"))
         assert rc == A.RSIK_OK, (what, rc, last_error(solver))
         solver.synchronize()
         return o.host(what), what
@@ -257,7 +244,7 @@ def test_control_continuous_step_outputs_and_inputs_left_out(torch_mod, kind):
     step finds them latched), the first with timed_out = 1: reachable and state dropped alone and together — cont_state and the
     joints after every step.  Then one input at a time in its explicit form against the NULL form, the same way: current_pose
     (the goal matrix), timed_out (zeros, steps two and three), current_joints (rows 1-7 of cont_state, transposed)."""
-    torch, A, n = torch_mod, _abi_mod(), 129
+    torch, A, n = torch_mod, abi(), 129
     c = make_control()
     solver = c._solver
     c._upload_arms()
@@ -277,9 +264,9 @@ def test_control_continuous_step_outputs_and_inputs_left_out(torch_mod, kind):
             cp = table(goal, 12) if (s == 0 and "current_pose" in explicit) else None
             cj = st[1:8].t().contiguous() if (s == 0 and "current_joints" in explicit) else None
             o = Outputs(torch, spec, drop)
-            rc = raw(solver, "rsik_control_continuous_step", n, table(goal, 12), cp, ptr(arm_t), arm_uniform, ptr(timed_out),
-                     PREFERRED_THETA, pts, A.MODE_UNCONSTRAINED, 0.01, ptr(cj), MAX_ANGLE, ptr(st), o.p("joints"),
-                     o.p("reachable"), o.p("state"))
+            rc = raw_call(solver, "rsik_control_continuous_step", n, table(goal, 12), cp, ptr(arm_t), arm_uniform, ptr(timed_out),
+                          PREFERRED_THETA, pts, A.MODE_UNCONSTRAINED, 0.01, ptr(cj), MAX_ANGLE, ptr(st), o.p("joints"),
+                          o.p("reachable"), o.p("state"))
             assert rc == A.RSIK_OK, (what, s, rc, last_error(solver))
             solver.synchronize()
             out = o.host(f"{what} step {s}")
@@ -316,7 +303,7 @@ def test_control_continuous_run_outputs_and_inputs_left_out(torch_mod, kind, for
     rsik_control_continuous_last_form reports the form asked for.  The reference run must hold trajectories that latch before the
     last block (the latch fill on entry of a later block), inside it (the fill behind a chunk), and a quarter that never latch.
     Then current_pose (the first goal) and current_joints (rows 1-7 of cont_state, transposed) explicit against NULL."""
-    torch, A, n, n_steps, block = torch_mod, _abi_mod(), 96, 40, 16
+    torch, A, n, n_steps, block = torch_mod, abi(), 96, 40, 16
     c = make_control()
     solver = c._solver
     c._upload_arms()
@@ -333,8 +320,8 @@ def test_control_continuous_run_outputs_and_inputs_left_out(torch_mod, kind, for
         cp = table(traj[0], 12) if "current_pose" in explicit else None
         cj = st[1:8].t().contiguous() if "current_joints" in explicit else None
         o = Outputs(torch, spec, drop)
-        rc = raw(solver, "rsik_control_continuous_run", n, n_steps, ptr(traj), cp, ptr(arm_t), arm_uniform, 1, PREFERRED_THETA, pts,
-                 A.MODE_UNCONSTRAINED, 0.01, ptr(cj), MAX_ANGLE, ptr(st), o.p("joints"), o.p("reachable"), o.p("state"))
+        rc = raw_call(solver, "rsik_control_continuous_run", n, n_steps, ptr(traj), cp, ptr(arm_t), arm_uniform, 1, PREFERRED_THETA, pts,
+                      A.MODE_UNCONSTRAINED, 0.01, ptr(cj), MAX_ANGLE, ptr(st), o.p("joints"), o.p("reachable"), o.p("state"))
         assert rc == A.RSIK_OK, (what, rc, last_error(solver))
         assert solver.continuous_last_form() == want_form, (what, solver.continuous_last_form())
         solver.synchronize()
@@ -372,7 +359,7 @@ def state_rows_inputs(torch, n, seed):
 def test_reach_state_outputs_left_out(torch_mod, sym):
     """n = 129, mixed arms, on rows prefilled with a sentinel: interval, reachable and state dropped alone and together — every
     slot of the solver-state rows (20-23 carry the same results) has the bits of the launch with all three."""
-    torch, A, solver, n = torch_mod, _abi_mod(), sym, 129
+    torch, A, solver, n = torch_mod, abi(), sym, 129
     p, arm, arm_t = state_rows_inputs(torch, n, 930)
     cols = table(p, 6)
     prefill = T(np.tile(1000.0 + np.arange(32.0), (n + GUARD, 1)), torch)
@@ -382,7 +369,7 @@ def test_reach_state_outputs_left_out(torch_mod, sym):
         what = f"rsik_reach_state without {drop}"
         st = prefill.clone()
         o = Outputs(torch, spec, drop)
-        rc = raw(solver, "rsik_reach_state", n, cols, ptr(arm_t), 0, 0, ptr(st), o.p("interval"), o.p("reachable"), o.p("state"))
+        rc = raw_call(solver, "rsik_reach_state", n, cols, ptr(arm_t), 0, 0, ptr(st), o.p("interval"), o.p("reachable"), o.p("state"))
         assert rc == A.RSIK_OK, (what, rc, last_error(solver))
         solver.synchronize()
         out = o.host(what)
@@ -404,7 +391,7 @@ def test_reach_state_outputs_left_out(torch_mod, sym):
 def test_joints_from_state_outputs_left_out(torch_mod, sym):
     """n = 129, mixed arms, rows a reach_state left: joints, elbow and both dropped — the rows (16-19 and 24-30 carry the values)
     and what is kept have the bits of the launch with both.  A NULL previous_joints is zeros."""
-    torch, A, solver, n = torch_mod, _abi_mod(), sym, 129
+    torch, A, solver, n = torch_mod, abi(), sym, 129
     p, arm, arm_t = state_rows_inputs(torch, n, 940)
     reached = solver.new_solver_state(n)
     r = solver.reach_state(p, reached, arm=arm_t)
@@ -417,7 +404,7 @@ def test_joints_from_state_outputs_left_out(torch_mod, sym):
         what = f"rsik_joints_from_state without {drop}"
         st = reached.clone()
         o = Outputs(torch, spec, drop)
-        rc = raw(solver, "rsik_joints_from_state", n, ptr(st), ptr(arm_t), 0, ptr(theta), ptr(prev), o.p("joints"), o.p("elbow"))
+        rc = raw_call(solver, "rsik_joints_from_state", n, ptr(st), ptr(arm_t), 0, ptr(theta), ptr(prev), o.p("joints"), o.p("elbow"))
         assert rc == A.RSIK_OK, (what, rc, last_error(solver))
         solver.synchronize()
         out = o.host(what)
@@ -438,7 +425,7 @@ def test_joints_from_state_outputs_left_out(torch_mod, sym):
 def test_theta_from_joints_outputs_left_out(torch_mod, sym):
     """n = 129 rows of tests/theta_workload.py, mixed arms.  rsik_theta_from_joints: joints, bracket, distance and state dropped alone
     and together; rsik_theta_from_joints_state: bracket dropped — theta, what is kept and the solver-state rows keep their bits."""
-    torch, A, solver, n = torch_mod, _abi_mod(), sym, 129
+    torch, A, solver, n = torch_mod, abi(), sym, 129
     pos, eul, arm, cur = W.theta_workload(950, n)
     p, arm_t, cur_t = soa(pos, eul, torch), T(arm, torch), T(cur, torch)
     cols = table(p, 6)
@@ -448,8 +435,8 @@ def test_theta_from_joints_outputs_left_out(torch_mod, sym):
     def fused(drop=()):
         what = f"rsik_theta_from_joints without {drop}"
         o = Outputs(torch, spec, drop)
-        rc = raw(solver, "rsik_theta_from_joints", n, A.GOAL_POSE6, cols, ptr(arm_t), 0, ptr(cur_t), pref, o.p("theta"), o.p("joints"),
-                 o.p("bracket"), o.p("distance"), o.p("state"))
+        rc = raw_call(solver, "rsik_theta_from_joints", n, A.GOAL_POSE6, cols, ptr(arm_t), 0, ptr(cur_t), pref, o.p("theta"), o.p("joints"),
+                      o.p("bracket"), o.p("distance"), o.p("state"))
         assert rc == A.RSIK_OK, (what, rc, last_error(solver))
         solver.synchronize()
         return o.host(what), what
@@ -469,7 +456,7 @@ def test_theta_from_joints_outputs_left_out(torch_mod, sym):
         what = f"rsik_theta_from_joints_state without {drop}"
         st = reached.clone()
         o = Outputs(torch, spec_state, drop)
-        rc = raw(solver, "rsik_theta_from_joints_state", n, ptr(st), ptr(arm_t), 0, ptr(cur_t), 7, pref, o.p("theta"), o.p("bracket"))
+        rc = raw_call(solver, "rsik_theta_from_joints_state", n, ptr(st), ptr(arm_t), 0, ptr(cur_t), 7, pref, o.p("theta"), o.p("bracket"))
         assert rc == A.RSIK_OK, (what, rc, last_error(solver))
         solver.synchronize()
         out = o.host(what)
@@ -483,7 +470,7 @@ def test_theta_from_joints_outputs_left_out(torch_mod, sym):
 
 def test_forward_kinematics_outputs_left_out(torch_mod, sym):
     """n = 129, mixed arms: position only and rotation only have the bits of the launch with both; both NULL is refused."""
-    torch, A, solver, n = torch_mod, _abi_mod(), sym, 129
+    torch, A, solver, n = torch_mod, abi(), sym, 129
     rng = np.random.default_rng(960)
     joints = T(rng.uniform(-np.pi, np.pi, size=(n, 7)), torch)
     arm_t = T((rng.uniform(size=n) < 0.5).astype(np.uint8), torch)
@@ -492,7 +479,7 @@ def test_forward_kinematics_outputs_left_out(torch_mod, sym):
     def launch(drop=()):
         what = f"rsik_forward_kinematics without {drop}"
         o = Outputs(torch, spec, drop)
-        rc = raw(solver, "rsik_forward_kinematics", n, ptr(joints), ptr(arm_t), 0, o.p("position"), o.p("rotation"))
+        rc = raw_call(solver, "rsik_forward_kinematics", n, ptr(joints), ptr(arm_t), 0, o.p("position"), o.p("rotation"))
         assert rc == A.RSIK_OK, (what, rc, last_error(solver))
         solver.synchronize()
         return o.host(what), what
@@ -502,7 +489,7 @@ def test_forward_kinematics_outputs_left_out(torch_mod, sym):
     for drop in (("rotation",), ("position",)):
         got, what = launch(drop)
         same_outputs(got, full, what)
-    assert raw(solver, "rsik_forward_kinematics", n, ptr(joints), ptr(arm_t), 0, None, None) == A.RSIK_E_INVALID
+    assert raw_call(solver, "rsik_forward_kinematics", n, ptr(joints), ptr(arm_t), 0, None, None) == A.RSIK_E_INVALID
     assert "rsik_forward_kinematics" in last_error(solver), last_error(solver)
     solver.synchronize()
 
@@ -555,14 +542,14 @@ def test_stage_row_strides_and_pinned_host_rows(torch_mod, sym, stage_inputs, op
     output padding — the payload has the bits of the packed call, the padding and the guard rows keep the sentinel; and the same
     padded rows in pinned host memory, read after rsik_sync.  A stride below what the stage reads or writes is refused: nothing
     is written."""
-    torch, A, solver = torch_mod, _abi_mod(), sym
+    torch, A, solver = torch_mod, abi(), sym
     need_in, need_out = A.STAGE_ROW[op]
     golden = stage_inputs[op]
     assert golden.shape[1] == need_in and len(golden) >= 64
     pad_in, pad_out = need_in + 3, need_out + 5
 
     def call(n, src, in_stride, dst, out_stride):
-        return raw(solver, "rsik_stage", op, n, 0, src.data_ptr(), in_stride, dst.data_ptr(), out_stride)
+        return raw_call(solver, "rsik_stage", op, n, 0, src.data_ptr(), in_stride, dst.data_ptr(), out_stride)
 
     for n in (1, 64, 65, 257):
         what = f"stage {op} n {n}"

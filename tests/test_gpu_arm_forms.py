@@ -14,17 +14,15 @@ geometries is pinned to the reference by G9 and G20 (tests/test_oracle_golden.py
 import numpy as np
 import pytest
 
-import test_gpu_solve_nearest as NT
-import test_gpu_solve_path as PT
 from arm_pairs import NON_MIRROR, PAIRS, checker_arms, solve_fractions, upload
+from compare import as_bits, bits, close, joint_error, joints_close, same_bits
+from gpu_support import T, abi, make_symbolic, orc, soa, to_np, torch_mod  # noqa: F401
 from nearest_workload import GAP, N_MAIN, main_case, main_thetas
 from path_workload import MAIN_SHAPES
 from path_workload import N_MAIN as N_PATHS
+from sampling_support import (LANES, check_against_solve, check_nearest, check_path, launches, lib_sweep, main_launches, path_arm_kwargs,
+                              same_nearest_outputs, same_path_outputs, solve_columns)
 from sweep_workload import columns, expected_tiled, sweep_poses, sweep_thetas
-from test_gpu_parity import make_symbolic, orc, soa, to_np, torch_mod  # noqa: F401
-from test_gpu_solve_sweep import check_against_solve, solve_columns
-from test_gpu_solver_state import T, close, joints_close, same_bits
-from test_solver_state_checker import bits
 
 pytestmark = pytest.mark.gpu
 
@@ -33,21 +31,9 @@ OPTIONS = ((0, 0), (0, 1), (1, 0), (1, 1))  # (RSIK_OPT_NO_MIRROR, RSIK_OPT_NO_T
 WRIST_YAW_TOL = 2e-15  # test_tip_z_specialisation_matches_general_path's bound on the one output the tip-on-z stage may round differently
 
 
-def abi():
-    from reachy2_symbolic_ik_amd import _abi
-
-    return _abi
-
-
 def set_options(solver, no_mirror, no_tipz):
     solver.set_option(abi().OPT_NO_MIRROR, no_mirror)
     solver.set_option(abi().OPT_NO_TIPZ, no_tipz)
-
-
-def joint_error(got, want):
-    """Largest |difference| over the rows whose elbow pitch is not 0 (joints_close compares the others through j2 + j6)."""
-    rows = np.abs(want[:, 3]) >= 1e-12
-    return float(np.max(np.abs(got[rows] - want[rows]), initial=0.0))
 
 
 # ------------------------------------------------------------------------------------------ A. non-mirror pairs against the checker
@@ -117,10 +103,10 @@ def test_nearest_on_arm_pairs(torch_mod, pair, k):
             sw = to_np(solver.solve_sweep(p, th, **kw))
             ok = sw["reachable"].astype(bool)
             assert ok[0::2].mean() >= 0.04 and ok[1::2].mean() > 0.5 and ok[arm == 0].sum() >= 100 and ok[arm == 1].sum() >= 100
-            for lanes in NT.LANES:
+            for lanes in LANES:
                 solver.set_option(_abi.OPT_NEAREST_LANES, lanes)
                 got = to_np(solver.solve_nearest(p, th, seedT, **kw))
-                NT.check_nearest(got, sw, seed, f"{pair} K {k} {policy} prev {prev is not None} L {lanes}", need_gap=True)
+                check_nearest(got, sw, seed, f"{pair} K {k} {policy} prev {prev is not None} L {lanes}", need_gap=True)
 
 
 @pytest.mark.parametrize("pair", list(PAIRS))
@@ -131,11 +117,11 @@ def test_path_on_arm_pairs(torch_mod, pair, shape):
     torch = torch_mod
     t, k, seed, _ = shape
     solver = upload(pair)
-    for what, p, th, policy, arm, start in PT.launches(torch, t, k, seed, "mixed"):
+    for what, p, th, policy, arm, start in launches(torch, t, k, seed, "mixed"):
         assert 0 < arm.sum() < N_PATHS
-        sw = PT.lib_sweep(solver, p, th, policy, arm, torch)
+        sw = lib_sweep(solver, p, th, policy, arm, torch)
         got = to_np(solver.solve_path(p, th, None if start is None else T(start, torch), policy=policy, arm=T(arm, torch)))
-        exp = PT.check_path(got, sw, t, N_PATHS, f"{pair} {what}", start, need_gap=True)
+        exp = check_path(got, sw, t, N_PATHS, f"{pair} {what}", start, need_gap=True)
         assert 0 < (~exp["solved"]).sum() and 1 <= exp["solved"].all(axis=0).sum() < N_PATHS, what
 
 
@@ -145,14 +131,14 @@ def nearest_rows_agree(a, b, exp, what):
     bits; index is the same wherever the gap is clear; and where index is the same, theta, elbow, projected and the first six joints
     are the same bits and the wrist yaw agrees within WRIST_YAW_TOL."""
     for key in ("interval", "reachable", "state"):
-        np.testing.assert_array_equal(NT.as_bits(a[key]), NT.as_bits(b[key]), err_msg=f"{what}: {key}")
+        np.testing.assert_array_equal(as_bits(a[key]), as_bits(b[key]), err_msg=f"{what}: {key}")
     np.testing.assert_array_equal(a["index"] == -1, b["index"] == -1, err_msg=what)
     clear = exp["gap"] > GAP
     np.testing.assert_array_equal(a["index"][clear], b["index"][clear], err_msg=what + ": index where the gap is clear")
     same = a["index"] == b["index"]
     assert same.mean() >= 0.95, what  # (what the gap condition, asserted by check_nearest, and the line above imply)
     for key in ("theta", "elbow", "projected"):
-        np.testing.assert_array_equal(NT.as_bits(a[key][same]), NT.as_bits(b[key][same]), err_msg=f"{what}: {key}")
+        np.testing.assert_array_equal(as_bits(a[key][same]), as_bits(b[key][same]), err_msg=f"{what}: {key}")
     same_bits(a["joints"][same][:, :6], b["joints"][same][:, :6], what + ": the first six joints")
     won = same & (a["index"] >= 0)
     err = float(np.max(np.abs(a["joints"][won, 6] - b["joints"][won, 6]), initial=0.0))
@@ -169,21 +155,21 @@ def test_nearest_under_every_option_form(torch_mod, kind, k, with_prev):
     torch = torch_mod
     _abi = abi()
     solver, _, _ = make_symbolic(0.03)
-    for what, p, th, seedT, kw, seed in NT.main_launches(torch, kind, k):
+    for what, p, th, seedT, kw, seed in main_launches(torch, kind, k):
         if (kw["previous_joints"] is not None) != with_prev:
             continue
         outs, exps = {}, {}
         for no_mirror, no_tipz in OPTIONS:
             set_options(solver, no_mirror, no_tipz)
             sw = to_np(solver.solve_sweep(p, th, **kw))
-            for lanes in NT.LANES:
+            for lanes in LANES:
                 solver.set_option(_abi.OPT_NEAREST_LANES, lanes)
                 got = to_np(solver.solve_nearest(p, th, seedT, **kw))
-                exp = NT.check_nearest(got, sw, seed, f"{what} no_mirror {no_mirror} no_tipz {no_tipz} L {lanes}", need_gap=True)
+                exp = check_nearest(got, sw, seed, f"{what} no_mirror {no_mirror} no_tipz {no_tipz} L {lanes}", need_gap=True)
                 outs[no_mirror, no_tipz, lanes], exps[no_mirror, no_tipz] = got, exp
-        for lanes in NT.LANES:
+        for lanes in LANES:
             for no_tipz in (0, 1):
-                NT.same_outputs(outs[1, no_tipz, lanes], outs[0, no_tipz, lanes], f"{what} no_tipz {no_tipz} L {lanes}: NO_MIRROR 1 against 0")
+                same_nearest_outputs(outs[1, no_tipz, lanes], outs[0, no_tipz, lanes], f"{what} no_tipz {no_tipz} L {lanes}: NO_MIRROR 1 against 0")
             for no_mirror in (0, 1):
                 nearest_rows_agree(outs[no_mirror, 0, lanes], outs[no_mirror, 1, lanes], exps[no_mirror, 0],
                                    f"{what} no_mirror {no_mirror} L {lanes}: NO_TIPZ 0 against 1")
@@ -192,14 +178,14 @@ def test_nearest_under_every_option_form(torch_mod, kind, k, with_prev):
 def paths_agree(a, b, exp, what):
     """nearest_rows_agree for two rsik_solve_path launches: per path."""
     for key in ("interval", "reachable", "state", "n_solved"):
-        np.testing.assert_array_equal(PT.as_bits(a[key]), PT.as_bits(b[key]), err_msg=f"{what}: {key}")
+        np.testing.assert_array_equal(as_bits(a[key]), as_bits(b[key]), err_msg=f"{what}: {key}")
     np.testing.assert_array_equal(a["index"] == -1, b["index"] == -1, err_msg=what)
     clear = exp["gap"] > GAP
     np.testing.assert_array_equal(a["index"][:, clear], b["index"][:, clear], err_msg=what + ": index where the gap is clear")
     same = (a["index"] == b["index"]).all(axis=0)
     assert same.any(), what
     for key in ("theta", "elbow", "projected"):
-        np.testing.assert_array_equal(PT.as_bits(a[key][:, same]), PT.as_bits(b[key][:, same]), err_msg=f"{what}: {key}")
+        np.testing.assert_array_equal(as_bits(a[key][:, same]), as_bits(b[key][:, same]), err_msg=f"{what}: {key}")
     same_bits(a["joints"][:, same][..., :6], b["joints"][:, same][..., :6], what + ": the first six joints")
     won = same[None] & (a["index"] >= 0)
     err = float(np.max(np.abs(a["joints"][won][:, 6] - b["joints"][won][:, 6]), initial=0.0))
@@ -213,17 +199,17 @@ def test_path_under_every_option_form(torch_mod, shape):
     torch = torch_mod
     t, k, seed, kind = shape
     solver, _, _ = make_symbolic(0.03)
-    for what, p, th, policy, arm, start in PT.launches(torch, t, k, seed, kind):
+    for what, p, th, policy, arm, start in launches(torch, t, k, seed, kind):
         outs, exps = {}, {}
         for no_mirror, no_tipz in OPTIONS:
             set_options(solver, no_mirror, no_tipz)
-            sw = PT.lib_sweep(solver, p, th, policy, arm, torch)
-            got = to_np(solver.solve_path(p, th, None if start is None else T(start, torch), policy=policy, **PT.arm_kw(arm, torch)))
+            sw = lib_sweep(solver, p, th, policy, arm, torch)
+            got = to_np(solver.solve_path(p, th, None if start is None else T(start, torch), policy=policy, **path_arm_kwargs(arm, torch)))
             need_gap = policy == "fraction" and k > 1 and (t > 1 or start is not None)
-            exps[no_mirror, no_tipz] = PT.check_path(got, sw, t, N_PATHS, f"{what} no_mirror {no_mirror} no_tipz {no_tipz}", start, need_gap=need_gap)
+            exps[no_mirror, no_tipz] = check_path(got, sw, t, N_PATHS, f"{what} no_mirror {no_mirror} no_tipz {no_tipz}", start, need_gap=need_gap)
             outs[no_mirror, no_tipz] = got
         for no_tipz in (0, 1):
-            PT.same_outputs(outs[1, no_tipz], outs[0, no_tipz], f"{what} no_tipz {no_tipz}: NO_MIRROR 1 against 0")
+            same_path_outputs(outs[1, no_tipz], outs[0, no_tipz], f"{what} no_tipz {no_tipz}: NO_MIRROR 1 against 0")
         for no_mirror in (0, 1):
             paths_agree(outs[no_mirror, 0], outs[no_mirror, 1], exps[no_mirror, 0], f"{what} no_mirror {no_mirror}: NO_TIPZ 0 against 1")
 
@@ -241,7 +227,7 @@ def test_form_1_on_a_mirror_pair_gives_the_bits_of_form_2(torch_mod):
     p, armT, seedT = soa(pos, eul, torch), T(arm, torch), T(seed, torch)
     u = T(solve_fractions(k, N_MAIN), torch)
     t, kp, pseed, _ = MAIN_SHAPES[1]
-    path_launches = list(PT.launches(torch, t, kp, pseed, "mixed"))
+    path_launches = list(launches(torch, t, kp, pseed, "mixed"))
 
     def run():
         out = {"solve i0": to_np(solver.solve(p, arm=armT)),
@@ -249,7 +235,7 @@ def test_form_1_on_a_mirror_pair_gives_the_bits_of_form_2(torch_mod):
         for policy in ("fraction", "explicit"):
             th = T(main_thetas(policy, True, k), torch)
             out[f"sweep {policy}"] = to_np(solver.solve_sweep(p, th, policy=policy, arm=armT))
-            for lanes in NT.LANES:
+            for lanes in LANES:
                 solver.set_option(_abi.OPT_NEAREST_LANES, lanes)
                 out[f"nearest {policy} L {lanes}"] = to_np(solver.solve_nearest(p, th, seedT, policy=policy, arm=armT))
         for what, pp, th, policy, parm, start in path_launches:

@@ -19,38 +19,18 @@ import numpy as np
 import pytest
 
 import control_workload as W
+import theta_workload as TW
 from arm_pairs import CONTROL_PAIRS, checker_arms, control_expectation, threshold_family, upload_control
-from test_gpu_parity import CONT_JOINT_TOL, CONT_THETA_TOL, TOL, _same_run, to_np, torch_mod  # noqa: F401
-from test_gpu_previous_rows import bucket_vectors
-from test_gpu_solver_state import T, joints_close
-from test_gpu_theta_from_joints import check_against_checker, goal_tensor
-from test_solver_state_checker import bits
-from tests import theta_workload as TW
+from compare import CONT_JOINT_TOL, CONT_THETA_TOL, TOL, bits, joint_error, joints_close
+from gpu_support import T, _same_run, abi, bucket_vectors, check_against_checker, goal_tensor, m12, to_np, torch_mod  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 FAMILY = list(threshold_family())
 
 
-def abi():
-    from reachy2_symbolic_ik_amd import _abi
-
-    return _abi
-
-
-def m12(M, torch):
-    from reachy2_symbolic_ik_amd.control_ik import matrices_to_m12_soa
-
-    return matrices_to_m12_soa(M, torch.device("cuda", 0))
-
-
-def joint_error(got, want):
-    rows = np.abs(want[:, 3]) >= 1e-12
-    return float(np.max(np.abs(got[rows] - want[rows]), initial=0.0))
-
-
 def previous_rows(seed, n=W.N, buckets=16):
-    """A previous_sol per row as tests/test_gpu_previous_rows.py draws it, from `buckets` vectors (the checker takes one vector per
+    """A previous_sol per row as tests/test_gpu_previous_rows.py draws it (gpu_support.bucket_vectors), from `buckets` vectors (the checker takes one vector per
     call): (rows [n, 7], bucket [n], vectors [buckets, 7])."""
     rng = np.random.default_rng(seed)
     vecs = bucket_vectors(rng, buckets)

@@ -13,24 +13,20 @@ import pytest
 import far_inputs as F
 import theta_workload as W
 from arm_pairs import checker_arms, upload
+from checker_support import CheckerRows
+from compare import CONT_JOINT_TOL, CONT_THETA_TOL, TOL
+from gpu_support import (_bits_equal, _rows_except, abi, check_against_checker, make_control, make_symbolic, orc, soa, to_np,  # noqa: F401
+                         torch_mod)
 from nearest_workload import GAP, nearest_from_sweep, seeds
 from path_workload import path_dp
+from rotations import euler_to_matrix, m12_soa_to_matrices
 from sweep_workload import expected_tiled
-from test_gpu_hostile import _bits_equal, _m12_to_matrices, _rows_except
-from test_gpu_parity import CONT_JOINT_TOL, CONT_THETA_TOL, TOL, make_control, make_symbolic, orc, soa, to_np, torch_mod  # noqa: F401
-from test_gpu_theta_from_joints import check_against_checker
 
 pytestmark = pytest.mark.gpu
 
 # the default pair launches FORM 2 / TIPZ (goal_from_euler_tipz), "default/custom" FORM 1 and the general goal path (rot_from_euler)
 PAIRS = ("default", "default/custom")
 KS = (1, 8)
-
-
-def _abi():
-    from reachy2_symbolic_ik_amd import _abi as A
-
-    return A
 
 
 def _setup(pair, orc):
@@ -101,7 +97,7 @@ def _ordinary_thetas(n, seed):
 def test_wound_angles_solve(torch_mod, orc, pair):
     """rsik_solve (mixed arms, every theta policy's output set), rsik_solve_rows, rsik_reach_state + rsik_joints_from_state: the
     wound rows against the checker (A) and, through the kernel itself, against their reduced twins (B)."""
-    torch, A = torch_mod, _abi()
+    torch, A = torch_mod, abi()
     solver, arms = _setup(pair, orc)
     w = F.wound_rows()
     pos, eul, twin, arm = w["pos"], w["eul"], w["twin_eul"], w["arm"]
@@ -205,7 +201,7 @@ def test_wound_angles_sampling(torch_mod, orc, pair, k):
 @pytest.mark.parametrize("pair", PAIRS)
 def test_wound_angles_theta_from_joints_and_stages(torch_mod, orc, pair):
     """rsik_theta_from_joints with a pose goal, RSIK_STAGE_WRIST_POSITION and RSIK_STAGE_POSE_IN_REACH on the wound rows."""
-    torch, A = torch_mod, _abi()
+    torch, A = torch_mod, abi()
     solver, arms = _setup(pair, orc)
     w = F.wound_rows()
     pos, eul, twin, arm = w["pos"], w["eul"], w["twin_eul"], w["arm"]
@@ -225,7 +221,7 @@ def test_wound_angles_theta_from_joints_and_stages(torch_mod, orc, pair):
         rows = np.flatnonzero(arm == a)
         pose, pose_tw = np.concatenate([pos[rows], eul[rows]], axis=1), np.concatenate([pos[rows], twin[rows]], axis=1)
         tip = arms[a].field("tip_position") * np.array([-1.0, 1.0, 1.0])       # S:418-425
-        want = pos[rows] + np.einsum("nij,j->ni", F.rotation_xyz(twin[rows]), tip)
+        want = pos[rows] + np.einsum("nij,j->ni", euler_to_matrix(twin[rows]), tip)
         wr = solver.stage(A.STAGE_WRIST_POSITION, _T(pose, torch), a).cpu().numpy()
         _close(wr, want, f"{pair} A wrist stage, arm {a}")
         _close(wr, solver.stage(A.STAGE_WRIST_POSITION, _T(pose_tw, torch), a).cpu().numpy(), f"{pair} B wrist stage, arm {a}")
@@ -257,7 +253,7 @@ def _pose_in_reach(arm_c, pos):
 def test_far_and_tiny_positions_solve(torch_mod, orc, pair, rows):
     """The entry points of leg A on positions up to DBL_MAX (the squared distance overflows from 1.34e154 on: the reference's
     norm is inf, its direction 0, the goal the shoulder itself) and down to the smallest denormal."""
-    torch, A = torch_mod, _abi()
+    torch, A = torch_mod, abi()
     solver, arms = _setup(pair, orc)
     pos, eul, arm, val, entry = F.far_position_rows() if rows == "far" else F.tiny_position_rows()
     n = len(pos)
@@ -306,7 +302,7 @@ def test_far_and_tiny_positions_solve(torch_mod, orc, pair, rows):
         np.testing.assert_array_equal(o[:, 4], code)
         _close(o[:, 1:4], gp, f"{pair} C {rows} pose-in-reach stage, arm {a}")
         tip = arms[a].field("tip_position") * np.array([-1.0, 1.0, 1.0])
-        want = pos[m] + np.einsum("nij,j->ni", F.rotation_xyz(eul[m]), tip)
+        want = pos[m] + np.einsum("nij,j->ni", euler_to_matrix(eul[m]), tip)
         wr = solver.stage(A.STAGE_WRIST_POSITION, _T(pose, torch), a).cpu().numpy()
         scale = np.maximum(1.0, np.abs(want))  # (a far position: the wrist is the position to rounding, one ulp of ITS size)
         _close(wr / scale, want / scale, f"{pair} C {rows} wrist stage, arm {a}")
@@ -400,7 +396,7 @@ def test_continuous_run_far_translations(torch_mod, orc):
     torch = torch_mod
     from bench import make_config5_trajectories
 
-    A = _abi()
+    A = abi()
     n_traj, n_steps = 9, 131
     traj = make_config5_trajectories(n_traj, n_steps, seed=123)
     far, cases = _far_trajectories(torch, traj)
@@ -431,8 +427,8 @@ def test_continuous_run_far_translations(torch_mod, orc):
     assert float((torch.nan_to_num(so_["joints"]) - torch.nan_to_num(po["joints"])).abs().max()) <= 1e-9
     a = orc.Arm("r_arm", -1.01)
     cols = sorted(cases)
-    Ms = _m12_to_matrices(far[:, :, torch.as_tensor(cols).cuda()].cpu().numpy())
-    M0 = _m12_to_matrices(traj[:1, :, torch.as_tensor(cols).cuda()].cpu().numpy())[0]
+    Ms = m12_soa_to_matrices(far[:, :, torch.as_tensor(cols).cuda()].cpu().numpy())
+    M0 = m12_soa_to_matrices(traj[:1, :, torch.as_tensor(cols).cuda()].cpu().numpy())[0]
     J, Fl, S = (so_[k].cpu().numpy() for k in ("joints", "reachable", "state"))
     for col, k in enumerate(cols):
         cs = orc.ContinuousState(c.previous_theta["r_arm"], c.previous_sol["r_arm"])
@@ -452,7 +448,7 @@ def test_far_elbow_angles(torch_mod, orc, pair):
     """theta_in of RSIK_THETA_EXPLICIT, the explicit grids of sweep / nearest / path, the theta of the two state entry points and
     the preferred theta of rsik_theta_from_joints at every rung and sign: against the checker, and against the reduced twin
     through the kernel."""
-    torch, A = torch_mod, _abi()
+    torch, A = torch_mod, abi()
     solver, arms = _setup(pair, orc)
     th, tw, rg = F.far_thetas()
     k = len(th)
@@ -548,8 +544,6 @@ def test_far_previous_joints_at_the_exact_singularity(torch_mod, orc):
 
     from reachy2_symbolic_ik_amd import HipSolver, SymbolicIK
     from reachy2_symbolic_ik_amd.constants import default_ik_parameters
-    from test_solver_state_checker import CheckerRows
-
     prm = default_ik_parameters()
     prm["r_shoulder_orientation"] = [0, 0, 0]
     prm["l_shoulder_orientation"] = [0, 0, 0]
@@ -621,7 +615,7 @@ def test_far_preferred_theta_continuous(torch_mod, orc):
     phases wrap angles with a modulo written for bounded values and carry the theta they start from step to step, so these entry
     points answer below 2^27 — as the checker does, step by step — and REFUSE a finite preferred theta from 2^27 up
     (RSIK_E_INVALID: nothing launched, outputs and carried state untouched); never a wrong row."""
-    torch, A = torch_mod, _abi()
+    torch, A = torch_mod, abi()
     from bench import make_config5_trajectories
 
     bound = 2.0 ** 27
@@ -629,7 +623,7 @@ def test_far_preferred_theta_continuous(torch_mod, orc):
     th = np.concatenate([F.far_thetas()[0], [last, -last, bound, -bound]])   # every rung and sign, and both sides of the bound itself
     n_traj, n_steps = 9, 24
     traj = make_config5_trajectories(n_traj, n_steps, seed=123)
-    Ms = _m12_to_matrices(traj.cpu().numpy())           # [steps, n, 4, 4]
+    Ms = m12_soa_to_matrices(traj.cpu().numpy())           # [steps, n, 4, 4]
     a = orc.Arm("r_arm", -1.01)
     c = make_control()
     hs = c._solver
@@ -697,7 +691,7 @@ def test_far_preferred_theta_continuous(torch_mod, orc):
 def test_ordinary_rows_next_to_far_rows_keep_their_bits(torch_mod, orc, pair):
     """A launch that holds far rows among ordinary ones returns, for every ordinary row, the bits of the launch in which the far
     rows held ordinary goals: rsik_solve (explicit theta), rsik_solve_sweep, rsik_solve_nearest, rsik_reach_state."""
-    torch, A = torch_mod, _abi()
+    torch, A = torch_mod, abi()
     solver, arms = _setup(pair, orc)
     w = F.wound_rows()
     n = len(w["pos"])

@@ -9,22 +9,13 @@ tests/golden/g13_hostile.npz and pinned against the checker's convention in test
 import numpy as np
 import pytest
 
-from test_gpu_parity import URDF, make_control, make_symbolic, orc, soa, to_np, torch_mod  # noqa: F401
+from gpu_support import _bits_equal, _rows_except, make_control, make_symbolic, orc, soa, to_np, torch_mod  # noqa: F401
+from rotations import m12_soa_to_matrices
 
 pytestmark = pytest.mark.gpu
 
 INVALID = 10
 POISONS = (float("nan"), float("inf"), float("-inf"))
-
-
-def _bits_equal(torch, a, b):
-    return torch.equal(a.contiguous().view(torch.uint8), b.contiguous().view(torch.uint8))
-
-
-def _rows_except(torch, n, rows):
-    keep = torch.ones(n, dtype=torch.bool, device="cuda")
-    keep[torch.as_tensor(rows, device="cuda")] = False
-    return keep
 
 
 def test_solve_rows_that_are_not_numbers(torch_mod, orc, golden_dir):
@@ -153,15 +144,6 @@ def _poisoned_trajectories(torch, traj):
     return t, {k: sorted(set(v)) for k, v in cases.items()}
 
 
-def _m12_to_matrices(m12):
-    """[n_steps, 12, k] -> [n_steps, k, 4, 4]"""
-    s, _, k = m12.shape
-    Ms = np.tile(np.eye(4), (s, k, 1, 1))
-    Ms[:, :, :3, :3] = np.moveaxis(m12[:, :9, :], 1, 2).reshape(s, k, 3, 3)
-    Ms[:, :, :3, 3] = np.moveaxis(m12[:, 9:, :], 1, 2)
-    return Ms
-
-
 @pytest.mark.parametrize("n_traj,n_steps", [(300, 200), (9, 131), (1, 64)])
 def test_continuous_run_goals_that_are_not_numbers(torch_mod, orc, n_traj, n_steps):
     """rsik_control_continuous_run, every form (the step kernel launch by launch, the phased pipeline with its edge kinds and
@@ -211,7 +193,7 @@ def test_continuous_run_goals_that_are_not_numbers(torch_mod, orc, n_traj, n_ste
     # ... and with the checker, step by step
     a = orc.Arm("r_arm", -1.01)
     cols = sorted(cases)
-    Ms = _m12_to_matrices(bad[:, :, torch.as_tensor(cols).cuda()].cpu().numpy())
+    Ms = m12_soa_to_matrices(bad[:, :, torch.as_tensor(cols).cuda()].cpu().numpy())
     J, F, S = (ref_o[k].cpu().numpy() for k in ("joints", "reachable", "state"))
     for col, k in enumerate(cols):
         cs = orc.ContinuousState(c.previous_theta["r_arm"], c.previous_sol["r_arm"])
@@ -236,7 +218,7 @@ def test_continuous_step_goal_that_is_not_a_number(torch_mod, orc):
 
     n, steps = 200, 12
     traj = make_config5_trajectories(n, steps, seed=31)
-    Ms = _m12_to_matrices(traj.cpu().numpy())           # [steps, n, 4, 4]
+    Ms = m12_soa_to_matrices(traj.cpu().numpy())           # [steps, n, 4, 4]
     bad = Ms.copy()
     bad[5, 17, 1, 3] = np.nan
     bad[0, 80, 0, 0] = np.inf

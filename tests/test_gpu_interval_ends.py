@@ -19,30 +19,23 @@ import functools
 import numpy as np
 import pytest
 
-TOL = 1e-9          # tests/test_gpu_parity.py
+from checker_support import default_arms
+from compare import TOL
+from oracle import oracle as orc
+
 TIGHT_TOL = 1e-7    # tests/test_gpu_parity.py: interval ends next to tangency (d angle ~ d disc / (2 sqrt(disc)))
 ARMS = ("r_arm", "l_arm")
 
 
-def _orc():
-    from oracle import oracle as o
-
-    return o
-
-
-def _checker_arms(o):
-    return o.Arm("r_arm", 0.03), o.Arm("l_arm", 0.03)
-
-
 def _solve(o, arm, P, E, **kw):
-    ar, al = _checker_arms(o)
+    ar, al = default_arms()
     aid = np.full(len(P), ARMS.index(arm), dtype=np.uint8)
     return o.solve_batch(ar, al, P, E, arm_id=aid, **kw)
 
 
 def measure(o, arm, P, E):
     """(R'^2, disc, reachable, state, interval) per row, from the checker alone."""
-    A = _checker_arms(o)[ARMS.index(arm)]
+    A = default_arms()[ARMS.index(arm)]
     sv = o.Solver(A)
     n = len(P)
     R2, disc, ok, st, itv = np.empty(n), np.empty(n), np.empty(n, bool), np.empty(n, int), np.empty((n, 2))
@@ -115,7 +108,7 @@ def _rotation_taking(a, b, roll):
 
 def parallel_family(o, arm, n=2500, seed=9):
     rng = np.random.default_rng(seed + ARMS.index(arm))
-    A = _checker_arms(o)[ARMS.index(arm)]
+    A = default_arms()[ARMS.index(arm)]
     s = A.field("shoulder_position")
     tip = A.field("tip_position")
     tl = np.array([-tip[0], tip[1], tip[2]])  # the wrist seen from the goal frame (symbolic_ik.py:418-425)
@@ -142,14 +135,14 @@ def parallel_family(o, arm, n=2500, seed=9):
 
 @functools.lru_cache(maxsize=None)
 def constructed(arm):
-    o = _orc()
+    o = orc
     return tangent_family(o, arm), parallel_family(o, arm)
 
 
 @pytest.mark.parametrize("arm", ARMS)
 def test_constructed_poses_sit_next_to_the_guard(arm):
     """CPU, checker alone: every constructed row is reachable and its R'^2 / disc lies in the range its family is named for."""
-    o = _orc()
+    o = orc
     (Pt, Et, R2t, dt), (Pp, Ep, R2p, dp) = constructed(arm)
     print(f"{arm}: tangent rows {len(Pt)} (disc {dt.min():.2e} ... {dt.max():.2e}, R'^2 >= {R2t.min():.2e}), "
           f"parallel rows {len(Pp)} (R'^2 {R2p.min():.2e} ... {R2p.max():.2e})")
@@ -178,7 +171,7 @@ def test_interval_ends_next_to_the_guard_match_the_checker(arm):
     from reachy2_symbolic_ik_amd import HipSolver, SymbolicIK
 
     assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    o = _orc()
+    o = orc
     with contextlib.redirect_stdout(io.StringIO()):
         ik = SymbolicIK(arm, singularity_offset=0.03, solver=HipSolver(0))
     for family, (P, E, _, _) in zip(("tangent", "parallel"), constructed(arm)):

@@ -21,7 +21,7 @@ import mpmath
 import numpy as np
 import pytest
 
-from test_gpu_parity import torch_mod  # noqa: F401
+from gpu_support import torch_mod  # noqa: F401
 
 MP = mpmath.mp.clone()
 MP.dps = 50

@@ -13,7 +13,7 @@ import io
 import numpy as np
 import pytest
 
-from test_gpu_parity import _abi_mod, _same_run, make_control, torch_mod  # noqa: F401
+from gpu_support import _same_run, abi, make_control, torch_mod  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -54,7 +54,7 @@ def test_overlapping_runs_are_the_serial_runs(torch_mod, n_traj, n_steps, block,
     from bench import make_config5_trajectories
 
     torch = torch_mod
-    A = _abi_mod()
+    A = abi()
     K = 5
     # one long eventful trajectory batch: the "continue" protocol walks it chunk by chunk, the "reset" protocol repeats its first chunk
     whole = _eventful(torch, make_config5_trajectories(n_traj, n_steps * K, seed=600 + n_traj), every=5, at=0.3 / K + 0.5)
@@ -100,7 +100,7 @@ def test_overlap_only_behind_a_run_of_the_same_shape(torch_mod):
     from bench import make_config5_trajectories
 
     torch = torch_mod
-    A = _abi_mod()
+    A = abi()
     c = make_control()
     hs = c._solver
     hs.set_option(A.OPT_CONT_GOALS_RESIDENT, 1)
@@ -174,7 +174,7 @@ def test_streamed_chunks_of_a_long_trajectory(torch_mod):
         outs.append(res)
         forms.append(res.run_form)
     torch.cuda.synchronize()
-    A = _abi_mod()
+    A = abi()
     assert forms[0] == A.CONT_FORM_PHASED and all(f == A.CONT_FORM_PHASED_OVERLAPPED for f in forms[1:]), forms
     got = {k: torch.cat([o[k] for o in outs], dim=0) for k in ("joints", "reachable", "state")}
     got["cont_state"] = st[:11].clone()
@@ -193,7 +193,7 @@ def test_last_form_says_when_a_run_fell_back_to_a_launch_per_step(torch_mod):
     from reachy2_symbolic_ik_amd import SymbolicIK
 
     torch = torch_mod
-    A = _abi_mod()
+    A = abi()
     n_traj, n_steps = 200, 64
     traj = make_config5_trajectories(n_traj, n_steps, seed=5150)
     c = make_control()
@@ -234,7 +234,7 @@ def test_run_numbers_start_over_before_they_wrap(torch_mod, tmp_path):
     import sys
 
     torch = torch_mod
-    A = _abi_mod()
+    A = abi()
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     sys.path.insert(0, root)
     from reachy2_symbolic_ik_amd import build as B

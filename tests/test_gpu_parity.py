@@ -9,63 +9,15 @@ import os
 import numpy as np
 import pytest
 
+import scale_inputs as SC
+from checker_support import CUSTOM_GEOMETRY, _check_scale_continuous, _check_scale_set, load
+from compare import CONT_JOINT_TOL, CONT_THETA_TOL, NORTH_STAR_TOL, TOL, singular_rows
+from fk_numpy import forward_kinematics
+from gpu_support import URDF, _eventful_trajectories, _same_run, abi, make_control, make_symbolic, orc, soa, to_np, torch_mod  # noqa: F401
+from rotations import euler_to_matrix
+
 pytestmark = pytest.mark.gpu
 
-TOL = 1e-9          # asserted (north-star bar: 1e-6 rad)
-NORTH_STAR_TOL = 1e-6
-CONT_JOINT_TOL = 1e-7   # continuous control step by step: joints
-CONT_THETA_TOL = 1e-9   # continuous control step by step: the carried theta
-URDF = "config_files/reachy2_ik_minimal.urdf"
-
-
-@pytest.fixture(scope="module")
-def torch_mod():
-    import torch
-
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch
-
-
-@pytest.fixture(scope="module")
-def orc():
-    from oracle import oracle as o
-
-    return o
-
-
-def _abi_mod():
-    from reachy2_symbolic_ik_amd import _abi
-
-    return _abi
-
-
-def load(golden_dir, name):
-    return np.load(os.path.join(golden_dir, name))
-
-
-def make_symbolic(so):
-    import contextlib
-    import io
-
-    from reachy2_symbolic_ik_amd import HipSolver, SymbolicIK
-
-    solver = HipSolver(0)
-    with contextlib.redirect_stdout(io.StringIO()):
-        r = SymbolicIK("r_arm", singularity_offset=so, solver=solver)
-        l = SymbolicIK("l_arm", singularity_offset=so, solver=solver)
-    return solver, r, l
-
-
-def soa(pos, eul, torch):
-    return torch.as_tensor(np.ascontiguousarray(np.concatenate([pos.T, eul.T], axis=0))).cuda()
-
-
-def to_np(res):
-    return {k: v.cpu().numpy() for k, v in res.items()}
-
-
-def singular_rows(j):
-    return np.abs(j[:, 3]) < 1e-12
 
 
 def check_symbolic(res, g, prefix, tol=TOL):
@@ -79,7 +31,7 @@ def check_symbolic(res, g, prefix, tol=TOL):
         mm = m & ~sing if k == "joints" else m
         err = np.max(np.abs(res[k][mm] - g[prefix + k][mm])) if mm.any() else 0.0
         assert err < tol, f"{prefix}{k}: max err {err}"
-    if sing.any():  # fully extended arm: only j2 + j6 is defined (see tests/test_oracle_golden.py)
+    if sing.any():  # fully extended arm: only j2 + j6 is defined (see compare.singular_rows)
         a, b = res["joints"][sing], g[prefix + "joints"][sing]
         assert np.max(np.abs(a[:, [0, 1, 3, 4, 5]] - b[:, [0, 1, 3, 4, 5]])) < tol
         dsum = (a[:, 2] + a[:, 6]) - (b[:, 2] + b[:, 6])  # defined modulo 2 pi only (elbow yaw is not wrapped, Q3)
@@ -292,16 +244,6 @@ def test_helpers_elbow_and_no_limits(golden_dir, torch_mod):
 MODES = {"u20": (20, "unconstrained"), "u64": (64, "unconstrained"), "l20": (20, "low_elbow"), "l64": (64, "low_elbow")}
 
 
-def make_control(is_dvt=False):
-    import contextlib
-    import io
-
-    from reachy2_symbolic_ik_amd import ControlIK
-
-    with contextlib.redirect_stdout(io.StringIO()):
-        return ControlIK(urdf_path=URDF, is_dvt=is_dvt)
-
-
 def test_control_catalogue_mixed(golden_dir, torch_mod):
     g = load(golden_dir, "g1_catalogue.npz")
     c = make_control()
@@ -373,7 +315,7 @@ def test_control_grid_sizes_match_checker(golden_dir, torch_mod, orc, nb, mode):
     points, the arc-end candidates above) must all reproduce the reference's first strict minimum."""
     g = load(golden_dir, "g4_control_discrete.npz")
     c = make_control()
-    c._solver.set_option(_abi_mod().OPT_SWEEP_MODE, mode)
+    c._solver.set_option(abi().OPT_SWEEP_MODE, mode)
     c.nb_search_points = nb
     ar, al = orc.Arm("r_arm", -1.01), orc.Arm("l_arm", -1.01)
     M = np.concatenate([g["std_r_arm_M"][900:1300], g["std_l_arm_M"][900:1300]])
@@ -407,13 +349,13 @@ def test_control_candidate_search_any_preferred_theta(golden_dir, torch_mod, orc
         c.nb_search_points = nb
         ref = orc.control_discrete_batch(ar, al, M, arm_id=arm, nb_search_points=nb, preferred_theta=pref)
         for mode in (2, 0):
-            c._solver.set_option(_abi_mod().OPT_SWEEP_MODE, mode)
+            c._solver.set_option(abi().OPT_SWEEP_MODE, mode)
             res = to_np(c.symbolic_inverse_kinematics_batch(arm_t, M, preferred_theta=pref))
             np.testing.assert_array_equal(res["reachable"], ref["reachable"], err_msg=f"pref {pref} nb {nb} mode {mode}")
             np.testing.assert_array_equal(res["state"], ref["state"], err_msg=f"pref {pref} nb {nb} mode {mode}")
             assert np.max(np.abs(res["joints"] - ref["joints"])) < TOL, (pref, nb, mode)
         searched += int(ref["reachable"].sum())
-    c._solver.set_option(_abi_mod().OPT_SWEEP_MODE, 0)
+    c._solver.set_option(abi().OPT_SWEEP_MODE, 0)
     assert searched > 1000, searched
 
 
@@ -425,7 +367,7 @@ def test_config3_full_size_against_checker(torch_mod, orc, mode):
 
     M = make_config3_matrices(1 << 18, seed=20250204)
     c = make_control()
-    c._solver.set_option(_abi_mod().OPT_SWEEP_MODE, mode)
+    c._solver.set_option(abi().OPT_SWEEP_MODE, mode)
     c.nb_search_points = 64
     res = to_np(c.symbolic_inverse_kinematics_batch("r_arm", M))
     ref = orc.control_discrete_batch(orc.Arm("r_arm", -1.01), orc.Arm("l_arm", -1.01), M, nb_search_points=64,
@@ -444,9 +386,6 @@ def test_scale_digests_of_the_reference(golden_dir, torch_mod):
     filter looked at, and over config 3's 256 Ki goal matrices through ControlIK discrete (64-point grid), plus every 64th row's
     interval and joints (oracle/gen_golden.py gen_scale; tests/scale_inputs.py regenerates the inputs from their seeds and proves
     it by their digest).  Flags and state codes bit-exact at 8.6 M poses, joints <= 1e-9 on the subsample."""
-    from tests import scale_inputs as SC
-    from tests.test_oracle_golden import _check_scale_set
-
     g = load(golden_dir, "g14_scale.npz")
     _, r, l = make_symbolic(0.03)
     for arm, ik in (("r_arm", r), ("l_arm", l)):
@@ -493,7 +432,7 @@ def test_stage_entry_points_against_reference(golden_dir, torch_mod):
     """rsik_stage: the stages of is_reachable on explicit operands, batched, against what the reference's own public methods returned
     for the same operands chained the way its harness chains them (G15; src/benchmark/ik_benchmarks.py:36-130): outcomes (found / not,
     how many points, empty or not) exact, numbers to 1e-9."""
-    A = _abi_mod()
+    A = abi()
     g = load(golden_dir, "g15_stages.npz")
     hs, r, l = make_symbolic(0.03)
     T = lambda a: torch_mod.as_tensor(np.ascontiguousarray(a, dtype=np.float64)).cuda()  # noqa: E731
@@ -800,7 +739,7 @@ def test_control_continuous_every_mode_trajectory_run(golden_dir, torch_mod, run
     step-per-launch form, against the vectors recorded from the reference — every mode, rate limit and preferred-theta
     argument, both arms, DVT and not.  Flags / states exact, joints <= 1e-7, carried theta at the end <= 1e-9."""
     g = load(golden_dir, "g12_control_continuous_modes.npz")
-    A = _abi_mod()
+    A = abi()
     names = ["unconstrained", "low_elbow"]
     ctrl = {False: make_control(False), True: make_control(True)}
     snapped = 0
@@ -842,7 +781,7 @@ def test_control_continuous_deliberate_crash(golden_dir, torch_mod, monkeypatch)
     from scipy.spatial.transform import Rotation as R
 
     g = load(golden_dir, "g12_control_continuous_modes.npz")
-    A = _abi_mod()
+    A = abi()
 
     class Clock:
         t = 1000.0
@@ -1073,26 +1012,6 @@ def test_two_threads_two_contexts(torch_mod, orc):
     np.testing.assert_array_equal(jobs[0]["got"]["state"][:2000].cpu().numpy(), ref["state"])
 
 
-def _same_run(torch, ref, got, tag, joint_tol=1e-9):
-    """Two runs of the same trajectories (pipeline vs step kernel, or two block sizes of the pipeline): flags, state codes,
-    the carried theta (row 0 of the trajectory state) and its flag rows bit for bit; joints and previous_sol to
-    `joint_tol`.  (The pipeline's joints phase writes a quiet step as raw joint + whole turns instead of previous +
-    angle_diff(raw, previous) and rebuilds the goal rotation's third row from the other two: both within the last bit of
-    their inputs, no accumulation — but where the arm is stretched out the elbow-yaw / wrist-yaw split amplifies a last bit
-    2e4 times and more (see test_control_continuous_golden_default_start; 1.2e-10 over 32 M eventful trajectory-steps,
-    scripts/soak_pipeline.py), hence 1e-9 and not 1e-14.)"""
-    for k in ref:
-        a, b = ref[k], got[k]
-        if k == "joints":
-            assert float((a - b).abs().max()) <= joint_tol, (tag, k, float((a - b).abs().max()))
-        elif k == "cont_state":
-            assert torch.equal(a[0].view(torch.uint8), b[0].view(torch.uint8)), (tag, "previous_theta")
-            assert float((a[1:8] - b[1:8]).abs().max()) <= joint_tol, (tag, "previous_sol")
-            assert torch.equal(a[8:11], b[8:11]), (tag, "init / emergency / has_previous_sol")
-        else:
-            assert torch.equal(a.view(torch.uint8), b.view(torch.uint8)), (tag, k)
-
-
 @pytest.mark.parametrize("n_traj,n_steps", [(1, 300), (2, 77), (7, 129), (65, 33), (4099, 40)])
 def test_continuous_pipeline_odd_batch_shapes(torch_mod, n_traj, n_steps):
     """The pipeline's sequential phases address their arrays as (buffer, row, lane) and run single-wave workgroups: a
@@ -1100,7 +1019,7 @@ def test_continuous_pipeline_odd_batch_shapes(torch_mod, n_traj, n_steps):
     kernel (flags, states and the carried theta bit for bit, joints to 1e-12: _same_run)."""
     from bench import make_config5_trajectories
 
-    A = _abi_mod()
+    A = abi()
     traj = make_config5_trajectories(n_traj, n_steps, seed=1000 + n_traj)
     c = make_control()
     ref = None
@@ -1125,7 +1044,7 @@ def test_continuous_pipeline_every_short_length(torch_mod):
     as one block, and every length from 49 to 130 cut into blocks of 48, against one launch of the step kernel per step."""
     from bench import make_config5_trajectories
 
-    A = _abi_mod()
+    A = abi()
     n_traj = 72
     traj_all = make_config5_trajectories(n_traj, 130, seed=4242)
     c = make_control()
@@ -1160,7 +1079,7 @@ def test_continuous_pipeline_theta_step_per_interval_kind(torch_mod, arm, mode, 
     arm x constrained mode, also with a rate limit large enough for theta to cross the gap's middle in one step."""
     from bench import make_config5_trajectories
 
-    A = _abi_mod()
+    A = abi()
     n_traj, n_steps = 520, 150
     traj = make_config5_trajectories(n_traj, n_steps, seed=7 + len(arm) + len(mode))
     if arm == "l_arm":  # the left arm's side of the workspace: y -> -y (rows 0-8 are the rotation, 9-11 x y z)
@@ -1191,7 +1110,7 @@ def test_continuous_run_equals_stepwise(golden_dir, torch_mod, run_mode):
     one launch per step ("steps", what chip-filling batches get)."""
     g = load(golden_dir, "g7_control_continuous_start.npz")
     c = make_control()
-    A = _abi_mod()
+    A = abi()
     c._solver.set_option(A.OPT_CONT_RUN_MODE, {"loop": A.CONT_RUN_PHASED, "steps": A.CONT_RUN_STEPS}[run_mode])
     for arm in ("r_arm", "l_arm"):
         sel = ~g[f"{arm}_is_dvt"].astype(bool)
@@ -1225,7 +1144,7 @@ def test_continuous_pipeline_block_sizes_agree(torch_mod):
     equal to one launch of the step kernel per control step."""
     from bench import make_config5_trajectories
 
-    A = _abi_mod()
+    A = abi()
     n_traj, n_steps = 300, 131
     traj = make_config5_trajectories(n_traj, n_steps, seed=99)
     c = make_control()
@@ -1256,7 +1175,7 @@ def test_continuous_pipeline_takes_slightly_skewed_matrices_as_they_are(torch_mo
     pipeline forms and the step kernel agree to 1e-9 (where the arm is stretched out a rebuilt row would differ by more)."""
     from bench import make_config5_trajectories
 
-    A = _abi_mod()
+    A = abi()
     n_traj, n_steps = 500, 96
     traj = make_config5_trajectories(n_traj, n_steps, seed=4242).clone()
     g = torch_mod.Generator(device="cpu").manual_seed(5)
@@ -1287,7 +1206,7 @@ def test_continuous_pipeline_through_gimbal_lock(torch_mod):
     every step of every trajectory sits 0 ... 2e-5 rad from the lock (both sides, the lock itself included), so a branch
     that ran ahead of the table's staging, or derived another rotation than the prepare phase, shows: pipeline forms against the
     step kernel, flags / states / carried theta bit for bit, joints to 1e-9."""
-    A = _abi_mod()
+    A = abi()
     n_traj, n_steps = 777, 160
     dev = torch_mod.device("cuda", 0)
     g = torch_mod.Generator(device="cpu").manual_seed(99)
@@ -1325,35 +1244,6 @@ def test_continuous_pipeline_through_gimbal_lock(torch_mod):
     hs.set_option(A.OPT_CONT_BLOCK_STEPS, 0)
 
 
-def _eventful_trajectories(torch, n_traj, n_steps, seed, arm):
-    """[n_steps, 12, n_traj] goal matrices: config 5's sinusoids plus, per trajectory, one of: a jump of the goal, a winding
-    wrist (reaches the +-6 pi limit), a stretch far out of reach, a run of exact repeats ("stay" steps) — what makes the
-    sequential phases take their rare paths (scripts/soak_pipeline.py's generator, smaller)."""
-    dev = torch.device("cuda", 0)
-    g = torch.Generator(device="cpu").manual_seed(seed)
-    r = lambda *sh: torch.rand(*sh, generator=g, dtype=torch.float64).to(dev)  # noqa: E731
-    k = torch.arange(n_steps, dtype=torch.float64, device=dev)[:, None]
-    t = k / 60.0 + 11.0 + r(n_traj)[None, :] * 40.0
-    c0 = [0.45, -0.2 if arm == "r_arm" else 0.2, -0.1, 0.0, -np.pi / 2, 0.0]
-    amp = [0.3, 0.3, 0.3, np.pi / 4, np.pi / 4, np.pi / 4]
-    freq = [0.6, 0.34, 0.78, 0.18, 0.31, 0.47]
-    v = [c + a * torch.sin(f * t) for c, a, f in zip(c0, amp, freq)]
-    kind = (r(n_traj) * 6).floor()
-    at = (r(n_traj) * max(n_steps - 20, 1) + 5).floor()
-    after = (k >= at[None, :]).double()
-    v[0] = v[0] + after * (kind < 2).double()[None, :] * 0.25 * (r(n_traj)[None, :] - 0.5)
-    v[5] = v[5] + (kind == 2).double()[None, :] * k * 0.12 + (kind == 3).double()[None, :] * k * -0.2
-    far = ((k >= at[None, :]) & (k < at[None, :] + 25)).double() * (kind == 4).double()[None, :]
-    v[0] = v[0] + far * 2.0
-    hold = ((k >= at[None, :]) & (k < at[None, :] + 6)).double() * (kind == 5).double()[None, :]
-    idx = torch.where(hold.bool(), at[None, :].expand(n_steps, -1), k.expand(-1, n_traj)).long().clamp(max=n_steps - 1)
-    v = [torch.gather(x, 0, idx) for x in v]
-    ca, sa, cb, sb, cc, sc = torch.cos(v[3]), torch.sin(v[3]), torch.cos(v[4]), torch.sin(v[4]), torch.cos(v[5]), torch.sin(v[5])
-    rows = [cc * cb, cc * sb * sa - sc * ca, cc * sb * ca + sc * sa, sc * cb, sc * sb * sa + cc * ca, sc * sb * ca - cc * sa,
-            -sb, cb * sa, cb * ca, v[0], v[1], v[2]]
-    return torch.stack(rows, dim=1).contiguous()
-
-
 @pytest.mark.parametrize("n_traj,n_steps,arm,mode,dmax", [(1, 300, "r_arm", "unconstrained", 0.01), (7, 129, "l_arm", "low_elbow", 0.3),
                                                          (65, 33, "r_arm", "low_elbow", 0.01), (600, 203, "l_arm", "unconstrained", 0.3),
                                                          (4099, 40, "r_arm", "unconstrained", 0.01)])
@@ -1368,7 +1258,7 @@ def test_continuous_run_forms_are_bit_identical(torch_mod, n_traj, n_steps, arm,
     workspace slot before — a hint that saves the chain phase its atomic adds on trajectories that have wound up (long runs: -5 ... -9 %)
     — and a quiet step's value is then raw + turns x 2 pi in ONE rounding instead of two: flags, states, the carried theta and the
     latch are still the same bits, joints and previous_sol the same to 1e-12 (observed: 2 ulp)."""
-    A = _abi_mod()
+    A = abi()
     traj = _eventful_trajectories(torch_mod, n_traj, n_steps, 7000 + n_traj, arm)
     c = make_control()
     hs = c._solver
@@ -1414,7 +1304,7 @@ def test_continuous_run_outgrows_its_workspace_without_stopping_the_device(torch
     hipDeviceSynchronize inside an asynchronous API): what is outgrown is parked and freed by rsik_sync.  Every run against the step kernel."""
     from bench import make_config5_trajectories
 
-    A = _abi_mod()
+    A = abi()
     c = make_control()
     hs = c._solver
     sizes = [(8, 40), (300, 100), (64, 17), (2000, 230), (9, 300)]
@@ -1446,7 +1336,7 @@ def test_continuous_run_that_begins_latched(torch_mod, timed_out):
     pipeline fills their steps in without walking them (the chain phase's fill_rest writes the previous_sol rows of a block on entry, stores only);
     every output and the carried state against the step kernel, launch per step; the latched trajectories' rows are previous_sol
     bit for bit and their state rows are untouched, whether or not the caller says its first step timed out."""
-    A = _abi_mod()
+    A = abi()
     n_traj, n_steps = 300, 120
     c = make_control()
     hs = c._solver
@@ -1524,7 +1414,7 @@ def test_config5_full_size_against_checker(torch_mod, orc, mode, d_theta_max, pr
         for i in range(n_steps):
             j, ok, code = orc.control_continuous_step(a, cs, Ms[i], timed_out=(i == 0), preferred_theta_arg=preferred,
                                                       preferred_theta_self=c.preferred_theta["r_arm"],
-                                                      constrained_mode=_abi_mod().MODES[mode],
+                                                      constrained_mode=abi().MODES[mode],
                                                       current_joints=cs.previous_sol, current_pose=Ms[0], d_theta_max=d_theta_max)
             assert ok == bool(F[i, k]) and code == S[i, k], (k, i)
             worst = max(worst, float(np.max(np.abs(j - J[i, k]))))
@@ -1552,16 +1442,13 @@ def test_scale_continuous_digests_of_the_reference(golden_dir, torch_mod):
     the build container (oracle/gen_golden.py gen_scale_continuous), digests of the `reachable` and `state` arrays, sixteen
     trajectories' joints and the carried theta.  The trajectory pipeline over the regenerated matrices (tests/scale_inputs.py): flags
     and state codes bit-exact at half a million control steps, joints <= 1e-7, theta <= 1e-9 — no checker in between."""
-    from tests import scale_inputs as SC
-    from tests.test_oracle_golden import _check_scale_continuous
-
     g = load(golden_dir, "g16_scale_continuous.npz")
     M = SC.config5_trajectories()
     assert SC.sha256(M) == str(g["input_sha256"]), "the seeded inputs did not regenerate"
     n_steps, n_traj = M.shape[:2]
     c = make_control()
-    for run_mode in (_abi_mod().CONT_RUN_PHASED, _abi_mod().CONT_RUN_STEPS):
-        c._solver.set_option(_abi_mod().OPT_CONT_RUN_MODE, run_mode)
+    for run_mode in (abi().CONT_RUN_PHASED, abi().CONT_RUN_STEPS):
+        c._solver.set_option(abi().OPT_CONT_RUN_MODE, run_mode)
         st = c.new_continuous_state("r_arm", n_traj)
         Mt = torch_mod.as_tensor(M).cuda()
         start = np.tile(np.asarray(c.previous_pose["r_arm"], dtype=np.float64), (n_traj, 1, 1))  # (a fresh ControlIK's previous_pose)
@@ -1569,7 +1456,7 @@ def test_scale_continuous_digests_of_the_reference(golden_dir, torch_mod):
         torch_mod.cuda.synchronize()
         _check_scale_continuous(g, res, st[0].cpu().numpy(), st[9].cpu().numpy())
     assert 0 < int(g["emergency_stop"].sum()) < 8  # (one trajectory trips the reference's continuity check at the gimbal lock and stays latched)
-    c._solver.set_option(_abi_mod().OPT_CONT_RUN_MODE, _abi_mod().CONT_RUN_AUTO)
+    c._solver.set_option(abi().OPT_CONT_RUN_MODE, abi().CONT_RUN_AUTO)
 
 
 def test_scale_variants_digests_of_the_reference(golden_dir, torch_mod):
@@ -1577,10 +1464,7 @@ def test_scale_variants_digests_of_the_reference(golden_dir, torch_mod):
     config 3's 256 Ki goal matrices with is_dvt=True (the kernels' singularity-plane variant), "low_elbow", 20 grid points; ControlIK
     continuous on the l_arm mirror images of 256 of G16's trajectories x 1000 steps, "low_elbow", d_theta_max = 0.05 (pipeline and
     step kernel).  Flags and state codes by digest, joints on the subsamples."""
-    from tests import scale_inputs as SC
-    from tests.test_oracle_golden import _check_scale_continuous, _check_scale_set
-
-    A = _abi_mod()
+    A = abi()
     g = load(golden_dir, "g17_scale_variants.npz")
     _, _, _, Mr = SC.config3_from_kept(load(golden_dir, "g14_scale.npz")["c3_kept_bits"])
     Ml = SC.mirror_matrices(Mr)
@@ -1677,7 +1561,7 @@ def test_emergency_reports_continuous(golden_dir, torch_mod, monkeypatch):
                 assert np.max(np.abs(np.asarray(c.previous_sol[arm]) - g[pre + "previous_sol"][k, i])) < 1e-7
         # the same trajectories as a batch (up to the "unfreeze" call): both ways rsik_control_continuous_run issues
         # the work, state codes with the latched steps reported as RSIK_STATE_EMERGENCY, reports from the state rows
-        A = _abi_mod()
+        A = abi()
         upto = Ms.shape[1] - 3
         codes = {s: k for k, s in enumerate(__import__("reachy2_symbolic_ik_amd").STATE_STRINGS)}
         for run_mode in (A.CONT_RUN_PHASED, A.CONT_RUN_STEPS):
@@ -1706,7 +1590,6 @@ def test_fk_of_ik_is_identity_full_size(torch_mod):
     goal pose back (1 M poses, any theta inside the interval), wherever the solver does not move the goal (no backward
     wrist shift, no min-distance reduce; singularity_offset = -1.01 so no elbow projection)."""
     from bench import make_config2_poses
-    from tests.fk_numpy import forward_kinematics
 
     pos, eul = make_config2_poses(1 << 20, seed=4242)
     solver, r, l = make_symbolic(-1.01)
@@ -1735,8 +1618,6 @@ def test_fk_of_ik_is_identity_full_size(torch_mod):
 @pytest.mark.parametrize("arm", ["r_arm", "l_arm"])
 def test_device_forward_kinematics_matches_numpy_chain(torch_mod, arm):
     """rsik_forward_kinematics against the NumPy restatement of the same chain (tests/fk_numpy.py) on random joints."""
-    from tests.fk_numpy import forward_kinematics
-
     solver, r, l = make_symbolic(0.03)
     ik = r if arm == "r_arm" else l
     rng = np.random.default_rng(77)
@@ -1786,12 +1667,6 @@ def test_device_fk_residual_full_size(torch_mod):
 MATRIX_KINDS = ("proper", "gimbal", "skewed", "near_identity")
 
 
-def _euler_to_matrix(e):
-    ca, sa, cb, sb, cc, sc = np.cos(e[:, 0]), np.sin(e[:, 0]), np.cos(e[:, 1]), np.sin(e[:, 1]), np.cos(e[:, 2]), np.sin(e[:, 2])
-    return np.stack([cc * cb, cc * sb * sa - sc * ca, cc * sb * ca + sc * sa, sc * cb, sc * sb * sa + cc * ca, sc * sb * ca - cc * sa,
-                     -sb, cb * sa, cb * ca], axis=1).reshape(-1, 3, 3)
-
-
 @pytest.mark.parametrize("kind", MATRIX_KINDS)
 def test_matrix_to_pose_golden(golden_dir, torch_mod, kind):
     """rsik_matrix_to_pose = batched utils.get_euler_from_homogeneous_matrix (utils.py:84-90) against the angles the
@@ -1806,7 +1681,7 @@ def test_matrix_to_pose_golden(golden_dir, torch_mod, kind):
         np.testing.assert_array_equal(pose[:3].T, M[:, :3, 3])
         eul, ref = pose[3:].T, g[pre + "euler"]
         if kind == "gimbal":
-            assert np.max(np.abs(_euler_to_matrix(eul) - _euler_to_matrix(ref))) < 1e-9
+            assert np.max(np.abs(euler_to_matrix(eul) - euler_to_matrix(ref))) < 1e-9
             locked = np.abs(np.abs(ref[:, 1]) - np.pi / 2) < 5e-8
             assert locked.sum() > 50 and np.all(eul[locked, 2] == 0.0)
             free = np.abs(np.abs(ref[:, 1]) - np.pi / 2) > 1.2e-7
@@ -1872,8 +1747,6 @@ def test_custom_geometry_golden(golden_dir, torch_mod):
     import contextlib
     import io
 
-    from test_oracle_golden import CUSTOM_GEOMETRY
-
     from reachy2_symbolic_ik_amd import DualArmIK, HipSolver, SymbolicIK
 
     g = load(golden_dir, "g9_custom_geometry.npz")
@@ -1920,7 +1793,7 @@ def test_tip_z_specialisation_matches_general_path(torch_mod):
     with contextlib.redirect_stdout(io.StringIO()):
         dual = DualArmIK(solver=solver)
     fast = [to_np(r.solve_batch(p)), to_np(dual.solve_batch(arm_id, p))]
-    solver.set_option(_abi_mod().OPT_NO_TIPZ, 1)
+    solver.set_option(abi().OPT_NO_TIPZ, 1)
     slow = [to_np(r.solve_batch(p)), to_np(dual.solve_batch(arm_id, p))]
     for a, b in zip(fast, slow):
         assert a["reachable"].sum() > 500
@@ -1931,8 +1804,8 @@ def test_tip_z_specialisation_matches_general_path(torch_mod):
         assert np.max(np.abs(a["joints"][m, 6] - b["joints"][m, 6])) < 2e-15
     # mixed launches of mirror-image arms read the constants without handedness as scalars (RSIK_OPT_NO_MIRROR: all per
     # lane from LDS): the same bits either way
-    solver.set_option(_abi_mod().OPT_NO_TIPZ, 0)
-    solver.set_option(_abi_mod().OPT_NO_MIRROR, 1)
+    solver.set_option(abi().OPT_NO_TIPZ, 0)
+    solver.set_option(abi().OPT_NO_MIRROR, 1)
     c = to_np(dual.solve_batch(arm_id, p))
     for k in ("reachable", "state", "interval", "joints", "elbow"):
         np.testing.assert_array_equal(c[k], fast[1][k])

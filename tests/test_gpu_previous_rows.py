@@ -2,69 +2,18 @@
 solution, in one launch.  Checked against the CPU checker (oracle/), whose batch drivers take one previous vector per call,
 by bucketing rows that share a vector; against the reference's own G11 recordings; and against the launch-uniform entry
 points bit for bit."""
-import contextlib
 import copy
-import io
 import os
 
 import numpy as np
 import pytest
 
+from compare import NORTH_STAR_TOL, TOL
+from gpu_support import bucket_vectors, m12, make_control, make_symbolic_dual, orc, soa, to_np, torch_mod, wrist_pitch  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
-TOL = 1e-9
-NORTH_STAR_TOL = 1e-6
-URDF = "config_files/reachy2_ik_minimal.urdf"
 NTHREADS = min(16, os.cpu_count() or 1)
-SIX_PI = 6 * np.pi
-
-
-@pytest.fixture(scope="module")
-def torch_mod():
-    import torch
-
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch
-
-
-@pytest.fixture(scope="module")
-def orc():
-    from oracle import oracle as o
-
-    return o
-
-
-def make_control():
-    from reachy2_symbolic_ik_amd import ControlIK
-
-    with contextlib.redirect_stdout(io.StringIO()):
-        return ControlIK(urdf_path=URDF)
-
-
-def make_symbolic(so=0.03):
-    from reachy2_symbolic_ik_amd import DualArmIK, HipSolver, SymbolicIK
-
-    solver = HipSolver(0)
-    with contextlib.redirect_stdout(io.StringIO()):
-        r = SymbolicIK("r_arm", singularity_offset=so, solver=solver)
-        r._upload()
-        SymbolicIK("l_arm", singularity_offset=so, solver=solver)._upload()
-        dual = DualArmIK(solver=solver, singularity_offset=so)
-    return solver, r, dual
-
-
-def soa(pos, eul, torch):
-    return torch.as_tensor(np.ascontiguousarray(np.concatenate([pos.T, eul.T], axis=0))).cuda()
-
-
-def to_np(res):
-    return {k: v.cpu().numpy() for k, v in res.items() if hasattr(v, "cpu")}
-
-
-def m12(M, torch):
-    from reachy2_symbolic_ik_amd.control_ik import matrices_to_m12_soa
-
-    return matrices_to_m12_soa(M, torch.device("cuda", 0))
 
 
 def random_poses(n, seed):
@@ -79,25 +28,6 @@ def assert_same(a, b, keys=None):
 
 
 # ------------------------------------------------------------------------------------------ discrete against the checker
-def wrist_pitch(rng, n):
-    """Wrist pitch of a previous solution: inside the Orbita3D cone, as every solution is (safety_checks).  A pitch beyond
-    +-pi/2 is the other Euler form of the same wrist (roll and yaw turned by pi): a pose that falls back to previous_sol
-    then lands exactly between two turns of allow_multiturn, and which one it takes rests on the last ulp of the wrist's
-    sin / cos, which the per-row kernels evaluate on the device (include/rsik.h)."""
-    return rng.uniform(-0.7, 0.7, size=n)
-
-
-def bucket_vectors(rng, B):
-    """B distinct previous_sol vectors, uniform in +-5 pi per joint; an eighth of them put joints 0, 2 and 6 just inside
-    +-6 pi (as G11 does), so that allow_multiturn carries the new joints past the limit and every emergency bit trips."""
-    v = rng.uniform(-5 * np.pi, 5 * np.pi, size=(B, 7))
-    v[:, 5] = wrist_pitch(rng, B)
-    edge = np.arange(B) % 8 == 0
-    for k in (0, 2, 6):
-        v[edge, k] = rng.choice([-1.0, 1.0], size=int(edge.sum())) * (SIX_PI - rng.uniform(0.05, 1.0, size=int(edge.sum())))
-    return v
-
-
 @pytest.mark.parametrize("nb,mode,with_cj", [(20, "unconstrained", False), (20, "low_elbow", True),
                                              (64, "unconstrained", True), (64, "low_elbow", False)])
 def test_discrete_rows_config3_against_checker(torch_mod, orc, nb, mode, with_cj):
@@ -180,7 +110,7 @@ def test_solve_rows_near_singular_catalogue(golden_dir, torch_mod, orc, no_tipz)
     g = np.load(os.path.join(golden_dir, "g1_catalogue.npz"))
     rng = np.random.default_rng(5 + no_tipz)
     for tag, so in (("so003_", 0.03), ("so101_", -1.01)):
-        solver, _, _ = make_symbolic(so)
+        solver, _, _ = make_symbolic_dual(so)
         solver.set_option(_abi.OPT_NO_TIPZ, no_tipz)
         n = len(g["arm"])
         prev = rng.uniform(-3.0, 3.0, size=(n, 7))
@@ -206,7 +136,7 @@ def test_solve_rows_uniform_is_rsik_solve(torch_mod):
     and mixed arms."""
     from reachy2_symbolic_ik_amd import _abi
 
-    solver, _, _ = make_symbolic(0.03)
+    solver, _, _ = make_symbolic_dual(0.03)
     n = 40000
     pos, eul = random_poses(n, 21)
     rng = np.random.default_rng(22)
@@ -279,7 +209,7 @@ def test_rows_that_are_not_numbers_stay_in_their_rows(torch_mod):
         return v
 
     # solve: previous_joints is read only at an exact singularity, so every row keeps its bits
-    solver, _, _ = make_symbolic(0.03)
+    solver, _, _ = make_symbolic_dual(0.03)
     pos, eul = random_poses(n, 32)
     p = soa(pos, eul, torch_mod)
     clean = rng.uniform(-2, 2, size=(n, 7))
@@ -306,7 +236,7 @@ def test_rows_that_are_not_numbers_stay_in_their_rows(torch_mod):
 
 # ------------------------------------------------------------------------------------------ Python layers
 def test_python_layers_and_shape_errors(torch_mod):
-    solver, r, dual = make_symbolic(0.03)
+    solver, r, dual = make_symbolic_dual(0.03)
     n = 5000
     pos, eul = random_poses(n, 41)
     rng = np.random.default_rng(42)
@@ -349,7 +279,7 @@ def test_planned_rows_launches_replay_from_a_graph(torch_mod):
     """plan_only=True with per-row previous vectors, recorded into a torch.cuda.graph: the replay gives the eager bits."""
     from bench import make_config3_matrices
 
-    solver, r, _ = make_symbolic(0.03)
+    solver, r, _ = make_symbolic_dual(0.03)
     n = 8192
     pos, eul = random_poses(n, 51)
     rng = np.random.default_rng(52)

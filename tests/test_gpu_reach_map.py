@@ -17,21 +17,15 @@ import numpy as np
 import pytest
 
 from arm_pairs import checker_arms, upload
+from checker_support import default_arms
+from compare import TOL, same_bits
+from gpu_support import KINDS, T, abi, arm_kwargs, last_error, make_symbolic, orc, ptr, raw_call, soa, torch_mod  # noqa: F401
 from reach_map_workload import N_STATES, expected_map, map_case, map_orientations, pack_mask, reduce_map, rounding_bound, tile
-from test_gpu_parity import TOL, make_symbolic, orc, soa, torch_mod  # noqa: F401
-from test_gpu_solver_state import T, last_error, ptr, same_bits
 
 pytestmark = pytest.mark.gpu
 
-KINDS = ("r", "l", "mixed")
 OUTPUTS = ("count", "state_count", "theta_measure", "mask")
 WAVES_PER_BLOCK = 4  # kReachMapWaves: with one position per wave a workgroup holds 4 positions
-
-
-def abi():
-    from reachy2_symbolic_ik_amd import _abi
-
-    return _abi
 
 
 def default_solver():
@@ -41,18 +35,10 @@ def default_solver():
     return solver, r, l
 
 
-def default_arms(orc):
-    return orc.Arm("r_arm", 0.03), orc.Arm("l_arm", 0.03)
-
-
-def arm_kw(kind, arm_ids, torch):
-    return dict(arm=T(arm_ids, torch)) if kind == "mixed" else dict(arm=None, arm_uniform=int(kind == "l"))
-
-
 def positions(orc, kind, n_pos, seed):
     """n_pos positions of the test grid's box (and their arm bytes for kind "mixed"): up to 729 a shuffled subset of the grid itself,
     above that uniform in the box around the position's own shoulder."""
-    arms = default_arms(orc)
+    arms = default_arms()
     P, arm_ids, _ = map_case(arms, kind, n_rot=1, seed=seed)
     rng = np.random.default_rng(seed + 1)
     if n_pos <= len(P):
@@ -77,7 +63,7 @@ def solve_tiled(solver, P, kind, arm_ids, E, torch):
     """The reference the entry point is defined against: rsik_solve under RSIK_THETA_NONE on the tiled poses, reduced with NumPy
     (math.fsum per position for the measure)."""
     pos, eul, arm = tile(P, arm_ids if kind == "mixed" else int(kind == "l"), E)
-    kw = dict(arm=T(arm, torch)) if kind == "mixed" else dict(arm=None, arm_uniform=int(kind == "l"))
+    kw = arm_kwargs(kind, arm, torch)
     res = solver.solve(soa(pos, eul, torch), theta_policy=abi().THETA_NONE, **kw)
     ref = reduce_map(res["reachable"].cpu().numpy(), res["state"].cpu().numpy(), res["interval"].cpu().numpy(), len(P), len(E))
     assert np.isnan(res["interval"].cpu().numpy()[res["reachable"].cpu().numpy() == 0]).all()
@@ -113,9 +99,7 @@ def raw_map(solver, n_pos, p, n_rot, e, arm=None, arm_uniform=0, count=None, sta
             null_col=None):
     """rsik_reach_map on the caller's own buffers: returns the ABI's code.  p / e: [3, n] tensors or None for a NULL table;
     null_col = ("pos" | "eul", k): that column pointer NULL."""
-    import torch
-
-    def cols(t, name):
+    def table(t, name):
         if t is None:
             return None
         ptrs = [t[k].data_ptr() for k in range(3)]
@@ -123,10 +107,8 @@ def raw_map(solver, n_pos, p, n_rot, e, arm=None, arm_uniform=0, count=None, sta
             ptrs[null_col[1]] = None
         return (C.c_void_p * 3)(*ptrs)
 
-    with torch.cuda.device(solver.device):
-        solver._bind_stream()
-        return solver.lib.rsik_reach_map(solver._h, n_pos, cols(p, "pos"), ptr(arm), int(arm_uniform), int(n_rot), cols(e, "eul"),
-                                         ptr(count), ptr(state_count), ptr(theta_measure), ptr(mask))
+    return raw_call(solver, "rsik_reach_map", n_pos, table(p, "pos"), ptr(arm), int(arm_uniform), int(n_rot), table(e, "eul"), ptr(count),
+                    ptr(state_count), ptr(theta_measure), ptr(mask))
 
 
 # ------------------------------------------------------------------------------------------ 1. against the library's own rsik_solve
@@ -147,7 +129,7 @@ def test_map_is_rsik_solve_reduced(torch_mod, orc, kind):
         if n_pos == 729 and n_rot == 130:
             assert ((ref["count"] > 0) & (ref["count"] < n_rot)).sum() >= 243
         for opts in with_options(solver):
-            got = to_map(solver.reach_map(T(P.T, torch), T(E.T, torch), **arm_kw(kind, arm_ids, torch)))
+            got = to_map(solver.reach_map(T(P.T, torch), T(E.T, torch), **arm_kwargs(kind, arm_ids, torch)))
             assert got["mask"].shape == (n_pos, (n_rot + 63) // 64) and got["state_count"].shape == (n_pos, N_STATES)
             check_map(got, ref, n_rot, f"{kind} {n_pos} x {n_rot} {opts}")
 
@@ -166,7 +148,7 @@ def test_more_positions_per_wave(torch_mod, orc, kind):
         n_pos = cus * 8 * WAVES_PER_BLOCK * ppw + extra
         P, arm_ids = positions(orc, kind, n_pos, seed=70 + ppw)
         ref = solve_tiled(solver, P, kind, arm_ids, E, torch)
-        got = to_map(solver.reach_map(T(P.T, torch), T(E.T, torch), **arm_kw(kind, arm_ids, torch)))
+        got = to_map(solver.reach_map(T(P.T, torch), T(E.T, torch), **arm_kwargs(kind, arm_ids, torch)))
         check_map(got, ref, n_rot, f"{kind} {n_pos} x {n_rot} ({ppw} positions per wave)")
 
 
@@ -177,7 +159,7 @@ def test_map_against_the_checker(torch_mod, orc, pair):
     2 * TOL * count[i] (TOL = 1e-9 per interval end) plus the rounding bound."""
     torch = torch_mod
     if pair == "default/default":
-        arms, solver = default_arms(orc), default_solver()[0]
+        arms, solver = default_arms(), default_solver()[0]
     else:
         arms, solver = checker_arms(pair), upload(pair)
     P, arm_ids, E = map_case(arms, "mixed")
@@ -195,7 +177,7 @@ def test_optional_outputs_and_guards(torch_mod, orc):
     _abi = abi()
     solver, _, _ = default_solver()
     n_pos, n_rot, guard = 729, 130, 256
-    P, arm_ids, E = map_case(default_arms(orc), "mixed")
+    P, arm_ids, E = map_case(default_arms(), "mixed")
     p, e, arm = T(P.T, torch), T(E.T, torch), T(arm_ids, torch)
     words = (n_rot + 63) // 64
     sizes = {"count": 4 * n_pos, "state_count": 4 * n_pos * N_STATES, "theta_measure": 8 * n_pos, "mask": 8 * n_pos * words}
@@ -234,7 +216,7 @@ def test_rows_that_are_not_numbers(torch_mod, orc):
     torch = torch_mod
     INVALID = abi().STATE_INVALID_INPUT
     solver, _, _ = default_solver()
-    P, arm_ids, E = map_case(default_arms(orc), "mixed")
+    P, arm_ids, E = map_case(default_arms(), "mixed")
     n_pos, n_rot = len(P), len(E)
     arm = T(arm_ids, torch)
     clean = to_map(solver.reach_map(T(P.T, torch), T(E.T, torch), arm=arm))
@@ -276,7 +258,7 @@ def test_far_inputs_are_answered_as_rsik_solve_answers_them(torch_mod, orc):
     are answered as their rsik_solve rows."""
     torch = torch_mod
     solver, _, _ = default_solver()
-    P, arm_ids, E = map_case(default_arms(orc), "mixed")
+    P, arm_ids, E = map_case(default_arms(), "mixed")
     P, arm_ids = P[200:264].copy(), arm_ids[200:264].copy()
     E = E.copy()
     E[3, 0] = 2.0 ** 27 + 1.5
@@ -297,7 +279,7 @@ def test_measure_is_reproducible_and_nothing_accumulates(torch_mod, orc):
     same result: nothing accumulates into the caller's memory.  n_rot = 2500: three LDS tiles, the totals carried between them."""
     torch = torch_mod
     solver, _, _ = default_solver()
-    P, arm_ids, _ = map_case(default_arms(orc), "mixed")
+    P, arm_ids, _ = map_case(default_arms(), "mixed")
     for n_rot in (130, 2500):
         E = map_orientations(n_rot, 7)
         p, e, arm = T(P.T, torch), T(E.T, torch), T(arm_ids, torch)
@@ -325,7 +307,7 @@ def test_argument_checks(torch_mod, orc):
     from reachy2_symbolic_ik_amd import HipSolver
 
     solver, r, _ = default_solver()
-    P, arm_ids, E = map_case(default_arms(orc), "mixed")
+    P, arm_ids, E = map_case(default_arms(), "mixed")
     p, e, arm = T(P.T, torch), T(E.T, torch), T(arm_ids, torch)
     sentinel = 0x5A5A5A5A
     count = torch.full((729,), sentinel, dtype=torch.int32, device="cuda")
@@ -373,7 +355,7 @@ def test_python_surface(torch_mod, orc):
     from reachy2_symbolic_ik_amd.symbolic_ik import unpack_reach_mask
 
     solver, r, l = default_solver()
-    arms = default_arms(orc)
+    arms = default_arms()
     for kind, ik in (("r", r), ("l", l)):
         P, _, E = map_case(arms, kind)
         raw = to_map(solver.reach_map(T(P.T, torch), T(E.T, torch), arm_uniform=int(kind == "l")))

@@ -15,103 +15,24 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from nearest_workload import COST_TOL, GAP, KS, N_MAIN, gap_condition, main_case, main_thetas, nearest_from_sweep, seeds, skip_projected_case
+from checker_support import reachable_rich
+from compare import bits
+from gpu_support import KINDS, T, abi, cols, last_error, make_symbolic, orc, ptr, raw_call, soa, to_np, torch_mod  # noqa: F401
+from nearest_workload import GAP, KS, N_MAIN, main_case, main_thetas, seeds, skip_projected_case
+from sampling_support import LANES, ROWS, check_nearest, main_launches, same_nearest_outputs
 from sweep_workload import sweep_poses, sweep_thetas
-from test_gpu_parity import make_symbolic, orc, soa, to_np, torch_mod  # noqa: F401
-from test_gpu_solver_state import T, arm_kwargs, last_error, ptr, reachable_rich
-from test_solver_state_checker import bits
 
 pytestmark = pytest.mark.gpu
 
-KINDS = ("r", "l", "mixed")
-LANES = (0, 1, 8, 64)  # RSIK_OPT_NEAREST_LANES: the library's choice, and each form forced
-ROWS = ("index", "theta", "joints", "elbow", "cost", "projected", "interval", "reachable", "state")
-
-
-def abi():
-    from reachy2_symbolic_ik_amd import _abi
-
-    return _abi
 
 
 def raw_nearest(solver, n, p, k, policy, thetas, per_pose, seed, weights=None, flags=0, arm=None, arm_uniform=0, prev=None,
                 index=None, theta=None, joints=None, elbow=None, cost=None, projected=None, interval=None, reachable=None, state=None):
     """rsik_solve_nearest on the caller's own buffers: returns the ABI's code."""
-    import torch
-
-    cols = None if p is None else (C.c_void_p * 6)(*[p[c].data_ptr() for c in range(6)])
     w = None if weights is None else (C.c_double * 7)(*[float(v) for v in weights])
-    with torch.cuda.device(solver.device):
-        solver._bind_stream()
-        return solver.lib.rsik_solve_nearest(solver._h, n, cols, ptr(arm), int(arm_uniform), int(k), int(policy), ptr(thetas),
-                                             int(per_pose), ptr(prev), ptr(seed), w, int(flags), ptr(index), ptr(theta), ptr(joints),
-                                             ptr(elbow), ptr(cost), ptr(projected), ptr(interval), ptr(reachable), ptr(state))
-
-
-def as_bits(a):
-    return bits(a) if a.dtype == np.float64 else a
-
-
-def same_outputs(a, b, what, rows=None, keys=ROWS):
-    for key in keys:
-        x, y = (a[key], b[key]) if rows is None else (a[key][rows], b[key][rows])
-        np.testing.assert_array_equal(as_bits(x), as_bits(y), err_msg=f"{what}: {key}")
-
-
-def check_nearest(got, sw, seed, what, weights=None, skip=False, need_gap=False):
-    """(a) - (d) of the module docstring for one launch `got` against the library's sweep `sw` of the same inputs."""
-    exp = nearest_from_sweep(sw, seed, weights, skip)
-    if need_gap:
-        gap_condition(exp, sw["reachable"], what)  # the condition on the inputs, before anything is compared
-    n = len(seed)
-    idx = got["index"]
-    assert idx.dtype == np.int32 and idx.shape == (n,), what
-    np.testing.assert_array_equal(idx == -1, exp["index"] == -1, err_msg=what + ": rows without a candidate")
-    has = idx >= 0
-    rows = np.flatnonzero(has)
-    assert (idx[has] < sw["joints"].shape[0]).all(), what
-    # (a)
-    for key in ("theta", "joints", "elbow"):
-        np.testing.assert_array_equal(bits(got[key][rows]), bits(sw[key][idx[rows], rows]), err_msg=f"{what}: {key} is not the sweep's sample")
-        assert np.isnan(got[key][~has]).all(), (what, key)
-    np.testing.assert_array_equal(got["projected"][rows], sw["projected"][idx[rows], rows], err_msg=what + ": projected")
-    assert (got["projected"][~has] == 0).all() and got["projected"].dtype == np.uint8, what
-    # (b)
-    masked = np.where(exp["candidate"], exp["c"], np.inf)
-    c_won = masked[idx[rows], rows]
-    c_min = exp["c_min"][rows]
-    excess = c_won - c_min
-    print(f"{what}: {len(rows)} winners, largest c - c_min {float(excess.max(initial=0.0)):.3e}")
-    assert (c_won <= c_min + COST_TOL * np.maximum(1.0, c_min)).all(), (what, float(excess.max(initial=0.0)))
-    # (c)
-    clear = has & (exp["gap"] > GAP)
-    np.testing.assert_array_equal(idx[clear], exp["index"][clear], err_msg=what + ": index where the gap is clear")
-    # (d)
-    err = np.abs(got["cost"][rows] - np.sqrt(c_won))
-    print(f"{what}: largest |cost - sqrt(c)| {float(err.max(initial=0.0)):.3e}")
-    assert (err <= COST_TOL).all() and np.isnan(got["cost"][~has]).all(), (what, float(err.max(initial=0.0)))
-    # the per-pose outputs of is_reachable
-    for key in ("interval", "reachable", "state"):
-        np.testing.assert_array_equal(as_bits(got[key]), as_bits(sw[key]), err_msg=f"{what}: {key}")
-    ok = sw["reachable"].astype(bool)
-    assert (idx[~ok] == -1).all(), what
-    return exp
-
-
-def main_launches(torch, kind, k):
-    """The launches of tests 1 and 2 for one (kind, K): what, poses, thetas, seed rows (device), the keyword arguments solve_sweep
-    and solve_nearest share, seed rows (host)."""
-    pos, eul, arm, seed = main_case(kind, k)
-    p = soa(pos, eul, torch)
-    kw = arm_kwargs(kind, arm, torch)
-    prev_rows = T(np.random.default_rng(40 + k).uniform(-2, 2, size=(N_MAIN, 7)), torch)
-    seedT = T(seed, torch)
-    for policy in ("fraction", "explicit"):
-        for per_pose in (False, True):
-            th = T(main_thetas(policy, per_pose, k), torch)
-            for prev in (None, prev_rows):
-                what = f"{kind} K {k} {policy} per_pose {per_pose} prev {prev is not None}"
-                yield what, p, th, seedT, dict(policy=policy, previous_joints=prev, **kw), seed
+    return raw_call(solver, "rsik_solve_nearest", n, cols(p, 6), ptr(arm), int(arm_uniform), int(k), int(policy), ptr(thetas), int(per_pose),
+                    ptr(prev), ptr(seed), w, int(flags), ptr(index), ptr(theta), ptr(joints), ptr(elbow), ptr(cost), ptr(projected),
+                    ptr(interval), ptr(reachable), ptr(state))
 
 
 # ------------------------------------------------------------------------------------------ 1. the winner is a sweep sample
@@ -150,7 +71,7 @@ def test_every_lane_count_gives_the_same_bits(torch_mod, kind):
                 outs[lanes] = to_np(solver.solve_nearest(p, th, seedT, **kw))
             assert (outs[1]["index"] >= 0).sum() > 300, what
             for lanes in LANES[1:]:
-                same_outputs(outs[lanes], outs[0], f"{what}: L {lanes} against the library's choice")
+                same_nearest_outputs(outs[lanes], outs[0], f"{what}: L {lanes} against the library's choice")
 
 
 # ------------------------------------------------------------------------------------------ 3. ties go to the lowest k
@@ -239,7 +160,7 @@ def test_weights(torch_mod):
         assert differ >= 10
     solver.set_option(_abi.OPT_NEAREST_LANES, 0)
     ones = to_np(solver.solve_nearest(p, th, seedT, weights=(1,) * 7, arm=armT))
-    same_outputs(ones, unit, "weights of ones against NULL")
+    same_nearest_outputs(ones, unit, "weights of ones against NULL")
     index = torch.full((N_MAIN,), 77, dtype=torch.int32, device="cuda")
     for bad in (-1.0, float("nan"), float("inf"), -0.5):
         for q in (0, 6):
@@ -325,7 +246,7 @@ def test_rows_that_are_not_numbers_stay_where_they_are(torch_mod):
     got = run(p2, per_pose, seed)
     keep = np.ones(n, dtype=bool)
     keep[bad] = False
-    same_outputs(got, clean, "bad poses: the other rows", rows=keep)
+    same_nearest_outputs(got, clean, "bad poses: the other rows", rows=keep)
     assert (got["state"][bad] == _abi.STATE_INVALID_INPUT).all() and (got["reachable"][bad] == 0).all() and (got["index"][bad] == -1).all()
     assert (got["projected"][bad] == 0).all()
     for key in ("theta", "joints", "elbow", "cost", "interval"):
@@ -338,8 +259,8 @@ def test_rows_that_are_not_numbers_stay_where_they_are(torch_mod):
     got = run(p, per_pose, seed2)
     keep = np.ones(n, dtype=bool)
     keep[bad] = False
-    same_outputs(got, clean, "bad seed rows: the other rows", rows=keep)
-    same_outputs(got, clean, "bad seed rows: is_reachable's outputs", keys=("interval", "reachable", "state"))
+    same_nearest_outputs(got, clean, "bad seed rows: the other rows", rows=keep)
+    same_nearest_outputs(got, clean, "bad seed rows: is_reachable's outputs", keys=("interval", "reachable", "state"))
     assert (got["index"][bad] == -1).all() and (got["reachable"][bad] == 1).all() and (got["projected"][bad] == 0).all()
     for key in ("theta", "joints", "elbow", "cost"):
         assert np.isnan(got[key][bad]).all(), key
@@ -353,7 +274,7 @@ def test_rows_that_are_not_numbers_stay_where_they_are(torch_mod):
     got = run(p, th2, seed)
     keep = np.ones(n, dtype=bool)
     keep[row_b] = False
-    same_outputs(got, clean, "a NaN theta beside the winner", rows=keep)
+    same_nearest_outputs(got, clean, "a NaN theta beside the winner", rows=keep)
     exp = check_nearest(got, sweep(p, th2), seed, "a NaN theta entry")
     assert got["index"][row_b] >= 0 and got["index"][row_b] != clean["index"][row_b]
     if exp["gap"][row_b] > GAP:
@@ -366,7 +287,7 @@ def test_rows_that_are_not_numbers_stay_where_they_are(torch_mod):
     got = run(p, sh2, seed)
     assert not (got["index"] == 1).any() and (got["index"][ok] >= 0).all()
     check_nearest(got, sweep(p, sh2), seed, "a NaN in the shared grid")
-    same_outputs(got, clean_s, "the rows sample 1 did not win", rows=clean_s["index"] != 1)
+    same_nearest_outputs(got, clean_s, "the rows sample 1 did not win", rows=clean_s["index"] != 1)
 
 
 # ------------------------------------------------------------------------------------------ 8. arguments
@@ -453,11 +374,11 @@ def test_arguments(torch_mod):
             part = {key: t for key, t in fresh().items() if key not in left_out}
             assert raw_nearest(solver, n, p, k, FR, th, 0, seed, **part) == _abi.RSIK_OK, (left_out, last_error(solver))
             torch.cuda.synchronize()
-            same_outputs({key: t.cpu().numpy() for key, t in part.items()}, full, f"without {left_out}, L {lanes}", keys=tuple(part))
+            same_nearest_outputs({key: t.cpu().numpy() for key, t in part.items()}, full, f"without {left_out}, L {lanes}", keys=tuple(part))
     solver.set_option(_abi.OPT_NEAREST_LANES, 0)
     no_elbow = solver.solve_nearest(p, th, seed, want_elbow=False)
     assert "elbow" not in no_elbow
-    same_outputs(to_np(no_elbow), full, "want_elbow=False", keys=tuple(key for key in ROWS if key != "elbow"))
+    same_nearest_outputs(to_np(no_elbow), full, "want_elbow=False", keys=tuple(key for key in ROWS if key != "elbow"))
 
 
 # ------------------------------------------------------------------------------------------ 9. Python surface
@@ -484,7 +405,7 @@ def test_python_surface(torch_mod):
     grid = torch.linspace(0.0, 1.0, k, dtype=torch.float64)
     p = soa(pos_r, eul_r, torch)
     raw = to_np(solver.solve_nearest(p, grid, T(seed, torch), policy="fraction", arm_uniform=0))
-    same_outputs(res, raw, "SymbolicIK.nearest_batch")
+    same_nearest_outputs(res, raw, "SymbolicIK.nearest_batch")
     check_nearest(res, to_np(solver.solve_sweep(p, grid)), seed, "nearest_batch against sweep_batch's grid")
     assert (res["index"] >= 0).sum() > 250
     default = r.nearest_batch(poses, seed)  # n_theta = 64
@@ -496,7 +417,7 @@ def test_python_surface(torch_mod):
     a = to_np(r.nearest_batch(poses, seed, thetas=th, policy="explicit", previous_joints=prev, weights=w, skip_projected=True))
     b = to_np(solver.solve_nearest(p, T(th, torch), T(seed, torch), policy="explicit", previous_joints=T(prev, torch), weights=w,
                                    skip_projected=True))
-    same_outputs(a, b, "explicit, previous_joints, weights, skip_projected")
+    same_nearest_outputs(a, b, "explicit, previous_joints, weights, skip_projected")
     sw = to_np(solver.solve_sweep(p, T(th, torch), policy="explicit", previous_joints=T(prev, torch)))
     check_nearest(a, sw, seed, "explicit, previous_joints, weights, skip_projected", weights=w, skip=True)
     # plan_only: nothing launched, the re-launch reproduces the result
@@ -506,17 +427,17 @@ def test_python_surface(torch_mod):
     assert bool((out["index"] == 77).all()) and bool((out["joints"] == 77).all()), "plan_only must not launch"
     planned["launch"]()
     torch.cuda.synchronize()
-    same_outputs({key: out[key].cpu().numpy() for key in want}, raw, "planned launch")
+    same_nearest_outputs({key: out[key].cpu().numpy() for key in want}, raw, "planned launch")
     planned["launch"]()
     torch.cuda.synchronize()
-    same_outputs({key: out[key].cpu().numpy() for key in want}, raw, "planned launch, again")
+    same_nearest_outputs({key: out[key].cpu().numpy() for key in want}, raw, "planned launch, again")
     # both arms
     pos, eul = reachable_rich(61, n, arm)
     dual = DualArmIK(solver=solver, singularity_offset=0.03)
     d = to_np(dual.nearest_batch(arm, np.stack([pos, eul], axis=1), seed, n_theta=k))
     raw = to_np(solver.solve_nearest(soa(pos, eul, torch), grid, T(seed, torch), arm=T(arm, torch)))
     assert d["joints"].shape == (n, 7) and d["index"].dtype == np.int32
-    same_outputs(d, raw, "DualArmIK.nearest_batch")
+    same_nearest_outputs(d, raw, "DualArmIK.nearest_batch")
     # what the Python driver refuses before any launch, by its whole text
     seedT = T(seed, torch)
     refused = {

@@ -16,112 +16,14 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from compare import bits
+from gpu_support import T, abi, cols, last_error, make_symbolic, orc, ptr, raw_call, to_np, torch_mod  # noqa: F401
 from nearest_workload import skip_projected_case
-from path_workload import (GAP, MAIN_SHAPES, N_MAIN, SMALL_SHAPES, cost_along, flat, gap_condition, path_dp, path_fractions, path_poses,
-                           path_start, path_tol)
-from test_gpu_parity import make_symbolic, orc, to_np, torch_mod  # noqa: F401
-from test_gpu_solver_state import T, last_error, ptr
-from test_solver_state_checker import bits
+from path_workload import GAP, MAIN_SHAPES, N_MAIN, SMALL_SHAPES, cost_along, path_fractions, path_poses, path_start, path_tol
+from sampling_support import ALL, check_path, launches, lib_sweep, path_arm_kwargs, path_soa, same_path_outputs
 
 pytestmark = pytest.mark.gpu
 
-PER_WAYPOINT = ("index", "theta", "joints", "elbow", "projected", "step_cost", "interval", "reachable", "state")
-PER_PATH = ("cost", "n_solved")
-ALL = PER_WAYPOINT + PER_PATH
-
-
-def abi():
-    from reachy2_symbolic_ik_amd import _abi
-
-    return _abi
-
-
-def path_soa(pos, eul, torch):
-    """[T,n,3] x 2 -> SoA [6, T, n] on the device."""
-    return torch.as_tensor(np.ascontiguousarray(np.concatenate([pos, eul], axis=2).transpose(2, 0, 1))).cuda()
-
-
-def arm_kw(arm, torch):
-    return dict(arm=T(arm, torch)) if arm.any() else dict(arm_uniform=0)
-
-
-def lib_sweep(solver, p, th, policy, arm, torch):
-    """The library's sweep over the T * n poses of p [6,T,n]; thetas [K] or [K,T,n]; the arm byte of a path at each of its waypoints."""
-    t, n = int(p.shape[1]), int(p.shape[2])
-    th = th if th.dim() == 1 else th.reshape(th.shape[0], t * n)
-    kw = dict(arm=T(np.tile(arm, t), torch)) if arm.any() else dict(arm_uniform=0)
-    return to_np(solver.solve_sweep(p.reshape(6, t * n), th, policy=policy, **kw))
-
-
-def as_bits(a):
-    return bits(a) if a.dtype == np.float64 else a
-
-
-def same_outputs(a, b, what, keys=ALL, paths=None, waypoints=None):
-    for key in keys:
-        x, y = a[key], b[key]
-        if key in PER_WAYPOINT:
-            if waypoints is not None:
-                x, y = x[waypoints[0]], y[waypoints[1]]
-            if paths is not None:
-                x, y = x[:, paths], y[:, paths]
-        elif paths is not None:
-            x, y = x[paths], y[paths]
-        np.testing.assert_array_equal(as_bits(x), as_bits(y), err_msg=f"{what}: {key}")
-
-
-def check_path(got, sw, t, n, what, start=None, weights=None, skip=False, need_gap=False):
-    """(a) - (c) of the module docstring for one launch `got` against the library's sweep `sw` over the same poses."""
-    exp = path_dp(sw, t, n, start, weights, skip)
-    if need_gap:
-        gap_condition(exp, what, seeded=start is not None)  # the condition on the inputs, before anything is compared
-    idx = got["index"]
-    k = sw["joints"].shape[0]
-    assert idx.dtype == np.int32 and idx.shape == (t, n) and got["n_solved"].dtype == np.int32, what
-    # (a)
-    np.testing.assert_array_equal(idx == -1, ~exp["solved"], err_msg=what + ": the skipped waypoints")
-    np.testing.assert_array_equal(got["n_solved"], exp["n_solved"], err_msg=what)
-    assert (idx < k).all(), what
-    tt, ii = np.nonzero(idx >= 0)
-    pose = tt * n + ii
-    for key in ("theta", "joints", "elbow"):
-        np.testing.assert_array_equal(bits(got[key][tt, ii]), bits(sw[key][idx[tt, ii], pose]), err_msg=f"{what}: {key} is not the sweep's sample")
-        assert np.isnan(got[key][idx < 0]).all(), (what, key)
-    np.testing.assert_array_equal(got["projected"][tt, ii], sw["projected"][idx[tt, ii], pose], err_msg=what + ": projected")
-    assert (got["projected"][idx < 0] == 0).all() and got["projected"].dtype == np.uint8, what
-    assert np.isnan(got["step_cost"][idx < 0]).all() and not np.isnan(got["step_cost"][idx >= 0]).any(), what
-    for key in ("interval", "reachable", "state"):
-        np.testing.assert_array_equal(as_bits(got[key].reshape((t * n,) + got[key].shape[2:])), as_bits(sw[key]), err_msg=f"{what}: {key}")
-    # (b)
-    tol = path_tol(t)
-    has = exp["n_solved"] > 0
-    along, step2 = cost_along(sw, idx, t, n, start, weights)
-    excess = along[has] - exp["cost"][has]
-    err_cost = np.abs(got["cost"][has] - along[has])
-    err_steps = np.abs(np.nansum(got["step_cost"] ** 2, axis=0)[has] - along[has])
-    print(f"{what}: {int(has.sum())} paths, device path - optimum in [{float(excess.min(initial=0.0)):.3e}, {float(excess.max(initial=0.0)):.3e}], "
-          f"|cost - recomputed| {float(err_cost.max(initial=0.0)):.3e}, |sum step_cost^2 - recomputed| {float(err_steps.max(initial=0.0)):.3e}, tol {tol:.1e}")
-    assert (np.abs(excess) <= tol).all(), (what, float(np.abs(excess).max(initial=0.0)))
-    assert (err_cost <= tol).all() and np.isnan(got["cost"][~has]).all(), (what, float(err_cost.max(initial=0.0)))
-    assert (err_steps <= tol).all(), (what, float(err_steps.max(initial=0.0)))
-    # (c)  (without start joints a path with one solved waypoint is an exact tie at 0, the lowest sample's on both sides)
-    clear = exp["gap"] > GAP
-    if start is None:
-        clear = clear | (exp["n_solved"] == 1)
-    np.testing.assert_array_equal(idx[:, clear], exp["index"][:, clear], err_msg=what + ": index where the gap is clear")
-    return exp
-
-
-def launches(torch, t, k, seed, kind, n=N_MAIN):
-    """The launches of test 1 for one shape: FRACTION with the shared grid and EXPLICIT with an angle per waypoint and sample, each
-    with and without start joints."""
-    pos, eul, arm = path_poses(seed, n, t, kind)
-    p = path_soa(pos, eul, torch)
-    start = path_start(seed, n)
-    explicit = np.random.default_rng(seed + 200).uniform(-np.pi, np.pi, size=(k, t, n))
-    for policy, th in (("fraction", path_fractions(k)), ("explicit", explicit)):
-        for st in (None, start):
-            yield f"T {t} K {k} seed {seed} {kind} n {n} {policy} start {st is not None}", p, T(th, torch), policy, arm, st
 
 
 # ------------------------------------------------------------------------------------------ 1, 2. sweep samples, and the optimum
@@ -132,7 +34,7 @@ def test_the_path_is_made_of_sweep_samples_and_is_the_optimum(torch_mod, shape):
     solver, _, _ = make_symbolic(0.03)
     for what, p, th, policy, arm, start in launches(torch, t, k, seed, kind, n):
         sw = lib_sweep(solver, p, th, policy, arm, torch)
-        got = to_np(solver.solve_path(p, th, None if start is None else T(start, torch), policy=policy, **arm_kw(arm, torch)))
+        got = to_np(solver.solve_path(p, th, None if start is None else T(start, torch), policy=policy, **path_arm_kwargs(arm, torch)))
         need_gap = n == N_MAIN and policy == "fraction" and k > 1 and (t > 1 or start is not None)
         exp = check_path(got, sw, t, n, what, start, need_gap=need_gap)
         if n == N_MAIN and t >= 5 and policy == "fraction":
@@ -157,7 +59,7 @@ def test_a_skipped_waypoint_is_as_good_as_absent(torch_mod, gone):
         b = to_np(solver.solve_path(path_soa(pos[keep], eul[keep], torch), th, start))
         assert (a["index"][gone] == -1).all() and (a["reachable"][gone] == 0).all() and np.isnan(a["step_cost"][gone]).all()
         assert (b["n_solved"] >= 2).sum() >= 20
-        same_outputs(a, b, f"waypoint {gone} skipped, start {start is not None}", waypoints=(keep, slice(None)))
+        same_path_outputs(a, b, f"waypoint {gone} skipped, start {start is not None}", waypoints=(keep, slice(None)))
 
 
 # ------------------------------------------------------------------------------------------ 4. against the greedy chain
@@ -202,7 +104,7 @@ def test_weights(torch_mod):
     solver, _, _ = make_symbolic(0.03)
     sw = lib_sweep(solver, p, th, "fraction", arm, torch)
     unit = to_np(solver.solve_path(p, th, T(start, torch)))
-    same_outputs(to_np(solver.solve_path(p, th, T(start, torch), weights=(1,) * 7)), unit, "weights of ones against NULL")
+    same_path_outputs(to_np(solver.solve_path(p, th, T(start, torch), weights=(1,) * 7)), unit, "weights of ones against NULL")
     for w in ((1, 1, 1, 1, 0, 0, 0), (0.5, 0, 2, 3, 5, 1, 0.25)):
         got = to_np(solver.solve_path(p, th, T(start, torch), weights=w))
         check_path(got, sw, t, n, f"weights {w}", start, weights=w, need_gap=True)
@@ -268,7 +170,7 @@ def test_unwind(torch_mod):
         moved = (bits(got["joints"]) != bits(plain["joints"])).any(axis=2)
         print(f"start {start is not None}: {int(moved.sum())} of {int((plain['index'] >= 0).sum())} solved rows were unwound")
         assert moved.sum() >= 20 and (np.abs(got["joints"][plain["index"] >= 0]) > np.pi).any()
-        same_outputs(got, plain, "everything but joints", keys=tuple(key for key in ALL if key != "joints"))
+        same_path_outputs(got, plain, "everything but joints", keys=tuple(key for key in ALL if key != "joints"))
 
 
 # ------------------------------------------------------------------------------------------ 7. rows that are not numbers
@@ -291,7 +193,7 @@ def test_rows_that_are_not_numbers_stay_where_they_are(torch_mod):
         return to_np(solver.solve_path(poses, T(thetas, torch), T(st, torch)))
 
     clean = run(p, per, start)
-    same_outputs(run(p, grid, start), clean, "one angle per waypoint and sample against the shared grid")
+    same_path_outputs(run(p, grid, start), clean, "one angle per waypoint and sample against the shared grid")
     whole = np.flatnonzero(clean["n_solved"] == t)
     assert len(whole) >= 9
     # a. poses that are not numbers
@@ -301,7 +203,7 @@ def test_rows_that_are_not_numbers_stay_where_they_are(torch_mod):
         p2[(0, 4, 2)[q], (0, 6, t - 1)[q], i] = (float("nan"), float("inf"), float("-inf"))[q]
     got = run(p2, per, start)
     others = np.setdiff1d(np.arange(n), bad)
-    same_outputs(got, clean, "bad poses: the other paths", paths=others)
+    same_path_outputs(got, clean, "bad poses: the other paths", paths=others)
     for q, i in enumerate(bad):
         s = (0, 6, t - 1)[q]
         assert got["state"][s, i] == _abi.STATE_INVALID_INPUT and got["reachable"][s, i] == 0 and got["index"][s, i] == -1
@@ -313,7 +215,7 @@ def test_rows_that_are_not_numbers_stay_where_they_are(torch_mod):
     th2[clean["index"][5, i_a], 5, i_a] = np.nan
     th2[(clean["index"][5, i_b] + 1) % k, 5, i_b] = np.nan
     got = run(p, th2, start)
-    same_outputs(got, clean, "a NaN theta: the other paths", paths=np.setdiff1d(np.arange(n), [i_a]))
+    same_path_outputs(got, clean, "a NaN theta: the other paths", paths=np.setdiff1d(np.arange(n), [i_a]))
     assert got["index"][5, i_a] >= 0 and got["index"][5, i_a] != clean["index"][5, i_a] and got["n_solved"][i_a] == t
     check_path(got, lib_sweep(solver, p, T(th2, torch), "fraction", arm, torch), t, n, "a NaN theta", start)
     sh2 = grid.copy()
@@ -328,8 +230,8 @@ def test_rows_that_are_not_numbers_stay_where_they_are(torch_mod):
     for q, i in enumerate(bad):
         st2[i, (0, 3, 6)[q]] = (np.nan, np.inf, np.nan)[q]
     got = run(p, per, st2)
-    same_outputs(got, clean, "bad start rows: the other paths", paths=np.setdiff1d(np.arange(n), bad))
-    same_outputs(got, clean, "bad start rows: is_reachable's outputs", keys=("interval", "reachable", "state"))
+    same_path_outputs(got, clean, "bad start rows: the other paths", paths=np.setdiff1d(np.arange(n), bad))
+    same_path_outputs(got, clean, "bad start rows: is_reachable's outputs", keys=("interval", "reachable", "state"))
     assert (got["n_solved"][bad] == 0).all() and (got["index"][:, bad] == -1).all() and np.isnan(got["cost"][bad]).all()
     assert (got["projected"][:, bad] == 0).all()
     for key in ("theta", "joints", "elbow", "step_cost"):
@@ -340,18 +242,13 @@ def test_rows_that_are_not_numbers_stay_where_they_are(torch_mod):
 def raw_path(solver, n, t, p, k, policy, thetas, per_pose, start=None, weights=None, flags=0, arm=None, arm_uniform=0, workspace=None,
              workspace_bytes=None, **outs):
     """rsik_solve_path on the caller's own buffers: returns the ABI's code."""
-    import torch
-
-    cols = None if p is None else (C.c_void_p * 6)(*[p[c].data_ptr() for c in range(6)])
     w = None if weights is None else (C.c_double * 7)(*[float(v) for v in weights])
     if workspace_bytes is None:
         workspace_bytes = 0 if workspace is None else workspace.numel()
     o = [ptr(outs.get(key)) for key in ("index", "theta", "joints", "elbow", "projected", "step_cost", "cost", "n_solved", "interval",
                                          "reachable", "state")]
-    with torch.cuda.device(solver.device):
-        solver._bind_stream()
-        return solver.lib.rsik_solve_path(solver._h, n, t, cols, ptr(arm), int(arm_uniform), int(k), int(policy), ptr(thetas), int(per_pose),
-                                          ptr(start), w, int(flags), ptr(workspace), int(workspace_bytes), *o)
+    return raw_call(solver, "rsik_solve_path", n, t, cols(p, 6), ptr(arm), int(arm_uniform), int(k), int(policy), ptr(thetas), int(per_pose),
+                    ptr(start), w, int(flags), ptr(workspace), int(workspace_bytes), *o)
 
 
 def test_arguments(torch_mod):
@@ -427,7 +324,7 @@ def test_arguments(torch_mod):
     assert bool((ws[need:] == 0x5A).all()), "a store ran past the end of the workspace"
     full = {key: v.cpu().numpy() for key, v in outs.items()}
     assert (full["index"] >= 0).sum() > 200
-    same_outputs(full, to_np(solver.solve_path(p.reshape(6, t, n), th, start)), "the caller's buffers against solve_path")
+    same_path_outputs(full, to_np(solver.solve_path(p.reshape(6, t, n), th, start)), "the caller's buffers against solve_path")
     # every output left out in turn: the same bits in the rest
     for left_out in list(ALL) + [("index", "theta"), ("index", "joints"), ("theta", "joints", "elbow")]:
         left_out = (left_out,) if isinstance(left_out, str) else left_out
@@ -436,10 +333,10 @@ def test_arguments(torch_mod):
             assert raw_path(solver, n, t, p, k, FR, th, 0, start, flags=flags, workspace=ws, **part) == _abi.RSIK_OK, (left_out, last_error(solver))
             torch.cuda.synchronize()
             keys = tuple(key for key in part if not (flags and key == "joints"))
-            same_outputs({key: v.cpu().numpy() for key, v in part.items()}, full, f"without {left_out}, flags {flags}", keys=keys)
+            same_path_outputs({key: v.cpu().numpy() for key, v in part.items()}, full, f"without {left_out}, flags {flags}", keys=keys)
     no_elbow = solver.solve_path(p.reshape(6, t, n), th, start, want_elbow=False)
     assert "elbow" not in no_elbow
-    same_outputs(to_np(no_elbow), full, "want_elbow=False", keys=tuple(key for key in ALL if key != "elbow"))
+    same_path_outputs(to_np(no_elbow), full, "want_elbow=False", keys=tuple(key for key in ALL if key != "elbow"))
 
 
 # ------------------------------------------------------------------------------------------ 9. the Python layers
@@ -465,15 +362,15 @@ def test_python_layers(torch_mod):
     p = path_soa(pos, eul, torch)
     grid = torch.linspace(0.0, 1.0, k, dtype=torch.float64)
     raw = to_np(solver.solve_path(p, grid, T(start, torch)))
-    same_outputs(res, raw, "SymbolicIK.path_batch")
+    same_path_outputs(res, raw, "SymbolicIK.path_batch")
     check_path(res, lib_sweep(solver, p, grid.cuda(), "fraction", arm, torch), t, n, "path_batch against the sweep over its grid", start)
-    same_outputs(to_np(r.path_batch(p, start, n_theta=k)), raw, "SoA poses")
+    same_path_outputs(to_np(r.path_batch(p, start, n_theta=k)), raw, "SoA poses")
     # explicit angles per waypoint, weights, both flags
     th = np.random.default_rng(62).uniform(-np.pi, np.pi, size=(3, t, n))
     w = (1, 2, 3, 4, 0.5, 0.25, 0)
     a = to_np(r.path_batch(poses, start, thetas=th, policy="explicit", weights=w, skip_projected=True, unwind=True))
     b = to_np(solver.solve_path(p, T(th, torch), T(start, torch), policy="explicit", weights=w, skip_projected=True, unwind=True))
-    same_outputs(a, b, "explicit, weights, skip_projected, unwind")
+    same_path_outputs(a, b, "explicit, weights, skip_projected, unwind")
     # plan_only: nothing launched, the re-launch reproduces the result
     out = {key: torch.full(shape, 77, dtype=dtype, device="cuda") for key, (shape, dtype) in want.items()}
     planned = r.path_batch(poses, start, n_theta=k, out=out, plan_only=True)
@@ -482,7 +379,7 @@ def test_python_layers(torch_mod):
     for again in ("", ", again"):
         planned["launch"]()
         torch.cuda.synchronize()
-        same_outputs({key: out[key].cpu().numpy() for key in want}, raw, "planned launch" + again)
+        same_path_outputs({key: out[key].cpu().numpy() for key in want}, raw, "planned launch" + again)
     # both arms
     pos, eul, arm = path_poses(21, n, t, "mixed")
     assert 0 < arm.sum() < n
@@ -490,7 +387,7 @@ def test_python_layers(torch_mod):
     d = to_np(dual.path_batch(arm, np.stack([pos, eul], axis=2), start, n_theta=k))
     raw = to_np(solver.solve_path(path_soa(pos, eul, torch), grid, T(start, torch), arm=T(arm, torch)))
     assert d["joints"].shape == (t, n, 7) and d["index"].dtype == np.int32
-    same_outputs(d, raw, "DualArmIK.path_batch")
+    same_path_outputs(d, raw, "DualArmIK.path_batch")
     # what the Python driver refuses before any launch, by its whole text
     refused = {
         "policy must be 'fraction' or 'explicit'": lambda: solver.solve_path(p, grid, policy="interval0"),

@@ -7,61 +7,24 @@ the checker alone by tests/test_solve_sweep_abi.py): reachable / state / project
 elbow pitch is 0 compared through j2 + j6 modulo 2 pi (joints_close).  Sizes are the smallest at which the kernel can go wrong:
 several 256-pose blocks with a ragged last block and a ragged last wave, r and l alternating inside every wave.
 """
-import ctypes as C
-
 import numpy as np
 import pytest
 
+from checker_support import ELBOW_LIMIT, reachable_rich
+from compare import bits, close, joints_close, same_bits
+from gpu_support import KINDS, T, abi, arm_kwargs, cols, last_error, make_symbolic, orc, ptr, raw_call, soa, to_np, torch_mod  # noqa: F401
+from sampling_support import PER_POSE, check_against_solve, solve_columns
 from sweep_workload import columns, expected_tiled, fraction_theta, sweep_poses, sweep_thetas
-from test_gpu_parity import TOL, make_symbolic, orc, soa, to_np, torch_mod  # noqa: F401
-from test_gpu_solver_state import T, arm_kwargs, close, joints_close, last_error, ptr, reachable_rich, same_bits
-from test_solver_state_checker import ELBOW_LIMIT, bits
 
 pytestmark = pytest.mark.gpu
 
-KINDS = ("r", "l", "mixed")
-PER_SAMPLE = ("joints", "elbow")
-PER_POSE = ("interval", "reachable", "state")
-
-
-def abi():
-    from reachy2_symbolic_ik_amd import _abi
-
-    return _abi
 
 
 def raw_sweep(solver, n, p, k, policy, thetas, per_pose, arm=None, arm_uniform=0, prev=None, joints=None, elbow=None,
               projected=None, theta=None, interval=None, reachable=None, state=None):
     """rsik_solve_sweep on the caller's own buffers: returns the ABI's code."""
-    import torch
-
-    cols = None if p is None else (C.c_void_p * 6)(*[p[c].data_ptr() for c in range(6)])
-    with torch.cuda.device(solver.device):
-        solver._bind_stream()
-        return solver.lib.rsik_solve_sweep(solver._h, n, cols, ptr(arm), int(arm_uniform), int(k), int(policy), ptr(thetas),
-                                           int(per_pose), ptr(prev), ptr(joints), ptr(elbow), ptr(projected), ptr(theta),
-                                           ptr(interval), ptr(reachable), ptr(state))
-
-
-def solve_columns(solver, p, policy, th_cols, torch, prev=None, **arm_kw):
-    """The reference the entry point is defined against: one rsik_solve (rsik_solve_rows with `prev`) per theta column."""
-    outs = [to_np(solver.solve(p, theta_policy=abi().THETA_FRACTION if policy == "fraction" else abi().THETA_EXPLICIT,
-                               theta_in=T(col, torch), previous_joints_rows=prev, **arm_kw)) for col in th_cols]
-    ref = {key: np.stack([o[key] for o in outs]) for key in PER_SAMPLE}
-    for key in PER_POSE:
-        for o in outs[1:]:
-            np.testing.assert_array_equal(o[key], outs[0][key])
-        ref[key] = outs[0][key]
-    return ref
-
-
-def check_against_solve(got, ref, what):
-    for key in PER_SAMPLE + PER_POSE:
-        assert got[key].shape == ref[key].shape, (what, key, got[key].shape, ref[key].shape)
-        if got[key].dtype == np.float64:
-            same_bits(got[key], ref[key], f"{what} {key}")
-        else:
-            np.testing.assert_array_equal(got[key], ref[key], err_msg=f"{what} {key}")
+    return raw_call(solver, "rsik_solve_sweep", n, cols(p, 6), ptr(arm), int(arm_uniform), int(k), int(policy), ptr(thetas), int(per_pose),
+                    ptr(prev), ptr(joints), ptr(elbow), ptr(projected), ptr(theta), ptr(interval), ptr(reachable), ptr(state))
 
 
 # ------------------------------------------------------------------------------------------ 1. each sample is rsik_solve's row

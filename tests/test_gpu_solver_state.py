@@ -13,35 +13,27 @@ reachable / state / projection flag bit-exact, numbers within TOL = 1e-9 row by 
 (max < NORTH_STAR_TOL, 0.9999-quantile < 1e-9).  Exact-singular rows (elbow pitch 0) are compared like check_symbolic does:
 j2 + j6 modulo 2 pi.  Every figure is printed before it is asserted (pytest -s shows them).
 """
-import ctypes as C
 import os
 
 import numpy as np
 import pytest
 
-from test_gpu_parity import NORTH_STAR_TOL, TOL, make_symbolic, orc, soa, to_np, torch_mod  # noqa: F401
-from test_solver_state_checker import ELBOW_LIMIT, CheckerRows, bits, state_workload
+import scale_inputs as SC
+from checker_support import ELBOW_LIMIT, CheckerRows, _check_scale_set, reachable_rich, state_workload
+from compare import NORTH_STAR_TOL, close, joints_close, same_bits
+from fk_numpy import forward_kinematics
+from gpu_support import (KINDS, T, _bits_equal, _rows_except, arm_kwargs, cols, last_error, make_symbolic, orc, ptr, raw_call, soa,  # noqa: F401
+                         to_np, torch_mod)
+from rotations import euler_to_matrix
 
 pytestmark = pytest.mark.gpu
 
-KINDS = ("r", "l", "mixed")
 NTHREADS = min(16, os.cpu_count() or 1)
 SHOULDER = {0: np.array([0.0, -0.2, 0.0]), 1: np.array([0.0, 0.2, 0.0])}
 SHOULDER_OFFSET_DEG = {0: [-15, 0, 10], 1: [15, 0, -10]}
 
 
 # ------------------------------------------------------------------------------------------ helpers
-def T(a, torch):
-    return torch.as_tensor(np.ascontiguousarray(a)).cuda()
-
-
-def arm_kwargs(kind, arm, torch):
-    """How an arrangement reaches the ABI: arm = NULL + arm_uniform (kernel<false>) or one byte per row (kernel<true>)."""
-    if kind == "mixed":
-        return dict(arm=T(arm, torch))
-    return dict(arm=None, arm_uniform=int(kind == "l"))
-
-
 def workload(kind, seed, n):
     pos, eul, arm = state_workload(seed, n, arm={"r": 0, "l": 1, "mixed": None}[kind])
     if kind == "mixed" and n >= 512:
@@ -50,82 +42,24 @@ def workload(kind, seed, n):
     return pos, eul, arm
 
 
-def reachable_rich(seed, n, arm):
-    """The poses of test_ragged_sizes_match_checker (most of them reachable), mirrored for the rows of the left arm."""
-    rng = np.random.default_rng(seed)
-    pos = np.array([0.25, -0.2, -0.15]) + rng.uniform(-0.25, 0.25, size=(n, 3))
-    eul = np.array([0, -np.pi / 2, 0]) + rng.uniform(-0.8, 0.8, size=(n, 3))
-    sgn = np.where(np.asarray(arm) == 1, -1.0, 1.0)
-    return pos * np.stack([np.ones(n), sgn, np.ones(n)], axis=1), eul * np.stack([sgn, np.ones(n), sgn], axis=1)
-
-
-def close(got, want, what, tol=TOL):
-    got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    assert np.array_equal(np.isnan(got), np.isnan(want)), f"{what}: NaN in different places"
-    err = float(np.max(np.abs(np.nan_to_num(got) - np.nan_to_num(want)), initial=0.0))
-    print(f"{what}: max err {err:.3e} over {got.shape}")
-    assert err < tol, (what, err)
-    return err
-
-
-def joints_close(got, want, what, tol=TOL):
-    """Joints; rows whose elbow pitch is 0 to rounding (fully extended arm) define only j2 + j6, modulo 2 pi (check_symbolic)."""
-    sing = np.abs(want[:, 3]) < 1e-12
-    close(got[~sing], want[~sing], what, tol)
-    if sing.any():
-        a, b = got[sing], want[sing]
-        close(a[:, [0, 1, 3, 4, 5]], b[:, [0, 1, 3, 4, 5]], what + " (singular rows)", tol)
-        dsum = (a[:, 2] + a[:, 6]) - (b[:, 2] + b[:, 6])
-        err = float(np.max(np.abs(dsum - 2 * np.pi * np.round(dsum / (2 * np.pi)))))
-        print(f"{what}: {int(sing.sum())} singular rows, j2 + j6 err {err:.3e}")
-        assert err < 1e-7, (what, err)
-
-
-def same_bits(got, want, what):
-    np.testing.assert_array_equal(bits(got), bits(want), err_msg=what)
-
-
 def inside(interval, u):
     a, b = interval[:, 0], interval[:, 1].copy()
     b[a > b] += 2 * np.pi
     return a + u * (b - a)
 
 
-def ptr(t):
-    return None if t is None else t.data_ptr()
-
-
 def raw_reach(solver, n, p, st, arm=None, arm_uniform=0, no_limits=0, interval=None, reachable=None, state=None):
     """rsik_reach_state on the caller's own buffers (the wrapper allocates its outputs): returns the ABI's code."""
-    import torch
-
-    cols = None if p is None else (C.c_void_p * 6)(*[p[k].data_ptr() for k in range(6)])
-    with torch.cuda.device(solver.device):
-        solver._bind_stream()
-        return solver.lib.rsik_reach_state(solver._h, n, cols, ptr(arm), int(arm_uniform), int(no_limits), ptr(st),
-                                           ptr(interval), ptr(reachable), ptr(state))
+    return raw_call(solver, "rsik_reach_state", n, cols(p, 6), ptr(arm), int(arm_uniform), int(no_limits), ptr(st), ptr(interval),
+                    ptr(reachable), ptr(state))
 
 
 def raw_joints(solver, n, st, theta, arm=None, arm_uniform=0, prev=None, joints=None, elbow=None):
-    import torch
-
-    with torch.cuda.device(solver.device):
-        solver._bind_stream()
-        return solver.lib.rsik_joints_from_state(solver._h, n, ptr(st), ptr(arm), int(arm_uniform), ptr(theta), ptr(prev),
-                                                 ptr(joints), ptr(elbow))
+    return raw_call(solver, "rsik_joints_from_state", n, ptr(st), ptr(arm), int(arm_uniform), ptr(theta), ptr(prev), ptr(joints), ptr(elbow))
 
 
 def raw_elbow(solver, n, st, theta, elbow):
-    import torch
-
-    with torch.cuda.device(solver.device):
-        solver._bind_stream()
-        return solver.lib.rsik_elbow_from_state(solver._h, n, ptr(st), ptr(theta), ptr(elbow))
-
-
-def last_error(solver):
-    return (solver.lib.rsik_last_error(solver._h) or b"").decode()
+    return raw_call(solver, "rsik_elbow_from_state", n, ptr(st), ptr(theta), ptr(elbow))
 
 
 def check_reach(rs, ref, what):
@@ -576,9 +510,6 @@ def test_scale_digests_of_the_reference_through_the_state_path(golden_dir, torch
     before filtering (1 Mi poses per arm, every outcome) reproduces the SHA-256 of its reachable / state arrays, and with
     joints_from_state(interval[0]) every 64th row's interval and joints."""
     torch = torch_mod
-    from tests import scale_inputs as SC
-    from tests.test_oracle_golden import _check_scale_set
-
     g = np.load(os.path.join(golden_dir, "g14_scale.npz"))
     solver, _, _ = make_symbolic(0.03)
     for a, arm in enumerate(("r_arm", "l_arm")):
@@ -592,15 +523,6 @@ def test_scale_digests_of_the_reference_through_the_state_path(golden_dir, torch
 
 
 # ------------------------------------------------------------------------------------------ h. checker-free property
-def _rot_xyz(eul):
-    ca, sa, cb, sb, cc, sc = (f(eul[:, k]) for k in (0, 1, 2) for f in (np.cos, np.sin))
-    R = np.empty((len(eul), 3, 3))
-    R[:, 0, 0] = cc * cb; R[:, 0, 1] = cc * sb * sa - sc * ca; R[:, 0, 2] = cc * sb * ca + sc * sa
-    R[:, 1, 0] = sc * cb; R[:, 1, 1] = sc * sb * sa + cc * ca; R[:, 1, 2] = sc * sb * ca - cc * sa
-    R[:, 2, 0] = -sb; R[:, 2, 1] = cb * sa; R[:, 2, 2] = cb * ca
-    return R
-
-
 @pytest.mark.parametrize("kind", KINDS)
 def test_fk_of_the_first_get_joints_is_the_stored_goal(torch_mod, kind):
     """Only the state path exposes this: after reach_state and the FIRST joints_from_state, forward kinematics of the returned
@@ -610,8 +532,6 @@ def test_fk_of_the_first_get_joints_is_the_stored_goal(torch_mod, kind):
     clamped arm does not reach the goal).  Not a property of a second call after a projection: the reference keeps a stale
     circle there (0.1 - 0.6 m in the checker)."""
     torch = torch_mod
-    from tests.fk_numpy import forward_kinematics
-
     n = 200000
     pos, eul, arm = workload(kind, 8000 + KINDS.index(kind), n)
     kw = arm_kwargs(kind, arm, torch)
@@ -634,7 +554,7 @@ def test_fk_of_the_first_get_joints_is_the_stored_goal(torch_mod, kind):
             continue
         p_fk, R_fk = forward_kinematics(out["joints"][sel], SHOULDER[a], SHOULDER_OFFSET_DEG[a], 0.28, 0.28, 0.10)
         worst_p = max(worst_p, float(np.max(np.abs(p_fk - S[sel, 0:3]))))
-        worst_r = max(worst_r, float(np.max(np.abs(R_fk - _rot_xyz(S[sel, 3:6])))))
+        worst_r = max(worst_r, float(np.max(np.abs(R_fk - euler_to_matrix(S[sel, 3:6])))))
     print(f"{kind}: FK residual position {worst_p:.3e} m, rotation {worst_r:.3e}")
     assert worst_p < 1e-9 and worst_r < 1e-8
 
@@ -645,8 +565,6 @@ def test_rows_that_are_not_numbers_stay_in_their_rows(torch_mod):
     previous_joints and a NaN-poisoned state row change that row only; every other row — outputs and state — is bit for bit that
     of the clean launch."""
     torch = torch_mod
-    from test_gpu_hostile import _bits_equal, _rows_except
-
     n = 3000
     arm = (np.random.default_rng(70).uniform(size=n) < 0.5).astype(np.uint8)
     pos, eul = reachable_rich(71, n, arm)
@@ -739,8 +657,6 @@ def test_fk_kernels_with_an_arm_byte_per_row(torch_mod):
     for bit, the two uniform launches; forward_kinematics stays within the 1e-14 of
     test_device_forward_kinematics_matches_numpy_chain against tests/fk_numpy.py."""
     torch = torch_mod
-    from tests.fk_numpy import forward_kinematics
-
     n = 5000 + 37
     rng = np.random.default_rng(90)
     arm = (rng.uniform(size=n) < 0.5).astype(np.uint8)
@@ -761,7 +677,7 @@ def test_fk_kernels_with_an_arm_byte_per_row(torch_mod):
         close(Rm[arm == a], R_ref, f"FK rotation arm {a}", tol=1e-14)
     pos, eul, _ = state_workload(91, n)
     goal6 = soa(pos, eul, torch)
-    goal12 = T(np.concatenate([_rot_xyz(eul).reshape(n, 9).T, pos.T], axis=0), torch)
+    goal12 = T(np.concatenate([euler_to_matrix(eul).reshape(n, 9).T, pos.T], axis=0), torch)
     for goal in (goal6, goal12):
         em = solver.fk_residual(goal, jT, arm=armT).cpu().numpy()
         eu = [solver.fk_residual(goal, jT, arm_uniform=a).cpu().numpy() for a in (0, 1)]

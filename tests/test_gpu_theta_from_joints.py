@@ -2,7 +2,7 @@
 (oracle.Solver, one object per row) and the reference's own recordings (G19) — never against the code under test.
 
 Where the search's decisions agree it only adds and divides by 3 numbers below 2 pi, so theta and the bracket agree to 1e-12;
-joints and the distance use TOL, the joint tolerance of the state path (tests/test_gpu_solver_state.py).  A row whose theta
+joints and the distance use TOL, the joint tolerance of the state path (tests/compare.py).  A row whose theta
 differs is only accepted as a NEAR TIE: the replay of its search with the checker's get_joints must hold a comparison whose two
 sides are within 1e-9 (a hundred times the 1e-11 rad the project holds its joints to), and the device's theta must be what the
 search gives with that one comparison reversed; at most 1 row in 10 000.  The expected bracket of a row is looked up by the
@@ -15,69 +15,20 @@ import os
 import numpy as np
 import pytest
 
-from test_gpu_parity import TOL, URDF, make_symbolic, orc, soa, to_np, torch_mod  # noqa: F401
-from test_gpu_solver_state import KINDS, T, arm_kwargs, close, same_bits
-from test_solver_state_checker import CheckerRows, bits
-from tests import scale_inputs as SC
-from tests import theta_workload as W
+import scale_inputs as SC
+import theta_workload as W
+from checker_support import CheckerRows
+from compare import close, same_bits
+from gpu_support import EXACT, KINDS, URDF, T, arm_kwargs, check_against_checker, goal_tensor, make_symbolic, soa, to_np, torch_mod  # noqa: F401
+from oracle import oracle as orc
 
 pytestmark = pytest.mark.gpu
 
-EXACT = 1e-12
 SOS = (-1.01, 0.03)
-
-
-def goal_tensor(goal_kind, pos, eul, torch):
-    if goal_kind == "pose":
-        return soa(pos, eul, torch)
-    from reachy2_symbolic_ik_amd.control_ik import matrices_to_m12_soa
-
-    return matrices_to_m12_soa(SC.matrices_from_pose(pos, eul), torch.device("cuda", 0))
 
 
 def kind_workload(kind, n, seed=W.SEED, so=0.03):
     return W.theta_workload(seed + KINDS.index(kind), n, arm={"r": 0, "l": 1, "mixed": None}[kind], so=so)
-
-
-def check_against_checker(got, ref, so, pos, eul, arm, cur, what, pref=W.PREFERRED, arms=None):
-    """theta / bracket / joints / distance / state of a fused launch against checker_batch's answer; returns the near ties.
-    arms: the checker's (r, l) arms of the launch, the default arms with offset `so` where None."""
-    n = len(pos)
-    assert ref["ok"].all()
-    np.testing.assert_array_equal(got["state"], np.zeros(n, dtype=np.uint8), err_msg=what)
-    dth = np.abs(got["theta"] - ref["theta"])
-    print(f"{what}: theta max diff {np.nanmax(dth):.3e}, rows beyond 1e-12: {int((dth > EXACT).sum())} of {n}")
-    odd = np.flatnonzero(~(dth <= EXACT))
-    assert len(odd) <= n // 10000, (what, len(odd))
-    arms = arms or (orc_mod().Arm("r_arm", so), orc_mod().Arm("l_arm", so))
-    for i in odd:  # a mismatch that is not a near tie fails
-        p = pref[int(arm[i])]
-        base = W.replay_row(arms, pos[i], eul[i], arm[i], cur[i], p)
-        ks = [k for k, m in enumerate(base["margins"]) if m <= W.NEAR_TIE]
-        print(f"{what}: row {i} device theta {got['theta'][i]!r} checker {ref['theta'][i]!r} smallest margin {min(base['margins']):.3e}")
-        assert ks, (what, i, "theta differs and no comparison of the search is a near tie")
-        flipped = [W.replay_row(arms, pos[i], eul[i], arm[i], cur[i], p, flip=k)["theta"] for k in ks]
-        assert any(abs(t - got["theta"][i]) <= EXACT for t in flipped), (what, i)
-    same = np.ones(n, dtype=bool)
-    same[odd] = False
-    want_br = W.bracket_of(np.where(ref["shortcut"], np.nan, ref["theta"]), arm)
-    assert np.array_equal(np.isnan(want_br[:, 0]), ref["shortcut"])
-    close(got["bracket"][same], want_br[same], what + " bracket", tol=EXACT)
-    still = same & ~ref["moved"]
-    close(got["joints"][still], ref["joints"][still], what + " joints (state not moved)")
-    close(got["distance"][still], ref["distance"][still], what + " distance (state not moved)")
-    moved = np.flatnonzero(same & ref["moved"])[:256]  # the rows a projection moved: replayed evaluation by evaluation
-    if len(moved):
-        rep = [W.replay_row(arms, pos[i], eul[i], arm[i], cur[i], pref[int(arm[i])]) for i in moved]
-        close(got["joints"][moved], np.array([r["joints"] for r in rep]), what + " joints (moved rows, replayed)")
-        close(got["distance"][moved], np.array([r["distance"] for r in rep]), what + " distance (moved rows, replayed)")
-    return odd
-
-
-def orc_mod():
-    from oracle import oracle as o
-
-    return o
 
 
 # ------------------------------------------------------------------------------------------ the fused entry point, full size
@@ -322,10 +273,10 @@ def test_a_pose_is_reachable_no_limits_refuses(torch_mod):
 
     with contextlib.redirect_stdout(io.StringIO()):
         s = SymbolicIK("r_arm", projection_margin=-0.05)
-    A = orc_mod().Arm("r_arm", 0.03, ik_parameters=default_ik_parameters(), projection_margin=-0.05)
+    A = orc.Arm("r_arm", 0.03, ik_parameters=default_ik_parameters(), projection_margin=-0.05)
     pos = np.array([[2.0, -0.2, 0.0], [0.4, -0.2, -0.1]])
     eul = np.array([[0.0, -np.pi / 2, 0.0]] * 2)
-    want = [orc_mod().Solver(A).is_reachable_no_limits(pos[i], eul[i]) for i in range(2)]
+    want = [orc.Solver(A).is_reachable_no_limits(pos[i], eul[i]) for i in range(2)]
     assert want == [False, True]
     res = to_np(s.theta_from_joints_batch(soa(pos, eul, torch), np.zeros((2, 7))))
     assert res["state"].tolist() == [9, 0] and np.isnan(res["theta"][0]) and np.isnan(res["joints"][0]).all() and np.isfinite(res["theta"][1])

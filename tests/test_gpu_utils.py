@@ -7,7 +7,8 @@ import os
 import numpy as np
 import pytest
 
-from test_gpu_parity import _abi_mod, load, make_symbolic, torch_mod  # noqa: F401
+from checker_support import load
+from gpu_support import abi, make_symbolic, torch_mod  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -15,7 +16,7 @@ pytestmark = pytest.mark.gpu
 def test_utils_stages_against_reference(golden_dir, torch_mod):
     """Every helper as a batch through HipSolver.stage: outcomes exact, numbers to 1e-12 (1e-9 for the Orbita3D cone, which goes
     through two Euler conversions)."""
-    A = _abi_mod()
+    A = abi()
     g = load(golden_dir, "g18_utils.npz")
     hs, r, l = make_symbolic(0.03)
     T = lambda *cols: torch_mod.as_tensor(np.ascontiguousarray(np.column_stack(cols), dtype=np.float64)).cuda()  # noqa: E731
@@ -67,7 +68,7 @@ def test_nearest_approach_of_nearly_parallel_planes(golden_dir, torch_mod):
     The stage solves it by QR (round 5's normal equations squared the condition: 1e-4 relative at 1e-6, the advisor's finding): q agrees
     with the reference's SVD to ~1e-14 / delta relative (two backward-stable solves of a system whose condition number is 1 / delta: 3e-9
     at 1e-6, where the normal equations gave 1e-4), the found / not-found decision (Q7) exactly."""
-    A = _abi_mod()
+    A = abi()
     g = load(golden_dir, "g18_utils.npz")
     hs, r, l = make_symbolic(0.03)
     rows = g["np_in"]

@@ -8,18 +8,14 @@ import os
 import numpy as np
 import pytest
 
+import far_inputs as F
+import scale_inputs as SC
+from arm_pairs import CUSTOM, ZTIP
+from checker_support import CUSTOM_GEOMETRY, _check_scale_continuous, _check_scale_set, _check_symbolic, load
+from compare import TOL
+from fk_numpy import forward_kinematics
 from oracle import oracle as orc
-
-TOL = 1e-9
-
-
-def load(golden_dir, name):
-    return np.load(os.path.join(golden_dir, name))
-
-
-def angle_close(a, b, tol=TOL):
-    """compare angles that the reference does not wrap consistently only up to rounding (no 2pi folding!)."""
-    return np.nanmax(np.abs(a - b)) if a.size else 0.0
+from rotations import euler_to_matrix, m12_to_matrices
 
 
 @pytest.fixture(scope="module")
@@ -37,35 +33,6 @@ def test_constants(golden_dir):
                       "wrist_singularity_position", "singularity_offset", "singularity_limit_coeff", "wrist_limit",
                       "backward_limit", "projection_margin", "normal_vector_margin", "elbow_limit"):
                 np.testing.assert_allclose(a.field(f), g[f"{arm}_{tag}_{f}"], rtol=0, atol=2e-16, err_msg=f"{arm} {tag} {f}")
-
-
-def _singular_rows(g, prefix):
-    """Fully extended arm (elbow pitch == 0 to rounding): elbow yaw and wrist yaw rotate about the same
-    axis, the reference's split between them is decided by 1e-17-level rounding noise (atan2 of two
-    ~1e-17 numbers).  Only j2 + j6 is defined there; those rows are compared through that sum."""
-    j = g[prefix + "joints"]
-    return np.abs(j[:, 3]) < 1e-12
-
-
-def _check_symbolic(res, g, prefix, n_expected=None):
-    reach = g[prefix + "reachable"]
-    np.testing.assert_array_equal(res["reachable"], reach)
-    np.testing.assert_array_equal(res["state"], g[prefix + "state"])
-    m = reach.astype(bool)
-    assert np.all(np.isnan(res["joints"][~m]))
-    assert np.all(np.isnan(res["interval"][~m]))
-    sing = _singular_rows(g, prefix) & m
-    for k in ("interval", "joints", "elbow"):
-        mm = m & ~sing if k == "joints" else m
-        err = np.max(np.abs(res[k][mm] - g[prefix + k][mm])) if mm.any() else 0.0
-        assert err < TOL, f"{prefix}{k}: max err {err}"
-    if sing.any():
-        a, b = res["joints"][sing], g[prefix + "joints"][sing]
-        assert np.max(np.abs(a[:, [0, 1, 3, 4, 5]] - b[:, [0, 1, 3, 4, 5]])) < TOL
-        dsum = (a[:, 2] + a[:, 6]) - (b[:, 2] + b[:, 6])  # defined modulo 2 pi only (elbow yaw is not wrapped, Q3)
-        assert np.max(np.abs(dsum - 2 * np.pi * np.round(dsum / (2 * np.pi)))) < TOL
-    # Q2: reference returns a 3-vector elbow exactly when the projection branch fired
-    np.testing.assert_array_equal(res["projected"][m], (g[prefix + "elbow_len"][m] == 3).astype(np.uint8))
 
 
 def test_catalogue_symbolic(golden_dir, arms):
@@ -259,15 +226,6 @@ def test_control_continuous_explicit_start(golden_dir):
                 assert abs(cs.previous_theta - TH[k, i]) < 1e-9
 
 
-def m12_to_matrices(M12):
-    """[..., 12] rows (R row-major, t) -> [..., 4, 4]."""
-    M = np.zeros(M12.shape[:-1] + (4, 4))
-    M[..., :3, :3] = M12[..., :9].reshape(M12.shape[:-1] + (3, 3))
-    M[..., :3, 3] = M12[..., 9:]
-    M[..., 3, 3] = 1.0
-    return M
-
-
 def test_control_continuous_every_mode(golden_dir):
     """G12: continuous mode for constrained_mode x d_theta_max x preferred_theta ARGUMENT x DVT x start, both arms
     (control_ik.py:225-252, 350-384; utils.py:93-127, 220-264).  The arguments 0.5 and 2.0 lie outside both control
@@ -351,8 +309,6 @@ def test_python_float_mod_semantics():
 def test_forward_kinematics_of_reference_joints(golden_dir):
     """tests/fk_numpy.py (the checker-free FK used by the GPU property test) against the reference's own joints:
     FK(joints recorded from the reference) == goal pose wherever the reference does not move the goal."""
-    from tests.fk_numpy import forward_kinematics
-
     g = load(golden_dir, "g3_reachable.npz")
     for arm, s, off in (("r_arm", [0.0, -0.2, 0.0], [-15, 0, 10]), ("l_arm", [0.0, 0.2, 0.0], [15, 0, -10])):
         pos, eul, J = g[f"{arm}_pos"], g[f"{arm}_eul"], g[f"{arm}_so101_in_joints"]
@@ -370,13 +326,6 @@ def test_forward_kinematics_of_reference_joints(golden_dir):
 
 
 KINDS = ("proper", "gimbal", "skewed", "near_identity")
-
-
-def euler_to_matrix(e):
-    """Rz(yaw) Ry(pitch) Rx(roll), vectorised (symbolic_ik.py:420 from_euler("xyz"))."""
-    ca, sa, cb, sb, cc, sc = np.cos(e[:, 0]), np.sin(e[:, 0]), np.cos(e[:, 1]), np.sin(e[:, 1]), np.cos(e[:, 2]), np.sin(e[:, 2])
-    return np.stack([cc * cb, cc * sb * sa - sc * ca, cc * sb * ca + sc * sa, sc * cb, sc * sb * sa + cc * ca, sc * sb * ca - cc * sa,
-                     -sb, cb * sa, cb * ca], axis=1).reshape(-1, 3, 3)
 
 
 @pytest.mark.parametrize("kind", KINDS)
@@ -401,16 +350,6 @@ def test_matrix_edges_euler_and_control(golden_dir, kind):
         np.testing.assert_array_equal(res["reachable"], g[pre + "reachable"])
         np.testing.assert_array_equal(res["state"], g[pre + "state"])
         assert np.max(np.abs(res["joints"] - g[pre + "joints"])) < TOL
-
-
-CUSTOM_GEOMETRY = dict(  # must match oracle/gen_golden.py CUSTOM_GEOMETRY (G9)
-    ik_parameters={
-        "r_shoulder_position": np.array([0.012, -0.185, 0.021]), "r_shoulder_orientation": [-11.0, 3.5, 7.0],
-        "r_upper_arm_size": 0.305, "r_forearm_size": 0.262, "r_tip_position": np.array([0.013, -0.008, 0.094]),
-        "l_shoulder_position": np.array([0.012, 0.185, 0.021]), "l_shoulder_orientation": [11.0, 3.5, -7.0],
-        "l_upper_arm_size": 0.305, "l_forearm_size": 0.262, "l_tip_position": np.array([0.013, 0.008, 0.094]),
-    },
-    elbow_limit=115, wrist_limit=38.0, backward_limit=0.035, singularity_offset=0.05, singularity_limit_coeff=0.8)
 
 
 def test_custom_geometry(golden_dir):
@@ -440,8 +379,6 @@ def test_ztip_geometry(golden_dir):
     """G20: a second arm that is not the reference's default one and whose tip stays on the goal z axis (tests/arm_pairs.ZTIP: other
     segment lengths and limits on the default shoulder), G9's record layout and test_custom_geometry's tolerances.  The two-arm GPU
     tests (tests/test_gpu_arm_forms.py) take the checker on this geometry as their reference."""
-    from arm_pairs import ZTIP
-
     g = load(golden_dir, "g20_ztip_geometry.npz")
     ar, al = orc.Arm("r_arm", **ZTIP), orc.Arm("l_arm", **ZTIP)
     for i, (arm, a) in enumerate((("r_arm", ar), ("l_arm", al))):
@@ -597,41 +534,11 @@ def test_hostile_goals_continuous(golden_dir):
 
 
 # ------------------------------------------------------------------------------------------ G14: BASELINE sizes
-def _check_scale_set(g, pre, res, n, joints_key="joints", tol=1e-9):
-    """A G14 set against results over the same n inputs: flags and state codes by SHA-256 (and by per-state counts, which say
-    where a difference lies), every 64th row's numbers to `tol`."""
-    from tests import scale_inputs as SC
-
-    assert len(res["reachable"]) == n == int(g[pre + "n"])
-    counts = np.bincount(res["state"], minlength=9)
-    assert counts.tolist() == g[pre + "state_counts"].tolist(), (pre, counts.tolist(), g[pre + "state_counts"].tolist())
-    assert SC.sha256(res["reachable"]) == str(g[pre + "reachable_sha256"]), pre + "reachable"
-    assert SC.sha256(res["state"]) == str(g[pre + "state_sha256"]), pre + "state"
-    sub = slice(None, None, SC.SUBSAMPLE)
-    np.testing.assert_array_equal(res["reachable"][sub], g[pre + "sub_reachable"])
-    np.testing.assert_array_equal(res["state"][sub], g[pre + "sub_state"])
-    worst = 0.0
-    for key in ("interval", joints_key):
-        if pre + "sub_" + key not in g.files:
-            continue
-        want, got = g[pre + "sub_" + key], res[key][sub]
-        m = ~np.isnan(want).any(axis=1)
-        if key == "interval":
-            assert np.array_equal(m, g[pre + "sub_reachable"].astype(bool))
-        # the fully stretched arm's elbow-yaw / wrist-yaw split is atan2 of two 1e-17 numbers in the reference itself (Q23): j2 + j6
-        ok = m & ~(np.abs(want[:, 3]) < 1e-12) if key == joints_key else m
-        worst = max(worst, float(np.max(np.abs(got[ok] - want[ok]))))
-    assert worst < tol, (pre, worst)
-    return worst
-
-
 def test_scale_digests_checker_against_reference(golden_dir):
     """G14: the reference itself over configs 2 and 3 at BASELINE size (2 x 1 Mi poses with every outcome; 6.3 M candidates of
     config 3's filter; 256 Ki goal matrices through ControlIK discrete with a 64-point grid) — digests of its flags and state
     codes, every 64th row's joints.  The checker over the regenerated inputs must reproduce every digest: 'flags bit-exact'
     first-hand at 8.6 M poses, which is what lets the checker stand in for the reference at these sizes."""
-    from tests import scale_inputs as SC
-
     g = load(golden_dir, "g14_scale.npz")
     nt = max(1, os.cpu_count() or 1)
     ar, al = orc.Arm("r_arm", 0.03), orc.Arm("l_arm", 0.03)
@@ -649,31 +556,10 @@ def test_scale_digests_checker_against_reference(golden_dir):
     _check_scale_set(g, "c3_", res, SC.N_CONFIG3)
 
 
-def _check_scale_continuous(g, res, theta, latched, joints_tol=1e-7):
-    """G16 against a walk of the same trajectories: `res` = joints [n_steps, n_traj, 7], reachable, state [n_steps, n_traj]; `theta` = the
-    carried previous_theta at the end [n_traj], `latched` = the emergency stop at the end [n_traj]."""
-    from tests import scale_inputs as SC
-
-    counts = np.bincount(res["state"].ravel(), minlength=11)
-    assert counts.tolist() == g["state_counts"].tolist(), (counts.tolist(), g["state_counts"].tolist())
-    assert SC.sha256(res["reachable"]) == str(g["reachable_sha256"]) and SC.sha256(res["state"]) == str(g["state_sha256"])
-    sub = slice(None, None, SC.SUBSAMPLE_TRAJ)
-    np.testing.assert_array_equal(res["state"][:, sub], g["sub_state"])
-    err = float(np.max(np.abs(res["joints"][:, sub] - g["sub_joints"])))
-    assert err < joints_tol, err
-    assert float(np.max(np.abs(res["joints"][-1] - g["last_joints"]))) < joints_tol
-    assert float(np.max(np.abs(theta - g["last_previous_theta"]))) < 1e-9
-    np.testing.assert_array_equal(np.asarray(latched) != 0, g["emergency_stop"] != 0)
-    assert int(g["state_counts"][9:].sum()) == 0
-    return err
-
-
 def test_scale_continuous_checker_against_reference(golden_dir):
     """G16: 512 trajectories of config 5's generator x 1000 control steps through the reference's ControlIK itself (one object per
     trajectory, fake clock).  The checker's state machine over the regenerated matrices reproduces the digests of its flags and state
     codes, the recorded joints to 1e-7 (observed ~1e-12) and the carried theta to 1e-9."""
-    from tests import scale_inputs as SC
-
     g = load(golden_dir, "g16_scale_continuous.npz")
     M = SC.config5_trajectories()
     assert SC.sha256(M) == str(g["input_sha256"]), "the seeded inputs did not regenerate"
@@ -692,8 +578,6 @@ def test_scale_variants_checker_against_reference(golden_dir):
     """G17: the other arm and the other modes at scale, through the reference itself — ControlIK discrete on the l_arm mirror images of
     config 3's 256 Ki matrices with is_dvt=True (the singularity plane can bind), "low_elbow", 20 grid points; ControlIK continuous on
     the l_arm mirror images of 256 of G16's trajectories, "low_elbow", d_theta_max = 0.05.  The checker reproduces every digest."""
-    from tests import scale_inputs as SC
-
     g = load(golden_dir, "g17_scale_variants.npz")
     g0 = load(golden_dir, "g0_constants.npz")
     nt = max(1, os.cpu_count() or 1)
@@ -802,8 +686,6 @@ def test_discrete_theta_on_non_default_geometries(golden_dir):
     control kernels (tests/test_gpu_control_arm_pairs.py) take the checker's theta search on these geometries as their reference."""
     import ctypes as C
 
-    from arm_pairs import CUSTOM, ZTIP
-
     g = load(golden_dir, "g21_discrete_theta_geometry.npz")
     L = orc.lib()
     D = lambda a: np.ascontiguousarray(a, dtype=np.float64).ctypes.data_as(C.POINTER(C.c_double))  # noqa: E731
@@ -840,8 +722,6 @@ def test_far_inputs_checker_against_reference(golden_dir, arms):
     DBL_MAX and down to the smallest denormal.  The reference answers every one of them without raising; the checker answers
     the same: flags, states and the projected bit exactly, numbers within the bars of this file."""
     import hashlib
-
-    import far_inputs as F
 
     g = load(golden_dir, "g22_far_inputs.npz")
     ar, al = arms[("r_arm", F.SINGULARITY_OFFSET)], arms[("l_arm", F.SINGULARITY_OFFSET)]

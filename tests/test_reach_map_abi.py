@@ -10,9 +10,9 @@ import numpy as np
 import pytest
 
 from arm_pairs import checker_arms
+from compare import bits
 from oracle import oracle as orc
 from reach_map_workload import N_STATES, expected_map, map_case, pack_mask, rounding_bound, tile
-from test_solver_state_checker import bits
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = [("default/default", "r"), ("default/default", "l"), ("default/default", "mixed"), ("custom/custom", "mixed"),

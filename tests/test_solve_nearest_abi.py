@@ -9,15 +9,12 @@ import re
 import numpy as np
 import pytest
 
+from checker_support import default_arms
 from nearest_workload import GAP, KS, gap_condition, main_case, main_thetas, nearest_from_sweep, seeds, skip_projected_case
 from oracle import oracle as orc
 from sweep_workload import expected_tiled, sweep_poses, sweep_thetas
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def arms():
-    return (orc.Arm("r_arm", 0.03), orc.Arm("l_arm", 0.03))
 
 
 def test_nearest_entry_point_is_part_of_abi_8():
@@ -63,7 +60,7 @@ def test_a_duplicated_theta_column_gives_the_lower_sample():
     pos, eul, arm = sweep_poses("mixed", 71, n)
     thetas = sweep_thetas("explicit", True, k, n, 72)
     thetas[4] = thetas[1]
-    ref = expected_tiled(orc, arms(), pos, eul, arm, "explicit", thetas)
+    ref = expected_tiled(orc, default_arms(), pos, eul, arm, "explicit", thetas)
     ok = ref["reachable"].astype(bool)
     assert ok.sum() >= 50
     seed = np.where(ok[:, None], ref["joints"][4], seeds(n, 73))
@@ -91,10 +88,10 @@ def test_a_nan_seed_row_or_theta_is_no_candidate():
     n, k = 200, 3
     pos, eul, arm = sweep_poses("r", 75, n)
     thetas = sweep_thetas("explicit", True, k, n, 76)
-    ok_rows = np.flatnonzero(expected_tiled(orc, arms(), pos, eul, arm, "explicit", thetas)["reachable"])
+    ok_rows = np.flatnonzero(expected_tiled(orc, default_arms(), pos, eul, arm, "explicit", thetas)["reachable"])
     row = int(ok_rows[0])
     thetas[1, row] = np.nan
-    ref = expected_tiled(orc, arms(), pos, eul, arm, "explicit", thetas)
+    ref = expected_tiled(orc, default_arms(), pos, eul, arm, "explicit", thetas)
     seed = seeds(n, 77)
     seed[int(ok_rows[1]), 3] = np.nan
     exp = nearest_from_sweep(ref, seed)
@@ -110,14 +107,14 @@ def test_the_inputs_of_the_gpu_tests_satisfy_the_gap_condition(kind):
         pos, eul, arm, seed = main_case(kind, k)
         for policy in ("fraction", "explicit"):
             for per_pose in (False, True):
-                ref = expected_tiled(orc, arms(), pos, eul, arm, policy, main_thetas(policy, per_pose, k), nthreads=4)
+                ref = expected_tiled(orc, default_arms(), pos, eul, arm, policy, main_thetas(policy, per_pose, k), nthreads=4)
                 for skip in (False, True):
                     exp = nearest_from_sweep(ref, seed, skip_projected=skip)
                     gap_condition(exp, ref["reachable"], f"{kind} K {k} {policy} per_pose {per_pose} skip {skip}")
     assert GAP == 1e-9
     if kind == "mixed":  # the weights test's inputs
         pos, eul, arm, seed = main_case(kind, 8)
-        ref = expected_tiled(orc, arms(), pos, eul, arm, "fraction", main_thetas("fraction", True, 8), nthreads=4)
+        ref = expected_tiled(orc, default_arms(), pos, eul, arm, "fraction", main_thetas("fraction", True, 8), nthreads=4)
         for w in ((1, 1, 1, 1, 0, 0, 0), (0, 0, 0, 0, 2, 3, 5)):
             gap_condition(nearest_from_sweep(ref, seed, weights=w), ref["reachable"], f"weights {w}")
         unit = nearest_from_sweep(ref, seed)["index"]

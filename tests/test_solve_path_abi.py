@@ -10,6 +10,7 @@ import re
 import numpy as np
 import pytest
 
+from checker_support import default_arms
 from oracle import oracle as orc
 from path_workload import (GAP, MAIN_SHAPES, N_MAIN, SMALL_SHAPES, candidates, cost_along, flat, gap_condition, greedy_chain, path_dp,
                            path_fractions, path_poses, path_start, path_tol, transition)
@@ -18,14 +19,10 @@ from sweep_workload import expected_tiled
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def arms():
-    return (orc.Arm("r_arm", 0.03), orc.Arm("l_arm", 0.03))
-
-
 def checker_sweep(t, k, seed, kind, n=N_MAIN, thetas=None, policy="fraction"):
     pos, eul, arm = path_poses(seed, n, t, kind)
     th = path_fractions(k) if thetas is None else thetas
-    return expected_tiled(orc, arms(), flat(pos), flat(eul), np.tile(arm, t), policy, th, nthreads=4)
+    return expected_tiled(orc, default_arms(), flat(pos), flat(eul), np.tile(arm, t), policy, th, nthreads=4)
 
 
 def test_path_entry_points_are_part_of_abi_8():

@@ -9,9 +9,9 @@ import re
 import numpy as np
 import pytest
 
+from compare import bits
 from oracle import oracle as orc
 from sweep_workload import columns, expected_tiled, fraction_theta, sweep_poses, sweep_thetas
-from test_solver_state_checker import bits
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 

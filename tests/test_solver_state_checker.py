@@ -9,80 +9,9 @@ import os
 
 import numpy as np
 
+from checker_support import ELBOW_LIMIT, SHOULDER_Y, CheckerRows, _check_symbolic, state_workload
+from compare import bits
 from oracle import oracle as orc
-
-TOL = 1e-9
-SHOULDER_Y = (-0.2, 0.2)            # r, l (symbolic_ik.py:40-51)
-ELBOW_LIMIT = np.radians(127.0)     # symbolic_ik.py:72, 853-861
-
-
-def state_workload(seed, n, arm=None):
-    """The sample of the solver-state tests: positions from the smoke() box around the row's own shoulder ([0, -+0.2, 0] +- 0.6),
-    Euler angles from +-pi and one arm byte per row (0 = r, 1 = l) — random, so r and l alternate inside every 64-lane wave and
-    across every 256-thread block, or the same `arm` in every row.  Returns pos [n,3], eul [n,3], arm [n] uint8."""
-    rng = np.random.default_rng(seed)
-    box = rng.uniform(-0.6, 0.6, size=(n, 3))
-    eul = rng.uniform(-np.pi, np.pi, size=(n, 3))
-    byte = (rng.uniform(size=n) < 0.5).astype(np.uint8)
-    if arm is not None:
-        byte = np.full(n, int(arm), dtype=np.uint8)
-    pos = box + np.stack([np.zeros(n), np.where(byte == 1, SHOULDER_Y[1], SHOULDER_Y[0]), np.zeros(n)], axis=1)
-    return pos, eul, byte
-
-
-def bits(a):
-    """float64 array as its bit patterns: equality that tells -0.0 from 0.0 and takes NaN as a value."""
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-class CheckerRows:
-    """n independent solver objects of the checker (one orc_solver_t per row: slots 0-15 laid out like the device row, 16-18 the
-    elbow of the last get_joints), stepped row by row on the host the way n scalar callers of the reference would step theirs."""
-
-    def __init__(self, arm_byte, so=0.03, arms=None, init=None):
-        self.arm = np.asarray(arm_byte, dtype=np.uint8)
-        self.n = len(self.arm)
-        self.arms = arms if arms is not None else (orc.Arm("r_arm", so), orc.Arm("l_arm", so))
-        self._sv = [orc.Solver(a) for a in self.arms]
-        self.width = len(self._sv[0].buf)
-        assert self.width == 19
-        self.buf = np.zeros((self.n, self.width))
-        if init is not None:
-            self.buf[:, :init.shape[1]] = init
-
-    def solver(self, i):
-        sv = self._sv[int(self.arm[i] != 0)]
-        sv.buf = self.buf[i]          # this row's object
-        return sv
-
-    def reach(self, pos, eul, no_limits=False):
-        ok = np.zeros(self.n, dtype=np.uint8)
-        st = np.zeros(self.n, dtype=np.uint8)
-        itv = np.full((self.n, 2), np.nan)
-        for i in range(self.n):
-            sv = self.solver(i)
-            if no_limits:
-                ok[i] = sv.is_reachable_no_limits(pos[i], eul[i])
-                if ok[i]:
-                    itv[i] = (-np.pi, np.pi)
-            else:
-                o, itv[i], st[i] = sv.is_reachable(pos[i], eul[i])
-                ok[i] = o
-        return dict(reachable=ok, state=st, interval=itv)
-
-    def joints(self, theta, previous_joints=None, rows=None):
-        j = np.full((self.n, 7), np.nan)
-        e = np.full((self.n, 3), np.nan)
-        p = np.zeros(self.n, dtype=np.uint8)
-        for i in (range(self.n) if rows is None else rows):
-            j[i], e[i], p[i] = self.solver(i).get_joints(theta[i], None if previous_joints is None else previous_joints[i])
-        return dict(joints=j, elbow=e, projected=p)
-
-    def elbow(self, theta, rows=None):
-        e = np.full((self.n, 3), np.nan)
-        for i in (range(self.n) if rows is None else rows):
-            e[i] = self.solver(i).get_elbow_position(theta[i])
-        return e
 
 
 def test_batch_is_the_object_row_by_row():
@@ -110,8 +39,6 @@ def test_batch_is_the_object_row_by_row():
 def test_object_reproduces_g3(golden_dir):
     """G3 (the reference's own numbers: both arms, singularity_offset 0.03 and -1.01, theta = interval[0] and the recorded
     interior theta) through the checker's solver OBJECT, one per row, at the bar test_oracle_golden.py holds the batch to."""
-    from tests.test_oracle_golden import _check_symbolic
-
     g = np.load(os.path.join(golden_dir, "g3_reachable.npz"))
     for a, arm in enumerate(("r_arm", "l_arm")):
         pos, eul = g[f"{arm}_pos"], g[f"{arm}_eul"]

@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle as orc
-from tests import theta_workload as W
+import theta_workload as W
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ARMS = ("r_arm", "l_arm")

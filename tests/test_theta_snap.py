@@ -14,20 +14,10 @@ import math
 import numpy as np
 import pytest
 
+from compare import angle_diff, is_valid_angle
+
 PI = math.pi
 TWO_PI = 2 * math.pi
-
-
-def angle_diff(a, b):  # utils.py:486-490
-    return ((a - b) + PI) % TWO_PI - PI
-
-
-def is_valid_angle(angle, i0, i1):  # utils.py:468-474
-    if i0 % TWO_PI == i1 % TWO_PI:
-        return True
-    if i0 < i1:
-        return i0 <= angle <= i1
-    return i0 <= angle or angle <= i1
 
 
 def limit_after_wrap(theta, l0, l1):  # utils.py:98-112 (theta already wrapped to (-pi, pi])

@@ -8,6 +8,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
+from compare import angle_diff
 from oracle import oracle as orc
 
 SEED = 20261016                     # chosen on the CPU: the checker's replay finds no near tie in the subsample (see near_ties)
@@ -18,11 +19,6 @@ NEAR_TIE = 1e-9                     # two sides of a comparison of the search cl
 PREFERRED = (-4 * np.pi / 6, -np.pi + 4 * np.pi / 6)   # ControlIK.preferred_theta of r, l (control_ik.py:133-139)
 BRACKET0 = ((-np.pi, np.pi), (0.0, 2 * np.pi))          # utils.py:288-292
 NTHREADS = min(16, os.cpu_count() or 1)
-
-
-def angle_diff(a, b):
-    """utils.py:486-490 (NumPy: the same IEEE operations as the checker's fmod form for these magnitudes, to rounding)."""
-    return ((np.asarray(a) - b) + np.pi) % (2 * np.pi) - np.pi
 
 
 def distance(joints, cur):
