@@ -803,6 +803,38 @@ int rsik_fk_residual(rsik_ctx *ctx, int64_t n, int goal_kind, const double *cons
                      const uint8_t *arm, int arm_uniform, double *err);
 
 /*
+ * rsik_jacobian — how the goal frame moves when the joints move: the 6 x 7 geometric Jacobian of the chain rsik_forward_kinematics
+ * evaluates, the arm's self-motion vector and Yoshikawa's manipulability, for n rows of joints (added within ABI version 8: one symbol,
+ * no option, no workspace).  The reference has none of the three (like FK: its users take them from placo or the SDK).
+ *
+ *   joints           [n_rep][n][7] device, row-major: seven joints per row in the convention rsik_solve returns and
+ *                    rsik_forward_kinematics reads.  n_rep >= 1; n_rep == 1 is the plain [n,7] form, n_rep > 1 takes the sample-major
+ *                    joints of rsik_solve_sweep ([n_theta][n][7]) and the waypoint-major joints of rsik_solve_path in place.
+ *   arm / arm_uniform  as rsik_forward_kinematics (arm: [n], one byte per row, shared by every repetition, or NULL)
+ *   jacobian         [n_rep][n][6][7] or NULL.  Column k is the velocity of the goal frame per unit rate of joint k, in the torso
+ *                    frame: rows 0-2 d position / d q_k for the position rsik_forward_kinematics returns (the goal-frame origin, tip
+ *                    offset RSIK_C_TIPL included, not the wrist), rows 3-5 the angular velocity w_k, d R / d q_k = [w_k]x R for the
+ *                    rotation it returns.  The signs are those of the caller's joints: joint 2 (elbow yaw) turns about -x of the upper
+ *                    arm and joint 6 about the goal's own z, as the chain has them.
+ *   null_vector      [n_rep][n][7] or NULL: the signed maximal minors of J, null[i] = (-1)^i det(J without column i) — the generalised
+ *                    cross product of J's six rows, so J . null = 0, the sign is defined and the vector is continuous in the joints.
+ *                    It is NOT normalised and goes to the zero vector at a singularity (a straight elbow, joints[3] == 0) instead of to
+ *                    an arbitrary direction.  Away from singularities, where neither the elbow projection nor the elbow-limit clamp of
+ *                    the solve is active, it is parallel to d joints / d theta of rsik_solve: with the sign the tests record for both
+ *                    arms, null . d joints / d theta < 0 (the vector points the way a DEcreasing theta moves the arm).
+ *   manipulability   [n_rep][n] or NULL: sqrt(sum null[i]^2) = sqrt(det(J J^T)) (Cauchy-Binet), without forming J J^T, which
+ *                    would lose half the digits near a singularity; 0, not NaN, at a singular row.
+ * Any output may be NULL, and the bits of an output do not depend on which others were requested.  A row with a NaN or an infinity
+ * among its joints gives NaN in every output of that row and changes no other row ("Rows that are not numbers" above); a finite
+ * angle of any size is answered like the angle of [-pi, pi] it is congruent to, to 1e-9.
+ * n == 0 launches nothing; n < 0, n_rep < 1, joints == NULL or all three outputs NULL give RSIK_E_INVALID, the arm checks and their
+ * codes are rsik_forward_kinematics' (RSIK_E_NOT_SET included).  Enqueued on the context's stream; allocates nothing and never waits
+ * for the device.
+ */
+int rsik_jacobian(rsik_ctx *ctx, int64_t n, int64_t n_rep, const double *joints, const uint8_t *arm, int arm_uniform,
+                  double *jacobian, double *null_vector, double *manipulability);
+
+/*
  * Multi-GPU.  Poses are independent, so a job is sharded across the GPUs of a node — one process and one
  * rsik context per GPU — with no data-path collective; the only exchange is the all-gather of the final arrays
  * (joints [n,7], state [n]) over RCCL / xGMI.  The reference has nothing distributed (single-threaded Python).  Python

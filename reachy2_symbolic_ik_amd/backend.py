@@ -834,6 +834,50 @@ class HipSolver:
         self._call("rsik_fk_residual", n, kind, self._cols(goal_soa, rows), _ptr(joints), _ptr(arm), int(arm_uniform), _ptr(err))
         return err
 
+    # ------------------------------------------------------------------ rsik_jacobian
+    JACOBIAN_OUTPUTS = ("jacobian", "null_vector", "manipulability")
+
+    def jacobian(
+        self,
+        joints: torch.Tensor,
+        arm: Optional[torch.Tensor] = None,
+        arm_uniform: int = 0,
+        want: Sequence[str] = JACOBIAN_OUTPUTS,
+        out: Optional[Dict[str, torch.Tensor]] = None,
+        plan_only: bool = False,
+    ) -> Dict[str, torch.Tensor]:
+        """How the goal frame moves with the joints, from one launch (rsik_jacobian).  joints: [n, 7], or [n_rep, n, 7] — the
+        sample-major joints of solve_sweep, the waypoint-major joints of solve_path — in the convention solve() returns and
+        forward_kinematics() reads.  arm: [n] u8, one byte per row, shared by every repetition, or None with arm_uniform.
+        `want`: which of the three outputs to compute, at least one; the bits of one do not depend on the others.  Returns device
+        tensors shaped like the joints' leading dimensions:
+        jacobian [..., 6, 7]: column k is the goal frame's velocity per unit rate of joint k in the torso frame, rows 0-2 the
+        derivative of forward_kinematics' position (tip offset included), rows 3-5 the angular velocity w_k, dR/dq_k = [w_k]x R;
+        null_vector [..., 7]: the signed minors of J, null[i] = (-1)^i det(J without column i): J . null = 0, the sign is defined,
+        the vector is continuous, not normalised, and the zero vector at a singularity; away from singularities and from the
+        elbow projection and the elbow-limit clamp it is parallel to d joints / d theta of solve();
+        manipulability [...]: |null| = sqrt(det(J J^T)), Yoshikawa's measure; 0, not NaN, at a singular row.
+        A row that holds a NaN or an infinity gives NaN in all three.
+        plan_only=True launches nothing and adds res["launch"], a zero-overhead re-launch callable (see plan())."""
+        if not isinstance(joints, torch.Tensor):
+            joints = torch.as_tensor(np.asarray(joints, dtype=np.float64))
+        if joints.dim() not in (2, 3) or joints.shape[-1] != 7:
+            raise ValueError("joints must have shape [n, 7] or [n_rep, n, 7]")
+        lead = tuple(int(v) for v in joints.shape[:-1])
+        n_rep, n = (1, lead[0]) if len(lead) == 1 else lead
+        if n_rep < 1:
+            raise ValueError("joints: at least one repetition")
+        want = tuple(want)
+        if not want or any(name not in self.JACOBIAN_OUTPUTS for name in want):
+            raise ValueError(f"want must name at least one of {self.JACOBIAN_OUTPUTS}")
+        joints = self._dev_f64(joints, lead + (7,), "joints")
+        arm = self._arm_ids(arm, n)
+        shapes = {"jacobian": lead + (6, 7), "null_vector": lead + (7,), "manipulability": lead}
+        res = {name: self._out_buf(out, name, shapes[name], _F64) for name in self.JACOBIAN_OUTPUTS if name in want}
+        cargs = (n, n_rep, _ptr(joints), _ptr(arm), int(arm_uniform),
+                 _ptr(res.get("jacobian")), _ptr(res.get("null_vector")), _ptr(res.get("manipulability")))
+        return self._finish(res, "rsik_jacobian", cargs, plan_only, (joints, arm))
+
     # ------------------------------------------------------------------ measurement hooks
     def clock_monitor(self, seconds: float, n_waves: int = 64, stream: Optional[torch.cuda.Stream] = None):
         """Starts rsik_debug_math op 8 on `stream` (a side stream, so that it runs BESIDE whatever the main stream is

@@ -38,6 +38,7 @@
 #include "rsik_kernel_nearest.hpp"
 #include "rsik_kernel_path.hpp"
 #include "rsik_kernel_reach_map.hpp"
+#include "rsik_kernel_jacobian.hpp"
 
 // =====================================================================================
 // C ABI
@@ -981,6 +982,39 @@ int rsik_fk_residual(rsik_ctx* ctx, int64_t n, int goal_kind, const double* cons
     if (rc != RSIK_OK) return rc;
     K.goal_kind = goal_kind; K.joints = joints; K.err = err;
     return launch_fk(ctx, K, n, arm, arm_uniform, "rsik_fk_residual");
+}
+
+int rsik_jacobian(rsik_ctx* ctx, int64_t n, int64_t n_rep, const double* joints, const uint8_t* arm, int arm_uniform,
+                  double* jacobian, double* null_vector, double* manipulability) {
+    if (!ctx) return RSIK_E_INVALID;
+    const char* who = "rsik_jacobian";
+    if (n < 0) return fail(ctx, RSIK_E_INVALID, "rsik_jacobian: n < 0");
+    if (n_rep < 1) return fail(ctx, RSIK_E_INVALID, "rsik_jacobian: n_rep < 1");
+    if (n == 0) return RSIK_OK;
+    if (!joints || (!jacobian && !null_vector && !manipulability))
+        return fail(ctx, RSIK_E_INVALID, "rsik_jacobian: joints or all three outputs are NULL");
+    int rc = check_arms(ctx, arm, arm_uniform, who);
+    if (rc != RSIK_OK) return rc;
+    rsik::JacobianArgs K;
+    K.n = n;
+    K.arm = arm;
+    bind_arms(ctx, arm, arm_uniform, K.arms);
+    dim3 grid, block(rsik::kBlock);
+    if ((rc = launch_begin(ctx, n, &grid, who)) != RSIK_OK) return rc;
+    // the repetition is the grid's y, which holds 65535: more repetitions than that go in as many launches, each on its own slice
+    for (int64_t rep0 = 0; rep0 < n_rep; rep0 += 65535) {
+        const int64_t first = rep0 * n;
+        grid.y = (unsigned)std::min<int64_t>(n_rep - rep0, 65535);
+        K.joints = joints + first * 7;
+        K.jacobian = jacobian ? jacobian + first * 42 : nullptr;
+        K.null_vector = null_vector ? null_vector + first * 7 : nullptr;
+        K.manipulability = manipulability ? manipulability + first : nullptr;
+        with_bool(arm != nullptr, [&](auto MIXED) { with_bool(jacobian != nullptr, [&](auto WJ) { with_bool(null_vector != nullptr, [&](auto WN) {
+            with_bool(manipulability != nullptr, [&](auto WM) {
+                if constexpr (WJ() || WN() || WM())
+                    hipLaunchKernelGGL((rsik::jacobian_kernel<MIXED(), WJ(), WN(), WM()>), grid, block, 0, ctx->stream, K); }); }); }); });
+    }
+    return launch_end(ctx);
 }
 
 int rsik_debug_math(rsik_ctx* ctx, int op, int64_t n, const double* a, const double* b, double* out0, double* out1) {

@@ -449,6 +449,25 @@ class SymbolicIK:
         j = torch.as_tensor(joints, dtype=torch.float64).to(self._solver.device)
         return self._solver.forward_kinematics(j.reshape(-1, 7).contiguous(), arm_uniform=self.arm_id)
 
+    def jacobian_batch(self, joints: Any, want: Sequence[str] = HipSolver.JACOBIAN_OUTPUTS,
+                       out: Optional[Dict[str, torch.Tensor]] = None, plan_only: bool = False) -> Dict[str, torch.Tensor]:
+        """How this arm's goal frame moves when its joints move, in one launch (HipSolver.jacobian, rsik_jacobian).
+        joints: [n,7], or [K,n,7] as sweep_batch and path_batch return them (judged in place), in the convention solve_batch returns
+        and forward_kinematics_batch reads.  want: which outputs to compute; the bits of one do not depend on the others.
+        Returns device tensors:
+        jacobian [...,6,7]: column k is the velocity of the goal frame per unit rate of joint k in the torso frame; rows 0-2 are
+        d position / d q_k of the position forward_kinematics_batch returns (the goal-frame origin, tip offset included, not the
+        wrist), rows 3-5 the angular velocity w_k, d R / d q_k = [w_k]x R; the signs are those of the caller's joint convention.
+        null_vector [...,7]: the signed minors of J, null[i] = (-1)^i det(J without column i) — the generalised cross product of J's
+        six rows: J . null = 0, the sign is defined and the vector is continuous in the joints; it is not normalised and is the
+        zero vector at a singularity.  Away from singularities, where neither the elbow projection nor the elbow-limit clamp is
+        active, it is parallel to d joints / d theta of solve_batch: the arm's self-motion.
+        manipulability [...]: sqrt(sum null[i]^2) = sqrt(det(J J^T)), Yoshikawa's measure, without forming J J^T; 0, not NaN, at a
+        singular row such as a straight elbow (joints[3] == 0).
+        A row with a NaN or an infinity among its joints is NaN in every output; a finite angle of any size is answered like the
+        angle of [-pi, pi] it is congruent to."""
+        return _jacobian_batch(self, {"arm_uniform": self.arm_id}, joints, want, out, plan_only)
+
     def fk_residual_batch(self, poses: Any, joints: Any) -> torch.Tensor:
         """err [n,2] = (position error m, rotation error rad) of FK(joints) against the poses they were solved for."""
         self._upload()
@@ -541,6 +560,11 @@ def _reach_map_batch(ik, arm, positions, orientations, want, out, plan_only):
     return ik._solver.reach_map(pos, eul, want=want, out=out, plan_only=plan_only, **arm)
 
 
+def _jacobian_batch(ik, arm, joints, want, out, plan_only):
+    ik._upload()
+    return ik._solver.jacobian(joints, want=want, out=out, plan_only=plan_only, **arm)
+
+
 def unpack_reach_mask(mask: torch.Tensor, n_rot: int) -> torch.Tensor:
     """The `mask` of reach_map_batch / HipSolver.reach_map, [n_pos, ceil(n_rot/64)] int64, as a bool tensor [n_pos, n_rot]:
     entry (i, j) is pose (i, j)'s reachable flag."""
@@ -608,6 +632,15 @@ class DualArmIK:
         """SymbolicIK.reach_map_batch for positions of both arms (arm_ids [n_pos] uint8, one byte per POSITION): every position
         with every orientation, reduced per position (count [n_pos] int32, state_count [n_pos,11], theta_measure, mask)."""
         return _reach_map_batch(self, {"arm": arm_ids}, positions, orientations, want, out, plan_only)
+
+    def jacobian_batch(self, arm_ids: Any, joints: Any, want: Sequence[str] = HipSolver.JACOBIAN_OUTPUTS,
+                       out: Optional[Dict[str, torch.Tensor]] = None, plan_only: bool = False) -> Dict[str, torch.Tensor]:
+        """SymbolicIK.jacobian_batch for rows of both arms (arm_ids [n] uint8, one byte per row, shared by every repetition of
+        joints [K,n,7]): jacobian [...,6,7] (column k: the goal frame's velocity per unit rate of joint k, rows 0-2 d position /
+        d q_k, rows 3-5 the angular velocity, torso frame), null_vector [...,7] (the signed minors of J, (-1)^i det(J without column
+        i): J . null = 0, signed, continuous, not normalised, zero at a singularity, parallel to d joints / d theta of the solve),
+        manipulability [...] (its norm = sqrt(det(J J^T)); 0, not NaN, at a singular row)."""
+        return _jacobian_batch(self, {"arm": arm_ids}, joints, want, out, plan_only)
 
     def theta_from_joints_batch(self, arm_ids: Any, poses: Any, current_joints: Any, preferred_theta: Optional[Sequence[float]] = None,
                                 out: Optional[Dict[str, torch.Tensor]] = None, plan_only: bool = False) -> Dict[str, torch.Tensor]:
