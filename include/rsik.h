@@ -835,6 +835,44 @@ int rsik_jacobian(rsik_ctx *ctx, int64_t n, int64_t n_rep, const double *joints,
                   double *jacobian, double *null_vector, double *manipulability);
 
 /*
+ * rsik_joint_rates — the joint rates that give the goal frame a wanted twist: the damped least-squares solve on the Jacobian of
+ * rsik_jacobian, for n rows, from one launch in which the Jacobian never leaves the registers (added within ABI version 8: one
+ * symbol, no option, no workspace).  Resolved-rate teleoperation, velocity feed-forward beside the continuous mode, the Newton step
+ * of a trajectory optimiser.  The reference has nothing of the kind.
+ *
+ *   joints, n_rep, arm / arm_uniform   exactly as rsik_jacobian: joints [n_rep][n][7], arm [n] shared by every repetition or NULL;
+ *                    n_rep > 1 takes a sweep's or a path's joints in place
+ *   twist            [n_rep][n][6] device, in the row order of the Jacobian: entries 0-2 the linear velocity of the goal-frame origin,
+ *                    entries 3-5 the angular velocity, torso frame
+ *   damping_host     lambda for every row when damping == NULL: finite and > 0 (and its square a normal double: 1.5e-154 < lambda <
+ *                    1.3e154), otherwise RSIK_E_INVALID.  Not read when damping is given.
+ *   damping          [n_rep][n] device or NULL: lambda per row, e.g. derived with torch from rsik_jacobian's manipulability
+ *   bias_rates       [n_rep][n][7] device or NULL for zeros: the rates q0 the arm would like to have — joint centring, or a
+ *                    self-motion command such as k * null_vector
+ *   rates            [n_rep][n][7] or NULL
+ *   achieved_twist   [n_rep][n][6] or NULL: J . rates, which differs from twist by the damping
+ * Definition, per row, with J the Jacobian rsik_jacobian defines for that row:
+ *     rates = argmin over q' of  |J q' - twist|^2 + lambda^2 |q' - q0|^2,
+ * computed as rates = q0 + J^T y with (J J^T + lambda^2 I) y = twist - J q0.  The 6 x 6 system is solved by an L D L^T factorisation
+ * (Cholesky without square roots) in natural order, every sum in a fixed order.  Every pivot is clamped from below at lambda^2: the
+ * exact pivots are Schur complements of J J^T, which is positive semi-definite, plus lambda^2, so they are never smaller and the clamp
+ * never changes an exact result; it is what makes a finite row give finite outputs at a straight elbow and with a tiny lambda, where
+ * rounding alone could produce a pivot of zero or below.
+ * lambda = 0 is not offered: lambda = 1e-6 is the pseudo-inverse solution to every digit that survives the solve (the two differ by
+ * lambda^2 / sigma^2 relative, 1e-12 / sigma^2, below what the conditioning of J J^T leaves), and it stays defined at a singularity,
+ * where the pseudo-inverse is not.
+ * Either output may be NULL, both NULL is RSIK_E_INVALID; the bits of one do not depend on whether the other was requested.  A NaN or
+ * an infinity among the row's joints, twist or bias, or a damping entry that is NaN, infinite or <= 0, makes every output of that
+ * row NaN and changes no other row ("Rows that are not numbers" above); a finite angle of any size is answered like the angle of
+ * [-pi, pi] it is congruent to.
+ * n == 0 launches nothing; n < 0, n_rep < 1, joints == NULL or twist == NULL give RSIK_E_INVALID, the arm checks and their codes are
+ * rsik_jacobian's (RSIK_E_NOT_SET included).  Enqueued on the context's stream; allocates nothing and never waits for the device.
+ */
+int rsik_joint_rates(rsik_ctx *ctx, int64_t n, int64_t n_rep, const double *joints, const uint8_t *arm, int arm_uniform,
+                     const double *twist, double damping_host, const double *damping, const double *bias_rates,
+                     double *rates, double *achieved_twist);
+
+/*
  * Multi-GPU.  Poses are independent, so a job is sharded across the GPUs of a node — one process and one
  * rsik context per GPU — with no data-path collective; the only exchange is the all-gather of the final arrays
  * (joints [n,7], state [n]) over RCCL / xGMI.  The reference has nothing distributed (single-threaded Python).  Python

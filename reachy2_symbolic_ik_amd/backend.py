@@ -878,6 +878,64 @@ class HipSolver:
                  _ptr(res.get("jacobian")), _ptr(res.get("null_vector")), _ptr(res.get("manipulability")))
         return self._finish(res, "rsik_jacobian", cargs, plan_only, (joints, arm))
 
+    # ------------------------------------------------------------------ rsik_joint_rates
+    JOINT_RATES_OUTPUTS = ("rates", "achieved_twist")
+
+    def joint_rates(
+        self,
+        joints: torch.Tensor,
+        twist: torch.Tensor,
+        damping: Any = None,
+        bias_rates: Optional[torch.Tensor] = None,
+        arm: Optional[torch.Tensor] = None,
+        arm_uniform: int = 0,
+        want: Sequence[str] = ("rates",),
+        out: Optional[Dict[str, torch.Tensor]] = None,
+        plan_only: bool = False,
+    ) -> Dict[str, torch.Tensor]:
+        """The joint rates that give the goal frame a wanted twist, damped least squares on the Jacobian of jacobian(), from one
+        launch in which J stays in registers (rsik_joint_rates).  joints: [n, 7] or [n_rep, n, 7] as jacobian() takes them; twist:
+        the same leading shape, [..., 6], in the row order of the Jacobian (entries 0-2 the linear velocity of the goal-frame origin,
+        3-5 the angular velocity, torso frame); damping: lambda, a float (finite, > 0) for every row or a tensor [..., n] with one
+        lambda per row (e.g. derived from jacobian()'s manipulability); bias_rates: [..., 7] or None for zeros, the rates q0 the arm
+        would like to have (joint centring, or a self-motion command k * null_vector); arm / arm_uniform as jacobian().
+        Per row, rates minimises |J q' - twist|^2 + lambda^2 |q' - q0|^2; it is computed as q0 + J^T y with
+        (J J^T + lambda^2 I) y = twist - J q0, an L D L^T factorisation in natural order in which every pivot is clamped from below
+        at lambda^2 (the exact pivots are never smaller, so the pivot clamp changes no exact result; it keeps a finite row finite at a
+        straight elbow and with a tiny lambda).  lambda = 0 is not offered: 1e-6 is the pseudo-inverse to every digit that survives.
+        `want`: which of rates [..., 7] and achieved_twist [..., 6] (= J . rates, short of twist by the damping) to compute, at least
+        one; the bits of one do not depend on the other.  A row with a NaN or an infinity in joints, twist or bias, or with a lambda
+        that is NaN, infinite or <= 0, is NaN in both.
+        plan_only=True launches nothing and adds res["launch"], a zero-overhead re-launch callable (see plan())."""
+        if not isinstance(joints, torch.Tensor):
+            joints = torch.as_tensor(np.asarray(joints, dtype=np.float64))
+        if joints.dim() not in (2, 3) or joints.shape[-1] != 7:
+            raise ValueError("joints must have shape [n, 7] or [n_rep, n, 7]")
+        lead = tuple(int(v) for v in joints.shape[:-1])
+        n_rep, n = (1, lead[0]) if len(lead) == 1 else lead
+        if n_rep < 1:
+            raise ValueError("joints: at least one repetition")
+        want = tuple(want)
+        if not want or any(name not in self.JOINT_RATES_OUTPUTS for name in want):
+            raise ValueError(f"want must name at least one of {self.JOINT_RATES_OUTPUTS}")
+        if damping is None:
+            raise ValueError("damping: a float > 0 or a tensor with one lambda per row")
+        joints = self._dev_f64(joints, lead + (7,), "joints")
+        twist = self._dev_f64(twist, lead + (6,), "twist")
+        bias_rates = None if bias_rates is None else self._dev_f64(bias_rates, lead + (7,), "bias_rates")
+        if isinstance(damping, (int, float)):
+            damping_host, damping = float(damping), None
+            if not (np.isfinite(damping_host) and damping_host > 0.0):
+                raise ValueError("damping must be finite and > 0")
+        else:
+            damping_host, damping = 0.0, self._dev_f64(damping, lead, "damping")
+        arm = self._arm_ids(arm, n)
+        shapes = {"rates": lead + (7,), "achieved_twist": lead + (6,)}
+        res = {name: self._out_buf(out, name, shapes[name], _F64) for name in self.JOINT_RATES_OUTPUTS if name in want}
+        cargs = (n, n_rep, _ptr(joints), _ptr(arm), int(arm_uniform), _ptr(twist), damping_host, _ptr(damping), _ptr(bias_rates),
+                 _ptr(res.get("rates")), _ptr(res.get("achieved_twist")))
+        return self._finish(res, "rsik_joint_rates", cargs, plan_only, (joints, twist, damping, bias_rates, arm))
+
     # ------------------------------------------------------------------ measurement hooks
     def clock_monitor(self, seconds: float, n_waves: int = 64, stream: Optional[torch.cuda.Stream] = None):
         """Starts rsik_debug_math op 8 on `stream` (a side stream, so that it runs BESIDE whatever the main stream is

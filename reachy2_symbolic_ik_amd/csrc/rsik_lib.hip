@@ -39,6 +39,7 @@
 #include "rsik_kernel_path.hpp"
 #include "rsik_kernel_reach_map.hpp"
 #include "rsik_kernel_jacobian.hpp"
+#include "rsik_kernel_joint_rates.hpp"
 
 // =====================================================================================
 // C ABI
@@ -1013,6 +1014,45 @@ int rsik_jacobian(rsik_ctx* ctx, int64_t n, int64_t n_rep, const double* joints,
             with_bool(manipulability != nullptr, [&](auto WM) {
                 if constexpr (WJ() || WN() || WM())
                     hipLaunchKernelGGL((rsik::jacobian_kernel<MIXED(), WJ(), WN(), WM()>), grid, block, 0, ctx->stream, K); }); }); }); });
+    }
+    return launch_end(ctx);
+}
+
+int rsik_joint_rates(rsik_ctx* ctx, int64_t n, int64_t n_rep, const double* joints, const uint8_t* arm, int arm_uniform,
+                     const double* twist, double damping_host, const double* damping, const double* bias_rates,
+                     double* rates, double* achieved_twist) {
+    if (!ctx) return RSIK_E_INVALID;
+    const char* who = "rsik_joint_rates";
+    if (n < 0) return fail(ctx, RSIK_E_INVALID, "rsik_joint_rates: n < 0");
+    if (n_rep < 1) return fail(ctx, RSIK_E_INVALID, "rsik_joint_rates: n_rep < 1");
+    if (n == 0) return RSIK_OK;
+    if (!joints || !twist) return fail(ctx, RSIK_E_INVALID, "rsik_joint_rates: joints or twist is NULL");
+    if (!rates && !achieved_twist) return fail(ctx, RSIK_E_INVALID, "rsik_joint_rates: both outputs are NULL");
+    if (!damping && !rsik::damping_usable(damping_host))
+        return fail(ctx, RSIK_E_INVALID, "rsik_joint_rates: damping_host must be finite and > 0 (its square a normal double)");
+    int rc = check_arms(ctx, arm, arm_uniform, who);
+    if (rc != RSIK_OK) return rc;
+    rsik::JointRatesArgs K;
+    K.n = n;
+    K.arm = arm;
+    K.damping_host = damping ? 0.0 : damping_host;
+    bind_arms(ctx, arm, arm_uniform, K.arms);
+    dim3 grid, block(rsik::kBlock);
+    if ((rc = launch_begin(ctx, n, &grid, who)) != RSIK_OK) return rc;
+    // the repetition is the grid's y, as in rsik_jacobian: one launch per 65535 repetitions, each on its own slice
+    for (int64_t rep0 = 0; rep0 < n_rep; rep0 += 65535) {
+        const int64_t first = rep0 * n;
+        grid.y = (unsigned)std::min<int64_t>(n_rep - rep0, 65535);
+        K.joints = joints + first * 7;
+        K.twist = twist + first * 6;
+        K.damping = damping ? damping + first : nullptr;
+        K.bias_rates = bias_rates ? bias_rates + first * 7 : nullptr;
+        K.rates = rates ? rates + first * 7 : nullptr;
+        K.achieved_twist = achieved_twist ? achieved_twist + first * 6 : nullptr;
+        with_bool(arm != nullptr, [&](auto MIXED) { with_bool(bias_rates != nullptr, [&](auto BIAS) { with_bool(rates != nullptr, [&](auto WR) {
+            with_bool(achieved_twist != nullptr, [&](auto WA) {
+                if constexpr (WR() || WA())
+                    hipLaunchKernelGGL((rsik::joint_rates_kernel<MIXED(), BIAS(), WR(), WA()>), grid, block, 0, ctx->stream, K); }); }); }); });
     }
     return launch_end(ctx);
 }

@@ -468,6 +468,19 @@ class SymbolicIK:
         angle of [-pi, pi] it is congruent to."""
         return _jacobian_batch(self, {"arm_uniform": self.arm_id}, joints, want, out, plan_only)
 
+    def joint_rates_batch(self, joints: Any, twist: Any, damping: Any, bias_rates: Any = None, want: Sequence[str] = ("rates",),
+                          out: Optional[Dict[str, torch.Tensor]] = None, plan_only: bool = False) -> Dict[str, torch.Tensor]:
+        """The joint rates that give this arm's goal frame the twist [...,6] (linear velocity of the goal-frame origin, then angular
+        velocity, torso frame: the row order of jacobian_batch's J), in one launch (HipSolver.joint_rates, rsik_joint_rates).
+        joints: [n,7] or [K,n,7] as jacobian_batch takes them; damping: lambda > 0, a float or a tensor [...] with one per row;
+        bias_rates: [...,7] or None for zeros, the rates q0 the arm would like to have, e.g. k * null_vector.
+        Per row, rates [...,7] minimises |J q' - twist|^2 + lambda^2 |q' - q0|^2: rates = q0 + J^T y with
+        (J J^T + lambda^2 I) y = twist - J q0, solved by L D L^T in natural order with every pivot clamped from below at lambda^2
+        (the pivot clamp changes no exact result and keeps a finite row finite at a straight elbow).  achieved_twist [...,6] =
+        J . rates.  want: which of the two to compute; the bits of one do not depend on the other.  A row with a NaN or an infinity
+        in joints, twist or bias, or a lambda that is NaN, infinite or <= 0, is NaN in every output."""
+        return _joint_rates_batch(self, {"arm_uniform": self.arm_id}, joints, twist, damping, bias_rates, want, out, plan_only)
+
     def fk_residual_batch(self, poses: Any, joints: Any) -> torch.Tensor:
         """err [n,2] = (position error m, rotation error rad) of FK(joints) against the poses they were solved for."""
         self._upload()
@@ -565,6 +578,11 @@ def _jacobian_batch(ik, arm, joints, want, out, plan_only):
     return ik._solver.jacobian(joints, want=want, out=out, plan_only=plan_only, **arm)
 
 
+def _joint_rates_batch(ik, arm, joints, twist, damping, bias_rates, want, out, plan_only):
+    ik._upload()
+    return ik._solver.joint_rates(joints, twist, damping=damping, bias_rates=bias_rates, want=want, out=out, plan_only=plan_only, **arm)
+
+
 def unpack_reach_mask(mask: torch.Tensor, n_rot: int) -> torch.Tensor:
     """The `mask` of reach_map_batch / HipSolver.reach_map, [n_pos, ceil(n_rot/64)] int64, as a bool tensor [n_pos, n_rot]:
     entry (i, j) is pose (i, j)'s reachable flag."""
@@ -641,6 +659,14 @@ class DualArmIK:
         i): J . null = 0, signed, continuous, not normalised, zero at a singularity, parallel to d joints / d theta of the solve),
         manipulability [...] (its norm = sqrt(det(J J^T)); 0, not NaN, at a singular row)."""
         return _jacobian_batch(self, {"arm": arm_ids}, joints, want, out, plan_only)
+
+    def joint_rates_batch(self, arm_ids: Any, joints: Any, twist: Any, damping: Any, bias_rates: Any = None,
+                          want: Sequence[str] = ("rates",), out: Optional[Dict[str, torch.Tensor]] = None,
+                          plan_only: bool = False) -> Dict[str, torch.Tensor]:
+        """SymbolicIK.joint_rates_batch for rows of both arms (arm_ids [n] uint8, one byte per row, shared by every repetition of
+        joints [K,n,7]): rates [...,7], the minimiser of |J q' - twist|^2 + lambda^2 |q' - q0|^2 (q0 = bias_rates or zero), from
+        (J J^T + lambda^2 I) y = twist - J q0 by L D L^T with the pivot clamp at lambda^2, and achieved_twist [...,6] = J . rates."""
+        return _joint_rates_batch(self, {"arm": arm_ids}, joints, twist, damping, bias_rates, want, out, plan_only)
 
     def theta_from_joints_batch(self, arm_ids: Any, poses: Any, current_joints: Any, preferred_theta: Optional[Sequence[float]] = None,
                                 out: Optional[Dict[str, torch.Tensor]] = None, plan_only: bool = False) -> Dict[str, torch.Tensor]:
