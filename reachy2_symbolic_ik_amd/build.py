@@ -10,9 +10,9 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ["rsik_lib.hip"]
-DEPS = ["rsik_lib.hip", "rsik_kernel_solve.hpp", "rsik_kernel_discrete.hpp", "rsik_kernel_continuous.hpp", "rsik_kernel_pipeline.hpp", "rsik_kernel_stages.hpp", "rsik_kernel_theta_from_joints.hpp", "rsik_kernel_sweep.hpp", "rsik_kernel_nearest.hpp", "rsik_kernel_path.hpp", "rsik_kernel_reach_map.hpp", "rsik_kernel_jacobian.hpp", "rsik_kernel_joint_rates.hpp",
-        "rsik_kernel_state.hpp", "rsik_cont_run.hpp", "rsik_comm.hpp", "rsik_device.hpp", "rsik_math.hpp", "rsik_poly_gen.hpp",
-        os.path.join("..", "..", "include", "rsik.h")]
+# Everything the library is compiled from: every source file of csrc/ (so a header that is added is hashed without being named
+# here), and the C ABI's header.  Paths relative to csrc/.
+DEPS = sorted(f for f in os.listdir(CSRC) if f.endswith((".hip", ".hpp"))) + [os.path.join("..", "..", "include", "rsik.h")]
 OUT = os.path.join(CSRC, "librsik_hip.so")
 
 # -ffp-contract=off: the compiler never fuses on its own (HIP's default "fast" mode fuses in the backend and ignores

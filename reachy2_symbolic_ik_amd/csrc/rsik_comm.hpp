@@ -1,5 +1,6 @@
 // rsik_comm.hpp — the RCCL all-gather entry points of the C ABI (rsik_comm_*, rsik_allgather)
-// (included by rsik_lib.hip inside its extern "C" block, after the context and error helpers)
+// (a fragment by design, not a header that stands alone: host code included by rsik_lib.hip inside its extern "C" block, after the
+// context and error helpers, whose statics it uses)
 #pragma once
 
 // ------------------------------------------------------------------------------------------

@@ -1,5 +1,6 @@
 // rsik_cont_run.hpp — the host-side scheduler of rsik_control_continuous_run: plan, workspace, dependency words, issue order
-// (included by rsik_lib.hip inside its extern "C" block, after the context, the error and launch helpers and fill_continuous)
+// (a fragment by design, not a header that stands alone: host code included by rsik_lib.hip inside its extern "C" block, after the
+// context, the error and launch helpers and fill_continuous, whose statics it uses)
 //
 // The dependency graph.  Streams: the caller's (start-up and theta kernels), prepare, joints, chain (the context's own).  Kernels on
 // one stream run in issue order; what else a kernel waits for, by form — captured (events, a run recorded into a hipGraph, or variant

@@ -1,6 +1,9 @@
 // rsik_kernel_continuous.hpp — rsik_control_continuous_step: the state-carrying step kernel and the (re)initialisation kernel
-// (one translation unit: included by rsik_lib.hip, in this order, inside nothing)
 #pragma once
+
+#include "rsik_goal.hpp"
+#include "rsik_rows.hpp"
+#include "rsik_tables.hpp"
 
 namespace rsik {
 
@@ -126,7 +129,7 @@ __global__ __launch_bounds__(kBlock) void control_continuous_kernel(const Contin
     const int64_t n = K.n;
 
     __shared__ SharedTables lds_tab;
-        stage_tables<MIXED, (int)offsetof(ContinuousArgs, arms) + (MIXED ? 0 : (int)sizeof(ArmC))>(lds_tab, K.arms);
+    stage_tables<MIXED, (int)offsetof(ContinuousArgs, arms) + (MIXED ? 0 : (int)sizeof(ArmC))>(lds_tab, K.arms);
     const Acc<MIXED> A = make_acc<MIXED>(K.arms, MIXED ? (K.arm[ii] != 0) : false, lds_tab);
     const int slot = MIXED ? (A.isl ? 1 : 0) : 0;
 
@@ -236,7 +239,7 @@ __global__ __launch_bounds__(kBlock) void cont_init_kernel(const ContinuousArgs 
     const bool live = i < K.n;
     const int64_t ii = live ? i : (K.n - 1);
     __shared__ SharedTables lds_tab;
-        stage_tables<MIXED, (int)offsetof(ContinuousArgs, arms) + (MIXED ? 0 : (int)sizeof(ArmC))>(lds_tab, K.arms);
+    stage_tables<MIXED, (int)offsetof(ContinuousArgs, arms) + (MIXED ? 0 : (int)sizeof(ArmC))>(lds_tab, K.arms);
     const Acc<MIXED> A = make_acc<MIXED>(K.arms, MIXED ? (K.arm[ii] != 0) : false, lds_tab);
     const int slot = MIXED ? (A.isl ? 1 : 0) : 0;
     const int64_t n = K.n;

@@ -1,6 +1,9 @@
 // rsik_kernel_discrete.hpp — rsik_control_discrete: the theta-grid sweep and control_discrete_kernel
-// (one translation unit: included by rsik_lib.hip, in this order, inside nothing)
 #pragma once
+
+#include "rsik_goal.hpp"
+#include "rsik_rows.hpp"
+#include "rsik_tables.hpp"
 
 namespace rsik {
 
@@ -32,13 +35,6 @@ struct DiscreteArgs {
     uint8_t* emergency;
     ArmC arms[2];
 };
-
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_s_waitcnt(0xC07F);
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // Per-wave LDS slab of the discrete kernel, kDiscRows rows of 64 doubles (one per lane), so that four workgroups fit in
 // a CU's 160 KB (the staged circle geometry used to sit in its own 13-row array: 47.6 KB per workgroup, 3 per CU):
@@ -172,7 +168,7 @@ __global__ __launch_bounds__(kDiscBlock, RSIK_DISC_MIN_WAVES) RSIK_DISC_ATTR voi
 #pragma unroll
         for (int k = 0; k < 7; k++) prow.v[k] = K.prev_rows[ii * 7 + k];
     }
-        __shared__ SharedTables lds_tab;
+    __shared__ SharedTables lds_tab;
     stage_tables<MIXED, (int)offsetof(DiscreteArgs, arms) + (MIXED ? 0 : (int)sizeof(ArmC)), kDiscBlock>(lds_tab, K.arms);
 #ifdef RSIK_TIMELINE_PROBE
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (probe build only: the head ends when the twelve columns are in)
@@ -350,7 +346,7 @@ __global__ __launch_bounds__(kDiscBlock, RSIK_DISC_MIN_WAVES) RSIK_DISC_ATTR voi
     // 16 the grid search was needed (the preferred-theta shortcut failed), 32 a theta was found, 64 it took the cooperative sweep
     em = (need ? 16 : 0) | (found ? 32 : 0) | (coop ? 64 : 0);
 #endif
-    // (written through: the launch is one round of waves, its end is a fifth of it — rsik_kernel_solve.hpp, kStoreThrough)
+    // (written through: the launch is one round of waves, its end is a fifth of it — rsik_rows.hpp, kStoreThrough)
     store_rows<7, kStoreThrough>(K.joints, wave_base, K.n, lane, &lds_slab[wave][0][0], jv);
     if (live) {
         if (K.reachable) st_stream<kStoreThrough>(K.reachable + i, (uint8_t)(found ? 1 : 0));

@@ -1,7 +1,9 @@
 // rsik_kernel_jacobian.hpp — rsik_jacobian: the 6 x 7 geometric Jacobian of the goal frame, its signed maximal minors (the self-motion vector) and
 // Yoshikawa's manipulability, one (repetition, row) per lane (jacobian_kernel)
-// (one translation unit: included by rsik_lib.hip after the other kernel headers, inside nothing)
 #pragma once
+
+#include "rsik_rows.hpp"
+#include "rsik_tables.hpp"
 
 namespace rsik {
 
@@ -44,7 +46,7 @@ __device__ __forceinline__ void jac_minors3(const V3 (&v)[7], double (&m)[35]) {
 
 // (-1)^I det(J without column I): the Laplace expansion of the 6 x 6 determinant across its linear (top) and angular (bottom) three
 // rows.  The six columns left are numbered 0 ... 5 in place; each of the 20 triples p < q < r of them takes the top minor of its columns
-// times the bottom minor of the other three, with the sign (-1)^(p + q + r + 1).  Twenty fused multiply-adds in this order, no branch,
+// times the bottom minor of the other three, with the sign (-1)^(p + q + r + 1).  Twenty fused multiply-adds in that order, no branch,
 // no division: the value does not depend on anything but the two sets of minors.
 template <int I>
 __device__ __forceinline__ double jac_null_entry(const double (&top)[35], const double (&bot)[35]) {

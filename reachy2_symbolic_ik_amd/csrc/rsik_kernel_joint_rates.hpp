@@ -1,7 +1,9 @@
 // rsik_kernel_joint_rates.hpp — rsik_joint_rates: damped least-squares joint rates from a twist of the goal frame, one (repetition, row)
 // per lane (joint_rates_kernel).  The Jacobian never leaves the lane's registers.
-// (one translation unit: included by rsik_lib.hip after rsik_kernel_jacobian.hpp, inside nothing)
 #pragma once
+
+#include "rsik_rows.hpp"
+#include "rsik_tables.hpp"
 
 namespace rsik {
 
@@ -23,35 +25,6 @@ struct JointRatesArgs {
 __host__ __device__ inline bool damping_usable(double lambda) {
     const double l2 = lambda * lambda;
     return lambda > 0.0 && l2 >= 2.2250738585072014e-308 && l2 <= 1.7976931348623157e308;
-}
-
-// The counterpart of store_rows' second half, for inputs: a wave's rows of a row-major [n, W] array, one contiguous [64 * W] slab, go to
-// LDS with W coalesced loads per wave and stay there; staged_row is the lane's row of that slab (a lane past the end: the last row).
-// Between the two stands rows_staged: the LDS counter drained, the wave in lock-step.
-template <int W>
-__device__ __forceinline__ void stage_rows(const double* __restrict__ in, int64_t wave_base, int64_t n, int lane,
-                                           double* __restrict__ lds_slab) {
-    int64_t rows = n - wave_base;
-    if (rows > 64) rows = 64;
-    const int total = (int)rows * W;
-    const double* src = in + wave_base * W;
-#pragma unroll
-    for (int k = 0; k < W; k++) {
-        const int idx = k * 64 + lane;
-        if (idx < total) lds_slab[idx] = ld_stream(src + idx);
-    }
-}
-__device__ __forceinline__ void rows_staged() {
-    __builtin_amdgcn_s_waitcnt(0xC07F);
-    __builtin_amdgcn_wave_barrier();
-}
-template <int W>
-__device__ __forceinline__ void staged_row(const double* lds_slab, int64_t wave_base, int64_t n, int lane, double (&vals)[W]) {
-    int64_t rows = n - wave_base;
-    if (rows > 64) rows = 64;
-    const int mine = (lane < (int)rows ? lane : (int)rows - 1) * W;
-#pragma unroll
-    for (int k = 0; k < W; k++) vals[k] = lds_slab[mine + k];
 }
 
 // Entry (i, j), i >= j, of a symmetric 6 x 6 matrix kept as its lower triangle, row by row: 0 ... 20

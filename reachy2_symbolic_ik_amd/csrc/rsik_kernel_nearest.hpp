@@ -1,7 +1,10 @@
 // rsik_kernel_nearest.hpp — rsik_solve_nearest: is_reachable once per pose, get_joints at n_theta elbow angles, and of those the one
 // solution nearest to the pose's seed joints (solve_nearest_kernel)
-// (one translation unit: included by rsik_lib.hip after rsik_kernel_sweep.hpp, inside nothing)
 #pragma once
+
+#include "rsik_goal.hpp"
+#include "rsik_rows.hpp"
+#include "rsik_tables.hpp"
 
 namespace rsik {
 
@@ -52,25 +55,6 @@ __device__ __forceinline__ void nearest_of_group(double& c, int& k) {
         const int ok = __shfl_xor(k, off, 64);
         if (nearer(oc, ok, c, k)) { c = oc; k = ok; }
     }
-}
-
-// The first `nrows` rows of W doubles a wave has staged in LDS, written as one contiguous run (flush_rows for a wave that holds
-// PW <= 64 poses: nrows <= PW).
-template <int W, int PW>
-__device__ __forceinline__ void flush_pose_rows(double* __restrict__ out, int64_t wave_base, int nrows, int lane,
-                                                const double* __restrict__ lds_rows) {
-    __builtin_amdgcn_s_waitcnt(0xC07F);
-    __builtin_amdgcn_wave_barrier();
-    const int total = nrows * W;
-    double* dst = out + wave_base * W;
-#pragma unroll
-    for (int k = 0; k < W; k++) {
-        if (k * 64 < PW * W) {
-            const int idx = k * 64 + lane;
-            if (idx < total) st_stream(dst + idx, lds_rows[idx]);
-        }
-    }
-    __builtin_amdgcn_wave_barrier();
 }
 
 // solve_sweep_kernel's head (loads, goal stage, reach_g once per pose) and its sample (get_joints on a copy of the wrist reach_g left,
@@ -136,8 +120,7 @@ __global__ __launch_bounds__(kBlock, RSIK_NEAREST_MIN_WAVES) void solve_nearest_
                 if (idx < wave_rows * 7) lds_wave[idx] = ld_stream(src + idx);
             }
         }
-        __builtin_amdgcn_s_waitcnt(0xC07F);
-        __builtin_amdgcn_wave_barrier();
+        wave_lds_fence();
     }
     const double* seed = lds_wave + (tt - wave * PW) * 7;  // (clamped: a lane past the end reads the last pose's row, as it solves that pose)
     double* jrow = lds_wave + pw * 7;

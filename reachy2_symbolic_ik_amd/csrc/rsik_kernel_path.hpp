@@ -1,7 +1,11 @@
 // rsik_kernel_path.hpp — rsik_solve_path: n paths of n_steps waypoints, n_theta elbow angles per waypoint, and of the n_theta ^ n_steps
 // ways through them the one whose joints move least (solve_path_kernel)
-// (one translation unit: included by rsik_lib.hip after rsik_kernel_nearest.hpp, inside nothing)
 #pragma once
+
+#include "rsik_goal.hpp"
+#include "rsik_kernel_nearest.hpp"
+#include "rsik_rows.hpp"
+#include "rsik_tables.hpp"
 
 namespace rsik {
 
@@ -91,8 +95,7 @@ __device__ __forceinline__ double path_cost_at(const double (&w)[7], const doubl
     return path_cost(w, b, a);
 }
 __device__ __forceinline__ void path_lds_fence() {  // the wave's LDS writes are done before any lane reads another lane's
-    __builtin_amdgcn_s_waitcnt(0xC07F);
-    __builtin_amdgcn_wave_barrier();
+    wave_lds_fence();
     branch_stores_stay();
 }
 

@@ -1,6 +1,10 @@
 // rsik_kernel_pipeline.hpp — rsik_control_continuous_run: the four phases of the trajectory pipeline
-// (one translation unit: included by rsik_lib.hip, in this order, inside nothing)
 #pragma once
+
+#include "rsik_goal.hpp"
+#include "rsik_kernel_continuous.hpp"
+#include "rsik_rows.hpp"
+#include "rsik_tables.hpp"
 
 namespace rsik {
 
@@ -115,7 +119,7 @@ struct ContRunArgs {
     ArmC arms[2];
 };
 #define RSIK_WS(K, t, i) (K).ws[(int64_t)(t) * (K).n + (i)]
-// The pipeline's bulk stores are written through to system scope (st_stream<kStoreThrough>, rsik_kernel_solve.hpp): the end of each of
+// The pipeline's bulk stores are written through to system scope (st_stream<kStoreThrough>, rsik_rows.hpp): the end of each of
 // its kernels is what a hand-over waits for, and nothing of its output is then left dirty in the L2s for the write-back at that end
 // (-1.3 ... -1.5 % per pass in every launch form, bit-identical; non-temporal LOADS of the goal matrices cost 1-3 %: the joints phase reads
 // what the prepare phase read).  kRowStoreAux: the same policy for the raw buffer stores (sc0 | sc1).
@@ -166,7 +170,7 @@ __global__ __launch_bounds__(kBlock) RSIK_PHASED_OCC_ATTR void cont_prepare_kern
     for (int k = 0; k < 12; k++) m[k] = src[k * K.n];
     const bool lane_isl = MIXED ? (K.arm[ii] != 0) : false;
     __shared__ SharedTables lds_tab;
-        stage_tables<MIXED, (int)offsetof(ContRunArgs, arms) + (MIXED ? 0 : (int)sizeof(ArmC))>(lds_tab, K.arms);
+    stage_tables<MIXED, (int)offsetof(ContRunArgs, arms) + (MIXED ? 0 : (int)sizeof(ArmC))>(lds_tab, K.arms);
     const Acc<MIXED> A = make_acc<MIXED>(K.arms, lane_isl, lds_tab);
     const int slot = MIXED ? (A.isl ? 1 : 0) : 0;
     cont_prepare_step<MIXED, PLANE>(K, A, slot, m, t, K.t0 + t, i, live);
@@ -529,8 +533,7 @@ __device__ __forceinline__ void cont_joints_chunk(const ContRunArgs& K, SharedTa
     // first row (a block's joints stay below 2 GB, see rsik_control_continuous_run)
 #pragma unroll
     for (int k = 0; k < 7; k++) lw[lane * 7 + k] = out[k];
-    __builtin_amdgcn_s_waitcnt(0xC07F);
-    __builtin_amdgcn_wave_barrier();
+    wave_lds_fence();
     const int traj_left = (int)((n - grp * 8) < 8 ? (n - grp * 8) : 8);  // trajectories of this group that exist (<= 0 past the end)
     const int steps_left = (int)((K.T - c * kJointChunk) < kJointChunk ? (K.T - c * kJointChunk) : kJointChunk);
     const __amdgpu_buffer_rsrc_t obuf = row_buffer(K.joints + ((K.t0 + c * kJointChunk) * n + grp * 8) * 7);
@@ -834,7 +837,7 @@ __global__ __launch_bounds__(kChainBlock) __attribute__((amdgpu_waves_per_eu(1, 
     __builtin_amdgcn_s_setprio(2);
     const int64_t gid = (int64_t)blockIdx.x * kChainBlock + threadIdx.x;
     __shared__ SharedTables lds_tab;
-        stage_tables<MIXED, (int)offsetof(ContRunArgs, arms) + (MIXED ? 0 : (int)sizeof(ArmC)), kChainBlock>(lds_tab, K.arms);
+    stage_tables<MIXED, (int)offsetof(ContRunArgs, arms) + (MIXED ? 0 : (int)sizeof(ArmC)), kChainBlock>(lds_tab, K.arms);
     cont_chain_walk<MIXED, kChainBatch>(K, lds_tab, gid >> 3, (int)(gid & 7), 0, K.t0, K.T, K.last_block != 0);
 }
 

@@ -1,6 +1,8 @@
 // rsik_kernel_reach_map.hpp — rsik_reach_map: is_reachable of n_pos positions x n_rot orientations, reduced per position on the device (reach_map_kernel)
-// (one translation unit: included by rsik_lib.hip after the other kernel headers, inside nothing)
 #pragma once
+
+#include "rsik_goal.hpp"
+#include "rsik_tables.hpp"
 
 namespace rsik {
 

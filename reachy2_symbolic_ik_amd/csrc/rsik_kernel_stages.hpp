@@ -1,6 +1,7 @@
 // rsik_kernel_stages.hpp — rsik_stage: the stages of SymbolicIK.is_reachable as entry points of their own
-// (one translation unit: included by rsik_lib.hip, in this order, inside nothing)
 #pragma once
+
+#include "rsik_tables.hpp"
 
 namespace rsik {
 
@@ -210,7 +211,7 @@ __device__ inline int circles_linked_ref(double normal_margin, V3 wrist, V3 c2, 
 __global__ __launch_bounds__(kBlock) void stage_kernel(const StageArgs K) {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     __shared__ SharedTables lds_tab;
-        stage_tables<false, (int)offsetof(StageArgs, arms) + (int)sizeof(ArmC)>(lds_tab, K.arms);
+    stage_tables<false, (int)offsetof(StageArgs, arms) + (int)sizeof(ArmC)>(lds_tab, K.arms);
     if (i >= K.n) return;
     const Acc<false> A = make_acc<false>(K.arms, false, lds_tab);
     const double* x = K.in + i * K.in_stride;

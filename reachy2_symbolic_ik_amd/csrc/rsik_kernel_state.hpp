@@ -1,6 +1,8 @@
 // rsik_kernel_state.hpp — solver-state kernels of the scalar drop-in API, forward kinematics, the math test hook, the clock monitor
-// (one translation unit: included by rsik_lib.hip, in this order, inside nothing)
 #pragma once
+
+#include "rsik_goal.hpp"
+#include "rsik_tables.hpp"
 
 namespace rsik {
 

@@ -1,6 +1,9 @@
 // rsik_kernel_sweep.hpp — rsik_solve_sweep: is_reachable once per pose, then get_joints at n_theta elbow angles (solve_sweep_kernel)
-// (one translation unit: included by rsik_lib.hip after the other kernel headers, inside nothing)
 #pragma once
+
+#include "rsik_goal.hpp"
+#include "rsik_rows.hpp"
+#include "rsik_tables.hpp"
 
 namespace rsik {
 

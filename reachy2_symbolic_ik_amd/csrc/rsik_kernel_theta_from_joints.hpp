@@ -1,8 +1,13 @@
 // rsik_kernel_theta_from_joints.hpp — rsik_theta_from_joints / rsik_theta_from_joints_state: for n independent rows, the theta of
 // the elbow circle whose solution is closest to the row's measured joints (utils.get_best_theta_to_current_joints, U:267-331), and
 // the two rate-limiter stages of rsik_stage (U:115-127, U:220-264)
-// (one translation unit: included by rsik_lib.hip, in this order, inside nothing)
 #pragma once
+
+#include "rsik_goal.hpp"
+#include "rsik_kernel_stages.hpp"
+#include "rsik_kernel_state.hpp"
+#include "rsik_rows.hpp"
+#include "rsik_tables.hpp"
 
 namespace rsik {
 

@@ -1,6 +1,9 @@
 // rsik_lib.hip — the C ABI of include/rsik.h: context, argument checks and launches.  The kernels (gfx950) live in the
-// rsik_kernel_*.hpp files next to it, the per-pose mathematics in rsik_device.hpp / rsik_math.hpp, the host-side scheduler of
-// rsik_control_continuous_run in rsik_cont_run.hpp.
+// rsik_kernel_*.hpp files next to it, one per entry point or family; what they share in rsik_tables.hpp (workgroup size, constant
+// access, table staging), rsik_rows.hpp (streaming accesses, rows through LDS, the wave-level LDS fence) and rsik_goal.hpp (the pose
+// kernels' head, the goal-matrix conversion); the per-pose mathematics in rsik_device.hpp / rsik_math.hpp.  Each of these headers
+// includes what it uses.  Two files are fragments of this one, host code included inside its extern "C" block: the scheduler of
+// rsik_control_continuous_run (rsik_cont_run.hpp) and the RCCL entry points (rsik_comm.hpp).
 // Every launching entry point reads: its own checks, in its own order (the return code and the message that wins are part of the
 // ABI), fill the kernel's argument block K, launch_begin, one launch line, launch_end.  What they share is below the memcpy entry
 // points: check_arms, bind_arms, copy_cols, launch_form / tip_on_z, launch_dims / launch_begin / launch_end; and, for the sampling
@@ -24,9 +27,7 @@
 #include <type_traits>
 #include <vector>
 
-#include "rsik_device.hpp"
-
-// the kernels, by entry point (one translation unit)
+// the kernels, by entry point (each header includes what it uses: any order)
 #include "rsik_kernel_solve.hpp"
 #include "rsik_kernel_discrete.hpp"
 #include "rsik_kernel_continuous.hpp"

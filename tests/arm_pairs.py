@@ -56,7 +56,7 @@ def checker_arms(pair):
 
 
 def is_sided(i):
-    """arm_const_is_sided (csrc/rsik_kernel_solve.hpp) restated: the entries a mirror-image pair may differ in."""
+    """arm_const_is_sided (csrc/rsik_tables.hpp) restated: the entries a mirror-image pair may differ in."""
     from reachy2_symbolic_ik_amd import constants as K
 
     return (i in (K.C_SHOULDER + 1, K.C_TIPL + 1, K.C_ES + 1, K.C_SIDE) or K.C_MST <= i < K.C_TSH + 3

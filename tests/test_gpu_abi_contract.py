@@ -9,8 +9,8 @@ neighbouring (dropped) output that landed there changes them.  Shares of reachab
 checked on the reference launch; they exclude no row from a comparison.
 
 A NULL output is only safe where every store to it is guarded; the guards were read before these tests first ran:
-  solve_kernel                    joints rsik_kernel_solve.hpp:395,398; elbow :347 (371, 378, 387, 396, 399); store_reach: interval :273,
-                                  reachable :277, state :278
+  solve_kernel                    joints rsik_kernel_solve.hpp:395,398; elbow :347 (371, 378, 387, 396, 399); store_reach (rsik_goal.hpp): interval,
+                                  reachable and state, each behind its own test
   control_discrete_kernel         rsik_kernel_discrete.hpp: reachable :354, state :355, emergency :356
   control_continuous_kernel       rsik_kernel_continuous.hpp: reachable :207, state :208 (inputs: timed_out :157, cur_pose :50,
                                   current_joints :44)

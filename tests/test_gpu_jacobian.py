@@ -27,7 +27,7 @@ from gpu_support import T, abi, arm_kwargs, last_error, ptr, raw_call, torch_mod
 
 pytestmark = pytest.mark.gpu
 
-KBLOCK = 256  # RSIK_BLOCK (csrc/rsik_kernel_solve.hpp)
+KBLOCK = 256  # RSIK_BLOCK (csrc/rsik_tables.hpp)
 SIZES = (1, 63, 64, 65, KBLOCK - 1, KBLOCK, KBLOCK + 1)
 REPS = (1, 3)
 OUTS = ("jacobian", "null_vector", "manipulability")
