@@ -64,7 +64,9 @@ extern "C" {
 #define RSIK_STATE_INVALID_INPUT 10       /* the row's goal (pose or matrix) holds a NaN or an infinity: see "Rows that are not
                                           * numbers" below.  Where the reference raises numpy.linalg.LinAlgError
                                           * (symbolic_ik.py:580, reached through the comparisons of :284-307, which are all
-                                          * false for a NaN) or ValueError (scipy's Rotation.from_matrix, control_ik.py:215). */
+                                          * false for a NaN) or ValueError (scipy's Rotation.from_matrix, control_ik.py:215).
+                                          * Also a goal matrix of finite entries whose rotation block has a determinant <= 0:
+                                          * "Goal matrices that are not rotations" below. */
 
 /* ---- Rows that are not numbers ----
  * A batch is data: a row with a NaN or an infinity in it is answered in that row, never with an error code, never by stalling,
@@ -102,7 +104,28 @@ extern "C" {
  * before anything is launched or written: their serial phases wrap angles with a modulo written for bounded values, and a
  * wrong start theta would be carried from step to step.  Below the bound they answer as the reference does.  Not covered:
  * a caller-written previous_theta in a cont_state row (the library itself keeps it inside the control interval; it is
- * assumed below 2^27 in magnitude), and huge or scaled rotation entries of a goal matrix (the nearest-rotation path). */
+ * assumed below 2^27 in magnitude).
+ *
+ * Goal matrices that are not rotations.  The reference converts the 3x3 block of a goal matrix with SciPy's
+ * Rotation.from_matrix(...).as_euler("xyz") (utils.py:84-90; rule and SVD as in SciPy 1.15), and so does every entry point that
+ * takes a matrix (rsik_matrix_to_pose, rsik_control_discrete(_rows), rsik_control_continuous_step / _run, rsik_theta_from_joints)
+ * under RSIK_EULER_AUTO and RSIK_EULER_ALWAYS:
+ *  - determinant <= 0 (a reflection such as a flipped axis, a singular block, the zero block): SciPy raises ValueError
+ *    ("Non-positive determinant (left-handed or null coordinate frame)") before it looks at anything else.  rsik_matrix_to_pose
+ *    gives NaN angles and passes the position through; the other entry points answer the row exactly as "Rows that are not
+ *    numbers" says for a goal that holds a NaN — RSIK_STATE_INVALID_INPUT, reachable 0, NaN outputs, emergency 0, in continuous
+ *    mode previous_sol / init / the latch untouched — and no other row changes.  The sign is that of row 2 . (row 0 x row 1) in
+ *    binary64, tested also where the block's Gramian is the identity (a reflection's is).  The scalar Python drop-ins raise
+ *    that ValueError.
+ *  - determinant > 0: the block stands for the nearest rotation, the orthogonal polar factor U V^T of its SVD, whatever its scale
+ *    or shear (SciPy takes a block whose Gramian is np.isclose to the identity as it is; so does the conversion here).  Range:
+ *    no entry larger than 1e100 in magnitude and every singular value in [1e-100, 1e100], so that no product of three entries
+ *    overflows and no determinant vanishes; within it the angles are SciPy's to max(1e-12, 8 x SciPy's own error against a
+ *    50-digit polar factor) as rotations — 1e-12 down to a singular-value ratio of 1e-8, growing like 1 / c for two singular
+ *    values c times the third (the polar factor's own condition) — and flags, states and joints follow as for any goal.
+ *    tests/test_gpu_matrix_forms.py, tests/matrix_forms.py, G23.
+ *  Not covered: blocks outside that range (entries beyond 1e100, singular values below 1e-100 or a determinant that underflows).
+ *  RSIK_EULER_NEVER makes no conversion and no determinant test: the block is consumed as it came. */
 
 /* ---- why an emergency stop tripped: one bit per message the reference appends to ControlIK.emergency_state
  * (utils.multiturn_safety_check utils.py:544-566, utils.continuity_check utils.py:584-586) ---- */
@@ -786,7 +809,9 @@ int rsik_theta_from_joints_state(rsik_ctx *ctx, int64_t n, double *solver_state,
 /* utils.get_euler_from_homogeneous_matrix for a batch (utils.py:84-90): goal matrices (m12_soa, layout as
  * rsik_control_discrete) -> pose_soa = 6 device arrays px,py,pz,roll,pitch,yaw (the input layout of rsik_solve),
  * Euler angles = Rotation.from_matrix(M[:3,:3]).as_euler("xyz").  identity_shortcut != 0 adds ControlIK's
- * np.allclose(M[:3,:3], I) => [0,0,0] (control_ik.py:212-214). */
+ * np.allclose(M[:3,:3], I) => [0,0,0] (control_ik.py:212-214).  A block that is no rotation: its nearest rotation's angles for a
+ * determinant > 0, NaN angles (the position passed through) for a determinant <= 0, where SciPy raises ValueError — "Goal
+ * matrices that are not rotations" above. */
 int rsik_matrix_to_pose(rsik_ctx *ctx, int64_t n, const double *const m12_soa[12], int identity_shortcut,
                         double *const pose_soa[6]);
 

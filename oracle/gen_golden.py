@@ -1709,6 +1709,56 @@ def gen_far_inputs(out):
     np.savez_compressed(os.path.join(out, "g22_far_inputs.npz"), **data)
 
 
+# ----------------------------------------------------------------------------------------
+# G23: goal matrices whose rotation block is not a rotation (tests/matrix_forms.py: scaled, flattened, sheared, at gimbal lock,
+# left-handed, singular), on reachable positions drawn as G8 draws them.  Records, per arm and family, what the reference does:
+# utils.get_euler_from_homogeneous_matrix and ControlIK discrete (control_call), with a `raised` byte where it raised ValueError —
+# Rotation.from_matrix's "Non-positive determinant" for det <= 0.  That rule and the SVD behind the nearest rotation are those of
+# the installed SciPy, 1.15.3 (the reference's pinned 1.8.0 knows neither).  The blocks themselves are not stored: the module
+# rebuilds them, and their SHA-256 is.  Also the poses of the ordinary goals the tests interleave the family rows with.
+# ----------------------------------------------------------------------------------------
+def gen_matrix_forms(out):
+    import hashlib
+    import warnings
+
+    import matrix_forms as F
+    from reachy2_symbolic_ik.utils import get_euler_from_homogeneous_matrix
+
+    rng = np.random.default_rng(F.SEED)
+    ctrl = quiet(ControlIK, urdf_path="../config_files/reachy2.urdf")
+    data = {}
+    for f in F.FAMILIES:
+        data[f + "_sha256"] = np.frombuffer(hashlib.sha256(F.blocks(f).tobytes()).digest(), dtype=np.uint8).copy()
+    for arm in ARMS:
+        solver = ctrl.symbolic_ik_solver[arm]
+        pos, eul = reachable_poses(rng, solver, arm, len(F.FAMILIES) * F.ROWS + F.N_ORDINARY)
+        data[f"{arm}_ordinary_pos"], data[f"{arm}_ordinary_eul"] = pos[-F.N_ORDINARY:], eul[-F.N_ORDINARY:]
+        for k, f in enumerate(F.FAMILIES):
+            p = pos[k * F.ROWS:(k + 1) * F.ROWS]
+            Ms = F.goal_matrices(F.blocks(f), p)
+            n = len(Ms)
+            eu, eu_raised = np.full((n, 3), NAN), np.zeros(n, dtype=np.uint8)
+            J, raised = np.full((n, 7), NAN), np.zeros(n, dtype=np.uint8)
+            FL, ST = np.zeros(n, dtype=np.uint8), np.full(n, 255, dtype=np.uint8)
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore")  # scipy's gimbal-lock warning
+                for i, M in enumerate(Ms):
+                    try:
+                        eu[i] = get_euler_from_homogeneous_matrix(M)[1]
+                    except ValueError as e:
+                        assert str(e).startswith("Non-positive determinant"), e
+                        eu_raised[i] = 1
+                    try:
+                        J[i], FL[i], ST[i] = control_call(ctrl, arm, M, 20, "unconstrained")
+                    except ValueError as e:
+                        assert str(e).startswith("Non-positive determinant"), e
+                        raised[i] = 1
+            pre = f"{arm}_{f}_"
+            data[pre + "pos"], data[pre + "euler"], data[pre + "euler_raised"] = p, eu, eu_raised
+            data[pre + "joints"], data[pre + "reachable"], data[pre + "state"], data[pre + "raised"] = J, FL, ST, raised
+    np.savez_compressed(os.path.join(out, "g23_matrix_forms.npz"), **data)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(os.path.dirname(__file__), "..", "tests", "golden"))
@@ -1735,7 +1785,7 @@ def main():
              ("g7", gen_continuous_start), ("g8", gen_matrix_edges),
              ("g9", gen_custom_geometry), ("g10", gen_custom_urdf_control), ("g11", gen_emergency),
              ("g12", gen_continuous_modes), ("g13", gen_hostile), ("g14", gen_scale), ("g15", gen_stages), ("g16", gen_scale_continuous), ("g17", gen_scale_variants),
-             ("g18", gen_utils), ("g20", gen_ztip_geometry), ("g21", gen_discrete_theta_geometry), ("g22", gen_far_inputs)]
+             ("g18", gen_utils), ("g20", gen_ztip_geometry), ("g21", gen_discrete_theta_geometry), ("g22", gen_far_inputs), ("g23", gen_matrix_forms)]
     bad = 0
     for name, fn in steps:
         if args.only and name not in args.only.split(","):  # exact names: "g1" does not select "g12"

@@ -183,8 +183,18 @@ static quat quat_axis(int axis, double angle) {
 }
 /* Rotation.from_matrix, first half (scipy >= 1.12): a matrix whose Gramian M M^T is not the identity
  * (np.isclose with atol = 1e-12 and the default rtol = 1e-5, i.e. 1e-12 off the diagonal) is replaced by the
- * solution of the orthogonal Procrustes problem, U V^T of its SVD.  Here U V^T = M (M^T M)^(-1/2), with the inverse
- * square root taken through a cyclic Jacobi eigen-decomposition of the symmetric 3x3 M^T M. */
+ * solution of the orthogonal Procrustes problem, U V^T of its SVD.  Before either, a determinant <= 0 raises ValueError
+ * ("Non-positive determinant (left-handed or null coordinate frame)": mat3_det_positive, judged by the callers).
+ * The SVD here is a one-sided Jacobi SVD (Hestenes): plane rotations from the right make the columns of M orthogonal, M V = U S,
+ * without ever forming M^T M — whose eigen-decomposition, used here before, squares the condition number and was 2.5e-3 rad off
+ * on a singular value of 1e-8.  A column U_k S_k whose S_k is small carries a relative error of eps / S_k; for a 3x3 block with
+ * det > 0 the left vector of the SMALLEST singular value is therefore taken as the cross product of the other two, with the
+ * sign that makes det(U V^T) = +1. */
+static int mat3_det_positive(mat3 M) { /* false for a NaN as well */
+    double c[3];
+    cross3(M.m[0], M.m[1], c);
+    return dot3(M.m[2], c) > 0.0;
+}
 static int gram_is_identity(mat3 M) {
     mat3 G = mat3_mul(M, mat3_T(M));
     for (int i = 0; i < 3; i++)
@@ -194,25 +204,61 @@ static int gram_is_identity(mat3 M) {
         }
     return 1;
 }
-static mat3 procrustes_rotation(mat3 M) {
-    mat3 S = mat3_mul(mat3_T(M), M), V = mat3_eye();
-    for (int sweep = 0; sweep < 30; sweep++) {
-        double off = fabs(S.m[0][1]) + fabs(S.m[0][2]) + fabs(S.m[1][2]);
-        if (off < 1e-300) break;
+static mat3 procrustes_rotation(mat3 M) { /* det(M) > 0 */
+    /* entries of order one, by a power of two (exact): no sum of squares leaves the format */
+    double top = 0.0;
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) top = fmax(top, fabs(M.m[i][j]));
+    int e2;
+    frexp(top, &e2);
+    mat3 A, V = mat3_eye();
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) A.m[i][j] = ldexp(M.m[i][j], -e2);
+    for (int sweep = 0; sweep < 60; sweep++) {
+        int rotated = 0;
         for (int p = 0; p < 2; p++)
             for (int q = p + 1; q < 3; q++) {
-                if (S.m[p][q] == 0.0) continue;
-                double th = (S.m[q][q] - S.m[p][p]) / (2 * S.m[p][q]);
-                double t = (th >= 0 ? 1.0 : -1.0) / (fabs(th) + sqrt(th * th + 1));
+                double alpha = 0, beta = 0, gamma = 0;
+                for (int i = 0; i < 3; i++) {
+                    alpha += A.m[i][p] * A.m[i][p]; beta += A.m[i][q] * A.m[i][q]; gamma += A.m[i][p] * A.m[i][q];
+                }
+                if (fabs(gamma) <= 1e-16 * sqrt(alpha) * sqrt(beta)) continue;
+                rotated = 1;
+                double zeta = (beta - alpha) / (2 * gamma);
+                double t = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(zeta * zeta + 1));
                 double c = 1 / sqrt(t * t + 1), sn = t * c;
-                mat3 J = mat3_eye();
-                J.m[p][p] = c; J.m[q][q] = c; J.m[p][q] = sn; J.m[q][p] = -sn;
-                S = mat3_mul(mat3_T(J), mat3_mul(S, J));
-                V = mat3_mul(V, J);
+                for (int i = 0; i < 3; i++) {
+                    double ap = A.m[i][p], aq = A.m[i][q], vp = V.m[i][p], vq = V.m[i][q];
+                    A.m[i][p] = c * ap - sn * aq; A.m[i][q] = sn * ap + c * aq;
+                    V.m[i][p] = c * vp - sn * vq; V.m[i][q] = sn * vp + c * vq;
+                }
             }
+        if (!rotated) break;
     }
-    mat3 D = {{{1 / sqrt(S.m[0][0]), 0, 0}, {0, 1 / sqrt(S.m[1][1]), 0}, {0, 0, 1 / sqrt(S.m[2][2])}}};
-    return mat3_mul(M, mat3_mul(V, mat3_mul(D, mat3_T(V))));
+    /* A = U S by columns */
+    double u[3][3], len[3];
+    int small = 0;
+    for (int j = 0; j < 3; j++) {
+        const double col[3] = {A.m[0][j], A.m[1][j], A.m[2][j]};
+        len[j] = norm3(col);
+        for (int i = 0; i < 3; i++) u[j][i] = col[i] / len[j];
+        if (len[j] < len[small]) small = j;
+    }
+    {
+        const int j1 = (small + 1) % 3, j2 = (small + 2) % 3;
+        const double v0[3] = {V.m[0][0], V.m[1][0], V.m[2][0]}, v1[3] = {V.m[0][1], V.m[1][1], V.m[2][1]};
+        const double v2[3] = {V.m[0][2], V.m[1][2], V.m[2][2]};
+        double vc[3], uc[3];
+        cross3(v0, v1, vc);
+        const double det_v = dot3(vc, v2) >= 0 ? 1.0 : -1.0; /* det U = det V for det(U V^T) = +1 */
+        cross3(u[j1], u[j2], uc);
+        const double n = norm3(uc);
+        for (int i = 0; i < 3; i++) u[small][i] = det_v * uc[i] / n;
+    }
+    mat3 R;
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) R.m[i][j] = u[0][i] * V.m[j][0] + u[1][i] * V.m[j][1] + u[2][i] * V.m[j][2];
+    return R;
 }
 /* Rotation.from_matrix, second half: orthogonal matrix -> quaternion (Markley 2008, scipy _rotation.pyx) */
 static quat quat_from_matrix(mat3 M) {
@@ -285,6 +331,10 @@ void orc_euler_from_matrix_xyz(const double Rm[9], double eul[3]) {
     mat3 M;
     for (int i = 0; i < 3; i++)
         for (int j = 0; j < 3; j++) M.m[i][j] = Rm[3 * i + j];
+    if (!mat3_det_positive(M)) { /* Rotation.from_matrix raises ValueError: no angles */
+        eul[0] = eul[1] = eul[2] = NAN;
+        return;
+    }
     const int seq[3] = {0, 1, 2};
     quat_as_euler(quat_from_matrix(M), seq, 1, eul);
 }
@@ -930,6 +980,15 @@ static int np_allclose_eye3(const double M[16]) { /* np.allclose(M[:3,:3], np.ey
     return 1;
 }
 
+/* include/rsik.h "Goal matrices that are not rotations": a rotation block that np.allclose does not take for the identity is
+ * converted by Rotation.from_matrix (C:215, U:89), which raises ValueError for a determinant <= 0 */
+static int matrix_is_goal(const double M[16]) {
+    if (!matrix_is_numbers(M)) return 0;
+    if (np_allclose_eye3(M)) return 1;
+    mat3 R = {{{M[0], M[1], M[2]}, {M[4], M[5], M[6]}, {M[8], M[9], M[10]}}};
+    return mat3_det_positive(R);
+}
+
 /* C:212-217 */
 static void matrix_to_pose(const double M[16], double pos[3], double eul[3]) {
     pos[0] = M[3]; pos[1] = M[7]; pos[2] = M[11];
@@ -983,7 +1042,7 @@ int orc_control_discrete(const orc_arm_t *arm, const double M[16], int nb, doubl
                          const double previous_sol[7], const double current_joints[7], double previous_theta,
                          double orbita3d_max_angle, double joints[7], int *reachable, int *emergency_stop) {
     double pos[3], eul[3], lim[2];
-    if (!matrix_is_numbers(M)) { /* the reference raises (C:215 / S:580): no joints, no verdict on them */
+    if (!matrix_is_goal(M)) { /* the reference raises (C:215 / S:580): no joints, no verdict on them */
         for (int i = 0; i < 7; i++) joints[i] = NAN;
         *reachable = 0;
         *emergency_stop = 0;
@@ -1086,7 +1145,7 @@ int orc_control_continuous_step(const orc_arm_t *arm, orc_cont_state_t *cs, cons
         return ORC_STATE_EMERGENCY;
     }
     double pos[3], eul[3], lim[2];
-    const int numbers = matrix_is_numbers(M);
+    const int numbers = matrix_is_goal(M);
     if (numbers) matrix_to_pose(M, pos, eul);
     double pref = preferred_theta_arg;
     interval_limit_for(arm, constrained_mode, lim, &pref);

@@ -35,8 +35,21 @@ STATE_STRINGS = (
     "",
     "emergency stop",
     "not reachable without limits",  # RSIK_STATE_NOT_REACHABLE_NO_LIMITS: where the reference raises (control_ik.py:385-387)
-    "invalid input",  # RSIK_STATE_INVALID_INPUT: the goal holds a NaN / an infinity — where the reference raises LinAlgError (symbolic_ik.py:580)
+    # RSIK_STATE_INVALID_INPUT: the goal holds a NaN / an infinity — where the reference raises LinAlgError (symbolic_ik.py:580) — or
+    # its rotation block has a determinant <= 0 (a reflection, a singular block) — where SciPy's Rotation.from_matrix raises
+    # ValueError under the reference's utils.get_euler_from_homogeneous_matrix (utils.py:89)
+    "invalid input",
 )
+
+
+def raise_invalid_goal_matrix(M: Any) -> None:
+    """What the reference raises for a goal matrix the device answered with RSIK_STATE_INVALID_INPUT: SciPy's ValueError for a
+    rotation block of finite entries whose determinant is <= 0 (the reference converts the rotation before it reads the position),
+    numpy's LinAlgError for entries that are not numbers."""
+    M = np.asarray(M, dtype=np.float64)
+    if np.all(np.isfinite(M[:3, :3])) and not np.linalg.det(M[:3, :3]) > 0:
+        raise ValueError(f"Non-positive determinant (left-handed or null coordinate frame) in rotation matrix 0: {M[:3, :3]}.")
+    raise np.linalg.LinAlgError("SVD did not converge")
 
 
 def default_ik_parameters() -> Dict[str, Any]:

@@ -17,7 +17,7 @@ import torch
 
 from . import _abi
 from .backend import HipSolver
-from .constants import ARM_IDS, STATE_STRINGS, get_ik_parameters_from_urdf
+from .constants import ARM_IDS, STATE_STRINGS, get_ik_parameters_from_urdf, raise_invalid_goal_matrix
 from .symbolic_ik import SymbolicIK
 
 DEFAULT_CURRENT_JOINTS = [
@@ -263,7 +263,7 @@ class ControlIK:
             torch.cuda.current_stream(sv.device).synchronize()
         flags = io["h_bytes"][8 * self._IO_B: 8 * self._IO_B + 4]
         if int(flags[1]) == _abi.STATE_INVALID_INPUT:  # rsik.h "Rows that are not numbers": the scalar drop-in raises like the reference
-            raise np.linalg.LinAlgError("SVD did not converge")
+            raise_invalid_goal_matrix(M)  # LinAlgError, or SciPy's ValueError for a determinant <= 0
         return hn[self._IO_J: self._IO_J + 7].tolist(), bool(flags[0]), STATE_STRINGS[int(flags[1])], int(flags[2])
 
     # ------------------------------------------------------------------ reference API
@@ -353,7 +353,7 @@ class ControlIK:
         self.previous_theta[name] = float(back[0])
         self.init = bool(back[8])
         if int(flags[1]) == _abi.STATE_INVALID_INPUT:  # rsik.h "Rows that are not numbers" (previous_sol, init, the latch: untouched)
-            raise np.linalg.LinAlgError("SVD did not converge")
+            raise_invalid_goal_matrix(M)  # LinAlgError, or SciPy's ValueError for a determinant <= 0
         if int(flags[1]) == _abi.STATE_NOT_REACHABLE_NO_LIMITS:
             # control_ik.py:385-387: is_reachable_no_limits failed (a solver with a non-positive projection_margin).  The
             # reference has by now (re)initialised previous_sol / previous_theta if the call timed out, and nothing else.

@@ -238,34 +238,70 @@ __device__ __forceinline__ Rot rot_from_caller_euler(double roll, double pitch, 
 // published algorithms SciPy uses, because for inputs that are not exactly orthonormal, and at gimbal lock, the
 // ALGORITHM defines the answer: (0) a matrix whose Gramian M M^T is not the identity (np.isclose, atol 1e-12, default
 // rtol 1e-5: 1e-12 off the diagonal) is replaced by the nearest rotation, U V^T of its SVD (orthogonal Procrustes,
-// SciPy >= 1.12) — computed here as the polar factor by Newton's iteration X <- (X + X^-T) / 2, which converges
-// quadratically to the same matrix; (1) matrix -> quaternion from the largest of (R00, R11, R22, trace) (Markley
+// SciPy >= 1.12) — computed here as the polar factor by Newton's iteration with norm scaling (nearest_rotation), which
+// converges quadratically to the same matrix — after a determinant <= 0 has been answered with NaN angles, where SciPy raises
+// (det_not_positive); (1) matrix -> quaternion from the largest of (R00, R11, R22, trace) (Markley
 // 2008), normalised; (2) quaternion -> extrinsic xyz angles after
 // Bernardes & Viollet (2022): with a = w - y, b = x + z, c = y + w, d = z - x the middle angle is
 // 2 atan2(|(c, d)|, |(a, b)|) - pi/2 and the outer angles are atan2(b, a) -+ atan2(d, c); within 1e-7 of gimbal lock
 // the third angle is set to 0 and the first takes the whole rotation.  Not on the hot path.
 // np.isclose(M M^T, I, atol=1e-12) with the default rtol = 1e-5: SciPy's test for "already a rotation"
-__device__ __forceinline__ bool gram_is_identity(const double (&m)[9]) {
+// (dia_tol: the caller that asks "does the round trip change anything" is stricter on the diagonal than SciPy — goal_from_m12)
+__device__ __forceinline__ bool gram_is_identity(const double (&m)[9], double dia_tol = 1e-12 + 1e-5) {
     // the six distinct entries of M M^T - I; the tolerance of np.isclose is 1e-12 + 1e-5 |I_ij|, i.e. 1e-12 off the
     // diagonal and 1e-5 (+1e-12) on it, four orders of magnitude above any rounding of the products, so the dot
     // products are fused and the two groups are reduced to one comparison each
     auto g = [&](int i, int j) { return fma(m[3 * i], m[3 * j], fma(m[3 * i + 1], m[3 * j + 1], m[3 * i + 2] * m[3 * j + 2])); };
     const double off = fmax(fmax(fabs(g(0, 1)), fabs(g(0, 2))), fabs(g(1, 2)));
     const double dia = fmax(fmax(fabs(g(0, 0) - 1.0), fabs(g(1, 1) - 1.0)), fabs(g(2, 2) - 1.0));
-    return off <= 1e-12 && dia <= 1e-12 + 1e-5;
+    return off <= 1e-12 && dia <= dia_tol;
 }
+// Row 0 x row 1 of a row-major 3x3 block, and with it the determinant row 2 . (row 0 x row 1): the ONE place where "not a
+// right-handed frame" is decided (rsik.h "Goal matrices that are not rotations").  Rotation.from_matrix raises ValueError
+// ("Non-positive determinant (left-handed or null coordinate frame)") for det <= 0 before it looks at the Gramian; here such a
+// block — and one whose determinant is a NaN — gives NaN angles (euler_xyz_from_matrix) and RSIK_STATE_INVALID_INPUT
+// (goal_from_m12).  Entries of magnitude in [1e-100, 1e100] keep every product of three inside the format.
+__device__ __forceinline__ void row0_cross_row1(const double* m, double& c6, double& c7, double& c8) {
+    c6 = fma(m[1], m[5], -(m[2] * m[4])); c7 = fma(m[2], m[3], -(m[0] * m[5])); c8 = fma(m[0], m[4], -(m[1] * m[3]));
+}
+__device__ __forceinline__ bool det_not_positive(const double* m, double c6, double c7, double c8) {
+    return !(fma(m[6], c6, fma(m[7], c7, m[8] * c8)) > 0.0);
+}
+__device__ __forceinline__ bool det_not_positive(const double* m) {
+    double c6, c7, c8;
+    row0_cross_row1(m, c6, c7, c8);
+    return det_not_positive(m, c6, c7, c8);
+}
+// The orthogonal polar factor of a block with a positive determinant.  Newton's iteration X <- (mu X + X^-T / mu) / 2 with the
+// norm scaling mu = (|X^-1|_F / |X|_F)^(1/2) (Higham, Functions of Matrices, 8.6): unscaled (mu = 1) it only halves the distance of
+// the singular values to 1 per step while they are far from it — 24 steps gave out beyond a scale of 1e+-6 or a singular value of
+// 1e-7 — scaled, the first step balances them around 1 and at most 6 steps reach 1e-13 for scales of 1e+-100 and singular-value
+// ratios down to 1e-8 (docs/experiments.md).  The block is first brought to entries of order 1 by a power of two (exact), so that
+// no cofactor or determinant leaves the format.  A bounded loop: kPolarSteps whatever the data.
+constexpr int kPolarSteps = 16;
 __device__ inline void nearest_rotation(double (&m)[9]) {
-    for (int it = 0; it < 24; it++) {
+    double top = 0.0;
+#pragma unroll
+    for (int k = 0; k < 9; k++) top = fmax(top, fabs(m[k]));
+    const int e2 = -::ilogb(top);
+#pragma unroll
+    for (int k = 0; k < 9; k++) m[k] = ::scalbn(m[k], e2);
+    for (int it = 0; it < kPolarSteps; it++) {
         // cofactors: X^-T = cof(X) / det(X)
         const double c0 = m[4] * m[8] - m[5] * m[7], c1 = m[5] * m[6] - m[3] * m[8], c2 = m[3] * m[7] - m[4] * m[6];
         const double c3 = m[2] * m[7] - m[1] * m[8], c4 = m[0] * m[8] - m[2] * m[6], c5 = m[1] * m[6] - m[0] * m[7];
         const double c6 = m[1] * m[5] - m[2] * m[4], c7 = m[2] * m[3] - m[0] * m[5], c8 = m[0] * m[4] - m[1] * m[3];
-        const double idet = 1.0 / (m[0] * c0 + m[1] * c1 + m[2] * c2);
+        const double det = m[0] * c0 + m[1] * c1 + m[2] * c2;
         const double cof[9] = {c0, c1, c2, c3, c4, c5, c6, c7, c8};
+        double xsq = 0.0, csq = 0.0;
+#pragma unroll
+        for (int k = 0; k < 9; k++) { xsq = fma(m[k], m[k], xsq); csq = fma(cof[k], cof[k], csq); }
+        const double mu = sqrt(sqrt(csq / xsq) / fabs(det));  // (|X^-1|_F / |X|_F)^(1/2), X^-1 = cof^T / det
+        const double imu = 1.0 / (det * mu);
         double change = 0.0;
 #pragma unroll
         for (int k = 0; k < 9; k++) {
-            const double x = 0.5 * (m[k] + cof[k] * idet);
+            const double x = 0.5 * (mu * m[k] + cof[k] * imu);
             change = fmax(change, fabs(x - m[k]));
             m[k] = x;
         }
@@ -276,6 +312,7 @@ __device__ inline void euler_xyz_from_matrix(const double (&m_in)[9], double (&e
     double m[9];
 #pragma unroll
     for (int k = 0; k < 9; k++) m[k] = m_in[k];
+    const bool bad = det_not_positive(m);  // SciPy raises ValueError (see det_not_positive): no angles (selected at the end: one path)
     const bool orth = gram_is_identity(m);
     if (!orth) nearest_rotation(m);
     const double tr = m[0] + m[4] + m[8];
@@ -305,6 +342,7 @@ __device__ inline void euler_xyz_from_matrix(const double (&m_in)[9], double (&e
     for (int k = 0; k < 3; k++) {
         if (eul[k] < -kPi) eul[k] += kTwoPi;
         else if (eul[k] > kPi) eul[k] -= kTwoPi;
+        if (bad) eul[k] = __builtin_nan("");
     }
 }
 

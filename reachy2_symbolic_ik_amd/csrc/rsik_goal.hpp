@@ -41,15 +41,21 @@ __device__ __forceinline__ void store_reach(const ARGS& K, bool live, int64_t ti
 // `special` (optional): set when the matrix did not go through as it came — the identity shortcut, the Euler round trip —
 // or is not a proper rotation whose third row is the cross product of the other two: the trajectory pipeline's joints
 // phase re-reads all twelve entries only for those (cont_joints_kernel).
-__device__ __forceinline__ void goal_from_m12(const double (&m)[12], Rot& Rg, V3& pos, int mode, bool* special = nullptr) {
+// Returns true for a block that is no right-handed frame (det <= 0, det_not_positive: SciPy raises ValueError where the reference
+// converts it, U:89): the caller answers RSIK_STATE_INVALID_INPUT; Rg is then the block as it came, or NaN.  Tested in AUTO and ALWAYS —
+// in AUTO also where the Gramian is the identity: a reflection has an identity Gramian — and not in NEVER, which makes no
+// conversion and consumes the block as it came.
+__device__ __forceinline__ bool goal_from_m12(const double (&m)[12], Rot& Rg, V3& pos, int mode, bool* special = nullptr) {
 #pragma unroll
     for (int k = 0; k < 9; k++) Rg.m[k] = m[k];
+    double c6, c7, c8;
+    row0_cross_row1(m, c6, c7, c8);
+    const bool bad = mode != 2 && det_not_positive(m, c6, c7, c8);
     if (special) {
         // row 2 against row 0 x row 1, entry by entry, to 1e-14: a few roundings of the entries themselves.  (A looser test — 1e-9
         // until round 4 — let the joints phase rebuild the third row of a matrix that is NOT orthonormal to rounding, and where
         // the arm is stretched out the elbow-yaw / wrist-yaw split amplifies such a difference 2e4 times and more: the pipeline
         // and the step kernel could then differ by ~1e-5 rad under RSIK_EULER_NEVER.  Anything else re-reads the three entries.)
-        const double c6 = fma(m[1], m[5], -(m[2] * m[4])), c7 = fma(m[2], m[3], -(m[0] * m[5])), c8 = fma(m[0], m[4], -(m[1] * m[3]));
         *special = !(fabs(c6 - m[6]) <= 1e-14 && fabs(c7 - m[7]) <= 1e-14 && fabs(c8 - m[8]) <= 1e-14);
     }
     // np.allclose(R, I) needs all nine entries close; R00 alone rules it out for nearly every goal
@@ -64,21 +70,24 @@ __device__ __forceinline__ void goal_from_m12(const double (&m)[12], Rot& Rg, V3
         for (int k = 0; k < 9; k++) Rg.m[k] = (k % 4 == 0) ? 1.0 : 0.0;
     } else {
         bool rt = mode == 1;
-        if (mode == 0) rt = (fabs(Rg.m[6]) > 1.0 - 1e-10) || !gram_is_identity(Rg.m);
+        // (1e-12 on the diagonal too: SciPy's own test lets a block scaled by 1 + 5e-6 pass as a rotation, and then normalises
+        // its quaternion — consumed as it came, such a block moves the wrist by 5e-7 m)
+        if (mode == 0) rt = (fabs(Rg.m[6]) > 1.0 - 1e-10) || !gram_is_identity(Rg.m, 1e-12);
         if (special && rt) *special = true;
-        if (RSIK_RARE(rt)) {
+        if (RSIK_RARE(rt)) {  // (a block with det <= 0 comes back as NaN: the row is invalid either way)
             double eul[3];
             euler_xyz_from_matrix(Rg.m, eul);
             Rg = rot_from_euler(eul[0], eul[1], eul[2]);
         }
     }
     pos = {m[9], m[10], m[11]};
+    return bad;
 }
-__device__ __forceinline__ void load_m12(const double* const* in, int64_t i, Rot& Rg, V3& pos, int mode) {
+__device__ __forceinline__ bool load_m12(const double* const* in, int64_t i, Rot& Rg, V3& pos, int mode) {
     double m[12];
 #pragma unroll
     for (int k = 0; k < 12; k++) m[k] = in[k][i];
-    goal_from_m12(m, Rg, pos, mode);
+    return goal_from_m12(m, Rg, pos, mode);
 }
 
 }  // namespace rsik

@@ -155,8 +155,8 @@ __global__ __launch_bounds__(kBlock) void control_continuous_kernel(const Contin
         double m[12];
 #pragma unroll
         for (int k = 0; k < 12; k++) m[k] = K.in[k][ii];
-        const bool invalid = !all_finite(m);
-        goal_from_m12(m, Rg, pos, K.euler_roundtrip);
+        const bool not_numbers = !all_finite(m);
+        const bool invalid = goal_from_m12(m, Rg, pos, K.euler_roundtrip) || not_numbers;  // ... or no right-handed frame
         if (K.first_timed_out || (K.timed_out && K.timed_out[ii])) { has_prev = false; init = true; }  // C:298-304
         if (!has_prev) {  // C:306-325
             has_prev = true;

@@ -178,10 +178,11 @@ __global__ __launch_bounds__(kDiscBlock, RSIK_DISC_MIN_WAVES) RSIK_DISC_ATTR voi
     const int slot = MIXED ? (A.isl ? 1 : 0) : 0;
 
     // C:212-217: M -> pose (see goal_from_m12)
-    const bool invalid = !all_finite(m12);  // rsik.h "Rows that are not numbers" (judged while the twelve values are at hand)
+    // rsik.h "Rows that are not numbers" (judged while the twelve values are at hand) and "Goal matrices that are not rotations"
+    const bool not_numbers = !all_finite(m12);
     Rot Rg;
     V3 pos;
-    goal_from_m12(m12, Rg, pos, K.euler_roundtrip);
+    const bool invalid = goal_from_m12(m12, Rg, pos, K.euler_roundtrip) || not_numbers;
 
     // Of the goal orientation the solver only needs three vectors (Goal); the two that are read again by the joint
     // stage wait in the output staging slab while the theta search runs (registers are the scarce resource here)

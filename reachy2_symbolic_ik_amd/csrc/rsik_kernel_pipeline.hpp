@@ -132,11 +132,11 @@ __device__ __forceinline__ void pipe_store(T* p, T v) { st_stream<kStoreThrough>
 template <bool MIXED, bool PLANE>
 __device__ __forceinline__ void cont_prepare_step(const ContRunArgs& K, const Acc<MIXED>& A, int slot, const double (&m)[12], int64_t t,
                                                   int64_t t_abs, int64_t i, bool live) {
-    const bool invalid = !all_finite(m);  // (judged while the twelve values are at hand)
+    const bool not_numbers = !all_finite(m);  // (judged while the twelve values are at hand)
     Rot Rg;
     V3 pos;
     bool special;
-    goal_from_m12(m, Rg, pos, K.euler_roundtrip, &special);
+    const bool invalid = goal_from_m12(m, Rg, pos, K.euler_roundtrip, &special) || not_numbers;  // ... or no right-handed frame
     const Goal G = make_goal(A, Rg);
     Reach r;
     ThetaTarget T = continuous_target<PLANE, false>(A, pos, G.woff, K.pref_self[slot], K.pref_self_cs[slot], K.pref_self_sn[slot], r);

@@ -131,7 +131,7 @@ __global__ __launch_bounds__(kBlock) void theta_from_joints_kernel(const ThetaFr
 #pragma unroll
         for (int k = 0; k < 12; k++) m[k] = K.goal[k][ii];
         invalid = invalid || !all_finite(m);
-        goal_from_m12(m, Rg, pos, K.euler_roundtrip);
+        invalid = goal_from_m12(m, Rg, pos, K.euler_roundtrip) || invalid;  // ... or no right-handed frame
     } else {
         double p[6];
 #pragma unroll

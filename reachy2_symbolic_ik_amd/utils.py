@@ -23,7 +23,7 @@ import numpy as np
 import numpy.typing as npt
 
 from . import _abi
-from .constants import get_ik_parameters_from_urdf, parse_vector  # noqa: F401  (utils.py:661-694)
+from .constants import get_ik_parameters_from_urdf, parse_vector, raise_invalid_goal_matrix  # noqa: F401  (utils.py:661-694)
 
 _lock = threading.Lock()
 _default: dict = {}
@@ -101,6 +101,8 @@ def get_euler_from_homogeneous_matrix(
         pose = sv.matrix_to_pose(m12, identity_shortcut=False)
         torch.cuda.current_stream(sv.device).synchronize()
         eul = pose[3:6, 0].cpu().numpy()
+    if np.isnan(eul).any() and np.all(np.isfinite(M[:3, :3])):  # determinant <= 0: Rotation.from_matrix's ValueError (utils.py:89)
+        raise_invalid_goal_matrix(M)
     return M[:3, 3], (np.degrees(eul) if degrees else eul)
 
 

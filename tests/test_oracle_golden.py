@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import far_inputs as F
+import matrix_forms as MF
 import scale_inputs as SC
 from arm_pairs import CUSTOM, ZTIP
 from checker_support import CUSTOM_GEOMETRY, _check_scale_continuous, _check_scale_set, _check_symbolic, load
@@ -350,6 +351,26 @@ def test_matrix_edges_euler_and_control(golden_dir, kind):
         np.testing.assert_array_equal(res["reachable"], g[pre + "reachable"])
         np.testing.assert_array_equal(res["state"], g[pre + "state"])
         assert np.max(np.abs(res["joints"] - g[pre + "joints"])) < TOL
+
+
+@pytest.mark.parametrize("family", MF.FAMILIES)
+def test_matrix_forms_euler_and_control(golden_dir, family):
+    """G23 next to G8: goal matrices whose rotation block is scaled, flattened, sheared, left-handed or singular
+    (tests/matrix_forms.py).  The checker's conversion and its ControlIK discrete result follow the reference on every row: its
+    angles (as rotations) and joints where it answers, NaN angles and the invalid-input outcome where it raises ValueError."""
+    g = load(golden_dir, MF.G23)
+    ar, al = orc.Arm("r_arm", -1.01), orc.Arm("l_arm", -1.01)
+    eul = orc.euler_from_matrix_xyz(MF.blocks(family))
+    for k, arm in enumerate(("r_arm", "l_arm")):
+        pre = f"{arm}_{family}_"
+        if family in MF.IMPROPER:
+            assert g[pre + "euler_raised"].all() and np.isnan(eul).all()
+        else:
+            assert not g[pre + "euler_raised"].any()
+            assert float(MF.rotation_error(eul, g[pre + "euler"]).max()) < MF.recorded_tolerance(family)
+        M = MF.family_matrices(g, arm)[family]
+        res = orc.control_discrete_batch(ar, al, M, arm_id=np.full(len(M), k, np.uint8), nb_search_points=20)
+        MF.check_control(res, g, arm, family, "checker", TOL)
 
 
 def test_custom_geometry(golden_dir):
