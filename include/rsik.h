@@ -898,6 +898,62 @@ int rsik_joint_rates(rsik_ctx *ctx, int64_t n, int64_t n_rep, const double *join
                      double *rates, double *achieved_twist);
 
 /*
+ * rsik_track — closed-loop tracking of goal trajectories at the velocity level: the loop a caller of rsik_joint_rates runs (forward
+ * kinematics, pose error, twist, joint rates, one integration step), for n trajectories of n_steps goals each, from ONE launch in which
+ * the joints never leave the registers (added within ABI version 8: one symbol, no option, no workspace).  It starts from any joints,
+ * degrades gracefully where the analytic solve answers NaN (a goal out of reach, the wrist limit), obeys rate and joint limits, and is
+ * continuous where the elbow projection makes the analytic answer jump.  The reference has nothing of the kind.
+ *
+ *   m12_steps        [n_steps][12][n] device, the layout of rsik_control_continuous_run (R row-major, then t): one buffer can feed
+ *                    both.  The 3 x 3 block is consumed as it comes, without an Euler round trip and without a determinant test (as
+ *                    RSIK_EULER_NEVER): it MUST be a rotation.
+ *   arm / arm_uniform  as rsik_jacobian (arm: [n], one byte per trajectory, or NULL)
+ *   start_joints     [n][7] device: where every trajectory starts.  NULL is RSIK_E_INVALID.
+ *   dt, kp, ko       the integration step (finite, > 0) and the gains on the position and the orientation error (finite, >= 0)
+ *   feedforward_steps  [n_steps][n][6] device, or NULL for zeros: a twist in the row order of the Jacobian, added to the feedback
+ *   damping_host / damping   lambda of rsik_joint_rates, for every trajectory or [n] device, one per trajectory and constant over the
+ *                    steps; the rules are rsik_joint_rates' (damping_host is not read when damping is given)
+ *   rest_joints      [n][7] device or NULL: a posture the arm is drawn to in the null space; rest_gain (finite, >= 0) is not read when
+ *                    rest_joints is NULL
+ *   limits_host      21 doubles on the HOST, [3][7], or NULL for none: the rows are rate_max, q_min, q_max.  rate_max > 0 and
+ *                    q_min <= q_max; +-infinity is allowed; a NaN is RSIK_E_INVALID.
+ *   joints_steps     [n_steps][n][7] or NULL: the joints after every step
+ *   rates_steps      [n_steps][n][7] or NULL: the rates of every step, after the rate limit
+ *   err_steps        [n_steps][n][2] or NULL: (|position error| in m, rotation error in rad) every step saw, before it moved
+ *   final_joints     [n][7] or NULL: the joints after the last step
+ *   final_err        [n][2] or NULL: the error of the last goal at the joints after the last step
+ * Definition, per trajectory: q := start_joints, then for t = 0 ... n_steps - 1
+ *   1. (p, R) = rsik_forward_kinematics(q)
+ *   2. e_p = p_g - p;  D = R_g R^T,  w = 1/2 (D21 - D12, D02 - D20, D10 - D01),  s = |w|,  c = 1/2 (tr D - 1),  angle = atan2(s, c),
+ *      e_o = w (angle / s) where s^2 >= 2^-52, else e_o = w: the rotation vector of D.  At a rotation by pi the direction is undefined
+ *      and e_o is close to 0 (s is): the loop does not turn towards such a goal until something else moves it off pi.
+ *      err_steps[t] = (|e_p|, angle).
+ *   3. v = feedforward[t] + (kp e_p, ko e_o)
+ *   4. q0 = rest_gain (rest_joints - q), a plain difference (q is continuous along the run); 0 without rest_joints
+ *   5. q' = exactly what rsik_joint_rates defines for (q, v, lambda, q0): L D L^T, pivot clamp, fixed order
+ *   6. with limits: m = max_k |q'_k| / rate_max_k; if m > 1, q' := q' / m (one factor for all joints: the direction is kept)
+ *   7. q := q + dt q'; with limits, clamped to [q_min, q_max] per joint
+ *   8. rates_steps[t] = q' (after the limit), joints_steps[t] = q
+ * final_joints is the last q; final_err is step 2 once more, for the last goal at the last q.
+ * Any output may be NULL, all five NULL is RSIK_E_INVALID; the bits of an output do not depend on which others were requested, two
+ * launches on the same inputs give the same bits, and a trajectory's bits depend neither on n nor on its neighbours.
+ * A NaN or an infinity in a trajectory's start_joints or rest_joints row, or a damping that is not usable, makes every output of that
+ * trajectory NaN and changes nothing else.  A step whose goal or feed-forward holds a NaN or an infinity is skipped: q is held,
+ * joints_steps[t] = q, rates_steps[t] = 0, err_steps[t] = NaN, and the trajectory goes on from there with the bits of the same run
+ * without that step; final_err is NaN if the last goal is such a goal.  A finite angle of any size is answered as rsik_jacobian
+ * answers it.
+ * n == 0 launches nothing; n < 0, n_steps outside 1 ... 65536, m12_steps == NULL, start_joints == NULL, all outputs NULL, a dt, gain,
+ * damping_host or limit outside the above give RSIK_E_INVALID, the arm checks and their codes are rsik_jacobian's (RSIK_E_NOT_SET
+ * included).  Enqueued on the context's stream; allocates nothing and never waits for the device.
+ */
+int rsik_track(rsik_ctx *ctx, int64_t n, int64_t n_steps, const double *m12_steps,
+               const uint8_t *arm, int arm_uniform, const double *start_joints,
+               double dt, double kp, double ko, const double *feedforward_steps,
+               double damping_host, const double *damping,
+               const double *rest_joints, double rest_gain, const double *limits_host,
+               double *joints_steps, double *rates_steps, double *err_steps, double *final_joints, double *final_err);
+
+/*
  * Multi-GPU.  Poses are independent, so a job is sharded across the GPUs of a node — one process and one
  * rsik context per GPU — with no data-path collective; the only exchange is the all-gather of the final arrays
  * (joints [n,7], state [n]) over RCCL / xGMI.  The reference has nothing distributed (single-threaded Python).  Python

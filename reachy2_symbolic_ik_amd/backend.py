@@ -936,6 +936,85 @@ class HipSolver:
                  _ptr(res.get("rates")), _ptr(res.get("achieved_twist")))
         return self._finish(res, "rsik_joint_rates", cargs, plan_only, (joints, twist, damping, bias_rates, arm))
 
+    # ------------------------------------------------------------------ rsik_track
+    TRACK_OUTPUTS = ("joints", "rates", "err", "final_joints", "final_err")
+
+    def track(
+        self,
+        m12_steps: torch.Tensor,
+        start_joints: torch.Tensor,
+        dt: float,
+        kp: float,
+        ko: float,
+        damping: Any = None,
+        feedforward: Optional[torch.Tensor] = None,
+        rest_joints: Optional[torch.Tensor] = None,
+        rest_gain: float = 0.0,
+        limits: Any = None,
+        arm: Optional[torch.Tensor] = None,
+        arm_uniform: int = 0,
+        want: Sequence[str] = ("joints",),
+        out: Optional[Dict[str, torch.Tensor]] = None,
+        plan_only: bool = False,
+    ) -> Dict[str, torch.Tensor]:
+        """Closed-loop tracking of n goal trajectories over T steps at the velocity level, every step in one launch in which the
+        joints stay in registers (rsik_track).  m12_steps: [T, 12, n] goal matrices (R row-major, then t: the layout of
+        control_continuous_run; R must be a rotation, it is consumed as it comes); start_joints: [n, 7]; dt > 0; kp, ko >= 0 the
+        gains on the position and orientation error; damping: lambda of joint_rates(), a float or a tensor [n], one per trajectory;
+        feedforward: [T, n, 6] or None for zeros, a twist in the row order of the Jacobian; rest_joints: [n, 7] or None, with
+        rest_gain >= 0; limits: [3, 7] on the host (rows rate_max > 0, q_min <= q_max; infinities allowed) or None for none;
+        arm / arm_uniform as jacobian().
+        Per trajectory, q := start_joints, then for every step t: (p, R) = forward_kinematics(q); e_p = p_g - p, e_o the rotation
+        vector of R_g R^T (close to 0, its direction undefined, at a rotation by pi); v = feedforward[t] + (kp e_p, ko e_o);
+        q0 = rest_gain (rest_joints - q); q' = joint_rates(q, v, lambda, q0) exactly; with limits q' is scaled by one factor so that
+        no |q'_k| exceeds rate_max_k; q := q + dt q', clamped to [q_min, q_max] with limits.
+        `want`: which of TRACK_OUTPUTS to compute, at least one; the bits of one do not depend on the others.  Returns device
+        tensors: joints [T, n, 7] (after every step), rates [T, n, 7] (after the limit), err [T, n, 2] (|e_p| in m and the rotation
+        angle in rad each step saw, before it moved), final_joints [n, 7], final_err [n, 2] (the last goal at the last joints).
+        A trajectory with a NaN or an infinity in its start or rest row, or an unusable lambda, is NaN everywhere; a step whose
+        goal or feed-forward is not numbers is skipped (joints held, rates 0, err NaN) and the trajectory goes on.
+        plan_only=True launches nothing and adds res["launch"], a zero-overhead re-launch callable (see plan())."""
+        if not isinstance(m12_steps, torch.Tensor):
+            m12_steps = torch.as_tensor(np.asarray(m12_steps, dtype=np.float64))
+        if m12_steps.dim() != 3 or m12_steps.shape[1] != 12:
+            raise ValueError("m12_steps must have shape [n_steps, 12, n]")
+        n_steps, n = int(m12_steps.shape[0]), int(m12_steps.shape[2])
+        if not 1 <= n_steps <= 65536:
+            raise ValueError("m12_steps: between 1 and 65536 steps")
+        want = tuple(want)
+        if not want or any(name not in self.TRACK_OUTPUTS for name in want):
+            raise ValueError(f"want must name at least one of {self.TRACK_OUTPUTS}")
+        if damping is None:
+            raise ValueError("damping: a float > 0 or a tensor with one lambda per trajectory")
+        dt, kp, ko, rest_gain = float(dt), float(kp), float(ko), float(rest_gain)
+        if not (np.isfinite(dt) and dt > 0.0):
+            raise ValueError("dt must be finite and > 0")
+        for name, gain in (("kp", kp), ("ko", ko), ("rest_gain", rest_gain)):
+            if not (np.isfinite(gain) and gain >= 0.0):
+                raise ValueError(f"{name} must be finite and >= 0")
+        m12_steps = self._dev_f64(m12_steps, (n_steps, 12, n), "m12_steps")
+        start_joints = self._dev_f64(start_joints, (n, 7), "start_joints")
+        feedforward = None if feedforward is None else self._dev_f64(feedforward, (n_steps, n, 6), "feedforward")
+        rest_joints = None if rest_joints is None else self._dev_f64(rest_joints, (n, 7), "rest_joints")
+        if isinstance(damping, (int, float)):
+            damping_host, damping = float(damping), None
+            if not (np.isfinite(damping_host) and damping_host > 0.0):
+                raise ValueError("damping must be finite and > 0")
+        else:
+            damping_host, damping = 0.0, self._dev_f64(damping, (n,), "damping")
+        lim, lim_p = None, None
+        if limits is not None:
+            lim = np.ascontiguousarray(limits.cpu().numpy() if isinstance(limits, torch.Tensor) else limits, dtype=np.float64)
+            if lim.shape != (3, 7) or np.isnan(lim).any() or not (lim[0] > 0.0).all() or not (lim[1] <= lim[2]).all():
+                raise ValueError("limits must be [3, 7]: rate_max > 0, q_min <= q_max, no NaN")
+            lim_p = lim.ctypes.data_as(C.POINTER(C.c_double))
+        arm = self._arm_ids(arm, n)
+        shapes = {"joints": (n_steps, n, 7), "rates": (n_steps, n, 7), "err": (n_steps, n, 2), "final_joints": (n, 7), "final_err": (n, 2)}
+        res = {name: self._out_buf(out, name, shapes[name], _F64) for name in self.TRACK_OUTPUTS if name in want}
+        cargs = (n, n_steps, _ptr(m12_steps), _ptr(arm), int(arm_uniform), _ptr(start_joints), dt, kp, ko, _ptr(feedforward),
+                 damping_host, _ptr(damping), _ptr(rest_joints), rest_gain, lim_p) + tuple(_ptr(res.get(name)) for name in self.TRACK_OUTPUTS)
+        return self._finish(res, "rsik_track", cargs, plan_only, (m12_steps, start_joints, feedforward, damping, rest_joints, arm, lim))
+
     # ------------------------------------------------------------------ measurement hooks
     def clock_monitor(self, seconds: float, n_waves: int = 64, stream: Optional[torch.cuda.Stream] = None):
         """Starts rsik_debug_math op 8 on `stream` (a side stream, so that it runs BESIDE whatever the main stream is

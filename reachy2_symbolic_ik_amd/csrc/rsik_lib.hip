@@ -41,6 +41,7 @@
 #include "rsik_kernel_reach_map.hpp"
 #include "rsik_kernel_jacobian.hpp"
 #include "rsik_kernel_joint_rates.hpp"
+#include "rsik_kernel_track.hpp"
 
 // =====================================================================================
 // C ABI
@@ -1055,6 +1056,49 @@ int rsik_joint_rates(rsik_ctx* ctx, int64_t n, int64_t n_rep, const double* join
                 if constexpr (WR() || WA())
                     hipLaunchKernelGGL((rsik::joint_rates_kernel<MIXED(), BIAS(), WR(), WA()>), grid, block, 0, ctx->stream, K); }); }); }); });
     }
+    return launch_end(ctx);
+}
+
+int rsik_track(rsik_ctx* ctx, int64_t n, int64_t n_steps, const double* m12_steps, const uint8_t* arm, int arm_uniform,
+               const double* start_joints, double dt, double kp, double ko, const double* feedforward_steps, double damping_host,
+               const double* damping, const double* rest_joints, double rest_gain, const double* limits_host, double* joints_steps,
+               double* rates_steps, double* err_steps, double* final_joints, double* final_err) {
+    if (!ctx) return RSIK_E_INVALID;
+    const char* who = "rsik_track";
+    const auto gain_ok = [](double g) { return std::isfinite(g) && g >= 0.0; };
+    if (n < 0) return fail(ctx, RSIK_E_INVALID, "rsik_track: n < 0");
+    if (n_steps < 1 || n_steps > 65536) return fail(ctx, RSIK_E_INVALID, "rsik_track: n_steps must be 1 ... 65536");
+    if (n == 0) return RSIK_OK;
+    if (!m12_steps || !start_joints) return fail(ctx, RSIK_E_INVALID, "rsik_track: m12_steps or start_joints is NULL");
+    if (!joints_steps && !rates_steps && !err_steps && !final_joints && !final_err)
+        return fail(ctx, RSIK_E_INVALID, "rsik_track: all five outputs are NULL");
+    if (!(std::isfinite(dt) && dt > 0.0)) return fail(ctx, RSIK_E_INVALID, "rsik_track: dt must be finite and > 0");
+    if (!gain_ok(kp) || !gain_ok(ko)) return fail(ctx, RSIK_E_INVALID, "rsik_track: kp and ko must be finite and >= 0");
+    if (rest_joints && !gain_ok(rest_gain)) return fail(ctx, RSIK_E_INVALID, "rsik_track: rest_gain must be finite and >= 0");
+    if (!damping && !rsik::damping_usable(damping_host))
+        return fail(ctx, RSIK_E_INVALID, "rsik_track: damping_host must be finite and > 0 (its square a normal double)");
+    for (int k = 0; limits_host && k < 7; k++) {
+        const double rate_max = limits_host[k], q_min = limits_host[7 + k], q_max = limits_host[14 + k];
+        if (!(rate_max > 0.0) || !(q_min <= q_max))  // (a NaN fails both)
+            return fail(ctx, RSIK_E_INVALID, "rsik_track: limits_host needs rate_max > 0 and q_min <= q_max, and no NaN");
+    }
+    int rc = check_arms(ctx, arm, arm_uniform, who);
+    if (rc != RSIK_OK) return rc;
+    rsik::TrackArgs K;
+    std::memset(&K, 0, sizeof K);
+    K.n = n; K.n_steps = n_steps; K.m12_steps = m12_steps; K.arm = arm; K.start_joints = start_joints;
+    K.feedforward = feedforward_steps; K.damping = damping; K.rest_joints = rest_joints;
+    K.joints_steps = joints_steps; K.rates_steps = rates_steps; K.err_steps = err_steps; K.final_joints = final_joints; K.final_err = final_err;
+    K.damping_host = damping ? 0.0 : damping_host; K.dt = dt; K.kp = kp; K.ko = ko; K.rest_gain = rest_joints ? rest_gain : 0.0;
+    if (limits_host) { fill7(K.rate_max, limits_host, 0.0); fill7(K.q_min, limits_host + 7, 0.0); fill7(K.q_max, limits_host + 14, 0.0); }
+    bind_arms(ctx, arm, arm_uniform, K.arms);
+    dim3 grid, block(rsik::kTrackBlock);
+    if ((rc = launch_begin(ctx, n, &grid, who, rsik::kTrackBlock)) != RSIK_OK) return rc;
+    with_bool(arm != nullptr, [&](auto MIXED) { with_bool(joints_steps != nullptr, [&](auto WJ) { with_bool(rates_steps != nullptr, [&](auto WR) {
+        with_bool(err_steps != nullptr, [&](auto WE) { with_bool(feedforward_steps != nullptr, [&](auto FF) {
+            with_bool(rest_joints != nullptr, [&](auto REST) { with_bool(limits_host != nullptr, [&](auto LIM) {
+                constexpr int OUTS = (WJ() ? rsik::kTrackJoints : 0) | (WR() ? rsik::kTrackRates : 0) | (WE() ? rsik::kTrackErr : 0);
+                hipLaunchKernelGGL((rsik::track_kernel<MIXED(), OUTS, FF(), REST(), LIM()>), grid, block, 0, ctx->stream, K); }); }); }); }); }); }); });
     return launch_end(ctx);
 }
 

@@ -481,6 +481,20 @@ class SymbolicIK:
         in joints, twist or bias, or a lambda that is NaN, infinite or <= 0, is NaN in every output."""
         return _joint_rates_batch(self, {"arm_uniform": self.arm_id}, joints, twist, damping, bias_rates, want, out, plan_only)
 
+    def track_batch(self, goals: Any, start_joints: Any, dt: float, kp: float, ko: float, damping: Any, feedforward: Any = None,
+                    rest_joints: Any = None, rest_gain: float = 0.0, limits: Any = None, want: Sequence[str] = ("joints",),
+                    out: Optional[Dict[str, torch.Tensor]] = None, plan_only: bool = False) -> Dict[str, torch.Tensor]:
+        """This arm follows n goal trajectories over T steps in closed loop, every step in one launch (HipSolver.track, rsik_track).
+        goals: [T,12,n] (R row-major, then t: what control_continuous_run takes) or matrices [T,n,4,4]; start_joints [n,7]: any
+        joints.  Per step: forward kinematics, e_p = p_g - p and e_o the rotation vector of R_g R^T, the twist
+        feedforward[t] + (kp e_p, ko e_o), the rates of joint_rates_batch for it with bias rest_gain (rest_joints - q), one common
+        factor so that no rate exceeds limits[0], q := q + dt q' clamped to [limits[1], limits[2]].  Returns the outputs named in
+        want, of HipSolver.TRACK_OUTPUTS: joints [T,n,7], rates [T,n,7], err [T,n,2] (m, rad; what each step saw before it moved),
+        final_joints [n,7], final_err [n,2].  Where solve_batch answers NaN (a goal out of reach, the wrist limit) the loop goes as
+        near as the damping lets it; a step whose goal is not numbers is skipped."""
+        return _track_batch(self, {"arm_uniform": self.arm_id}, goals, start_joints, dt, kp, ko, damping, feedforward, rest_joints,
+                            rest_gain, limits, want, out, plan_only)
+
     def fk_residual_batch(self, poses: Any, joints: Any) -> torch.Tensor:
         """err [n,2] = (position error m, rotation error rad) of FK(joints) against the poses they were solved for."""
         self._upload()
@@ -583,6 +597,16 @@ def _joint_rates_batch(ik, arm, joints, twist, damping, bias_rates, want, out, p
     return ik._solver.joint_rates(joints, twist, damping=damping, bias_rates=bias_rates, want=want, out=out, plan_only=plan_only, **arm)
 
 
+def _track_batch(ik, arm, goals, start_joints, dt, kp, ko, damping, feedforward, rest_joints, rest_gain, limits, want, out, plan_only):
+    g = goals if isinstance(goals, torch.Tensor) else torch.as_tensor(np.asarray(goals, dtype=np.float64))
+    g = g.to(device=ik._solver.device, dtype=torch.float64)
+    if g.dim() == 4 and tuple(g.shape[2:]) == (4, 4):  # [T,n,4,4] -> [T,12,n]
+        g = torch.cat([g[..., :3, :3].reshape(g.shape[0], g.shape[1], 9), g[..., :3, 3]], dim=2).permute(0, 2, 1).contiguous()
+    ik._upload()
+    return ik._solver.track(g, start_joints, dt, kp, ko, damping=damping, feedforward=feedforward, rest_joints=rest_joints,
+                            rest_gain=rest_gain, limits=limits, want=want, out=out, plan_only=plan_only, **arm)
+
+
 def unpack_reach_mask(mask: torch.Tensor, n_rot: int) -> torch.Tensor:
     """The `mask` of reach_map_batch / HipSolver.reach_map, [n_pos, ceil(n_rot/64)] int64, as a bool tensor [n_pos, n_rot]:
     entry (i, j) is pose (i, j)'s reachable flag."""
@@ -667,6 +691,16 @@ class DualArmIK:
         joints [K,n,7]): rates [...,7], the minimiser of |J q' - twist|^2 + lambda^2 |q' - q0|^2 (q0 = bias_rates or zero), from
         (J J^T + lambda^2 I) y = twist - J q0 by L D L^T with the pivot clamp at lambda^2, and achieved_twist [...,6] = J . rates."""
         return _joint_rates_batch(self, {"arm": arm_ids}, joints, twist, damping, bias_rates, want, out, plan_only)
+
+    def track_batch(self, arm_ids: Any, goals: Any, start_joints: Any, dt: float, kp: float, ko: float, damping: Any,
+                    feedforward: Any = None, rest_joints: Any = None, rest_gain: float = 0.0, limits: Any = None,
+                    want: Sequence[str] = ("joints",), out: Optional[Dict[str, torch.Tensor]] = None,
+                    plan_only: bool = False) -> Dict[str, torch.Tensor]:
+        """SymbolicIK.track_batch for trajectories of both arms (arm_ids [n] uint8, one byte per trajectory): closed-loop tracking of
+        goals [T,12,n] from start_joints [n,7] in one launch: joints [T,n,7], rates [T,n,7], err [T,n,2], final_joints [n,7],
+        final_err [n,2], as named in want."""
+        return _track_batch(self, {"arm": arm_ids}, goals, start_joints, dt, kp, ko, damping, feedforward, rest_joints, rest_gain,
+                            limits, want, out, plan_only)
 
     def theta_from_joints_batch(self, arm_ids: Any, poses: Any, current_joints: Any, preferred_theta: Optional[Sequence[float]] = None,
                                 out: Optional[Dict[str, torch.Tensor]] = None, plan_only: bool = False) -> Dict[str, torch.Tensor]:
