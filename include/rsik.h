@@ -954,6 +954,54 @@ int rsik_track(rsik_ctx *ctx, int64_t n, int64_t n_steps, const double *m12_step
                double *joints_steps, double *rates_steps, double *err_steps, double *final_joints, double *final_err);
 
 /*
+ * rsik_clearance — how far the arm is from a set of obstacles, which link and which obstacle are nearest, where, and how the distance
+ * changes with the joints, for n rows of joints from one launch (added within ABI version 8: one symbol, no option, no workspace).
+ * What a planner asks of the K elbow angles of a sweep ("which keep the arm off the table, the torso, the other arm?"), and what a
+ * caller of rsik_joint_rates or rsik_track puts into bias_rates for obstacle avoidance in the null space.  The reference has nothing
+ * of the kind.
+ *
+ * The arm is three capsules: link 0 shoulder -> elbow, link 1 elbow -> wrist, link 2 wrist -> goal origin (the position
+ * rsik_forward_kinematics returns, RSIK_C_TIPL included), with the radii link_radius_host[0..2].  The end points are the origins of
+ * the joints: joints 0, 1 at the shoulder, 2, 3 at the elbow, 4, 5, 6 at the wrist.
+ *
+ *   joints, n_rep, arm / arm_uniform   exactly as rsik_jacobian: joints [n_rep][n][7], arm [n] shared by every repetition or NULL;
+ *                    n_rep > 1 takes a sweep's or a path's joints in place
+ *   link_radius_host 3 doubles on the HOST, or NULL for zeros; each finite and >= 0, otherwise RSIK_E_INVALID
+ *   n_spheres, spheres   0 ... 4096 rows [n_spheres][4] device, row-major: (x, y, z, r) in the torso frame
+ *   n_capsules, capsules 0 ... 256 rows [n_capsules][7] device: (ax, ay, az, bx, by, bz, r); a == b is allowed (a sphere)
+ *                    At least one obstacle in all; a count outside its range is RSIK_E_INVALID.  The obstacles are shared by every
+ *                    row and every repetition.  Obstacle index o: spheres are 0 ... n_spheres - 1, capsule j is n_spheres + j.
+ *   clearance        [n_rep][n] or NULL: the minimum, over the 3 links and all usable obstacles, of (distance between the link's axis
+ *                    segment and the obstacle's axis segment or centre) - link radius - obstacle radius.  The distance is the true
+ *                    minimum of |x - y| over the two segments.  Negative: the radii penetrate; touching AXES give -(r_link + r_obs).
+ *                    An axis distance below 1.1e-136 m counts as touching.
+ *   nearest          [n_rep][n][2] int32 or NULL, aligned to 8 bytes: (link, obstacle index) of the pair that gives the minimum.
+ *                    Pairs are compared on the clearance as computed; the first minimum wins in the order (obstacle 0, link 0),
+ *                    (obstacle 0, link 1), (obstacle 0, link 2), (obstacle 1, link 0) ...
+ *   witness          [n_rep][n][2][3] or NULL: x on the link's axis and y on the obstacle's axis for the winning pair, a pair that
+ *                    attains the distance (not unique for parallel segments)
+ *   gradient         [n_rep][n][7] or NULL: d clearance / d joints of the winning pair, g_k = u . (a_k x (x - o_k)) for the joints that
+ *                    move the link (0-1 for link 0, 0-3 for link 1, 0-6 for link 2) and 0 for the others, with a_k, o_k the axis and
+ *                    origin of joint k as in rsik_jacobian and u = (x - y) / |x - y|.  Where the axes touch it is the zero vector.
+ *                    k * gradient as bias_rates of rsik_joint_rates or rsik_track moves the arm away in the null space.
+ *   link_points      [n_rep][n][4][3] or NULL: shoulder, elbow, wrist, goal origin — for drawing, and what a caller turns into the
+ *                    three capsules of this arm as obstacles for the other one
+ * Any output may be NULL, all five NULL is RSIK_E_INVALID.  The bits of an output depend neither on which others were requested, nor
+ * on n, n_rep or the arm form; clearance does not depend on the order of the obstacles; two launches give the same bits.
+ * A row with a NaN or an infinity among its joints gives NaN outputs and nearest (-1, -1) and changes no other row.  An obstacle whose
+ * row holds a NaN or an infinity, or a negative radius, is skipped: it is never the nearest and changes nothing else.  If every
+ * obstacle is skipped: clearance +infinity, nearest (-1, -1), gradient 0, witness NaN.  A finite angle of any size is answered as
+ * rsik_jacobian answers it.
+ * n == 0 launches nothing; n < 0, n_rep < 1, joints == NULL, a NULL obstacle array with a count above 0 give RSIK_E_INVALID, the arm
+ * checks and their codes are rsik_jacobian's (RSIK_E_NOT_SET included).  Enqueued on the context's stream; allocates nothing, needs no
+ * workspace and never waits for the device.
+ */
+int rsik_clearance(rsik_ctx *ctx, int64_t n, int64_t n_rep, const double *joints, const uint8_t *arm, int arm_uniform,
+                   const double *link_radius_host,
+                   int n_spheres, const double *spheres, int n_capsules, const double *capsules,
+                   double *clearance, int32_t *nearest, double *gradient, double *witness, double *link_points);
+
+/*
  * Multi-GPU.  Poses are independent, so a job is sharded across the GPUs of a node — one process and one
  * rsik context per GPU — with no data-path collective; the only exchange is the all-gather of the final arrays
  * (joints [n,7], state [n]) over RCCL / xGMI.  The reference has nothing distributed (single-threaded Python).  Python

@@ -1015,6 +1015,81 @@ class HipSolver:
                  damping_host, _ptr(damping), _ptr(rest_joints), rest_gain, lim_p) + tuple(_ptr(res.get(name)) for name in self.TRACK_OUTPUTS)
         return self._finish(res, "rsik_track", cargs, plan_only, (m12_steps, start_joints, feedforward, damping, rest_joints, arm, lim))
 
+    # ------------------------------------------------------------------ rsik_clearance
+    CLEARANCE_OUTPUTS = ("clearance", "nearest", "gradient", "witness", "link_points")
+    CLEARANCE_MAX_SPHERES, CLEARANCE_MAX_CAPSULES = 4096, 256
+
+    def clearance(
+        self,
+        joints: torch.Tensor,
+        spheres: Optional[torch.Tensor] = None,
+        capsules: Optional[torch.Tensor] = None,
+        link_radius: Any = None,
+        arm: Optional[torch.Tensor] = None,
+        arm_uniform: int = 0,
+        want: Sequence[str] = ("clearance", "nearest"),
+        out: Optional[Dict[str, torch.Tensor]] = None,
+        plan_only: bool = False,
+    ) -> Dict[str, torch.Tensor]:
+        """How far the arm is from a set of obstacles, from one launch (rsik_clearance).  The arm is three capsules — link 0
+        shoulder -> elbow, link 1 elbow -> wrist, link 2 wrist -> goal origin (forward_kinematics' position) — with the radii
+        link_radius (3 values on the host, or None for zeros).  joints: [n, 7] or [n_rep, n, 7] as jacobian() takes them (a sweep's
+        or a path's joints in place); spheres: [S, 4] rows (x, y, z, r), S <= 4096, or None; capsules: [Cp, 7] rows (a, b, r),
+        Cp <= 256, a == b allowed, or None; torso frame, shared by every row; at least one obstacle.  arm / arm_uniform as jacobian().
+        `want`: which of CLEARANCE_OUTPUTS to compute, at least one; the bits of one do not depend on the others.  Returns device
+        tensors shaped like the joints' leading dimensions:
+        clearance [...]: the minimum over links and obstacles of (distance between the axis segments) - link radius - obstacle
+        radius; negative where the radii penetrate;
+        nearest [..., 2] int32: (link, obstacle index) of the pair that gives it — spheres are 0 ... S - 1, capsule j is S + j; the
+        first minimum in the order (obstacle 0, link 0), (obstacle 0, link 1), (obstacle 0, link 2), (obstacle 1, link 0) ...;
+        witness [..., 2, 3]: x on the link's axis and y on the obstacle's axis, a pair that attains the distance;
+        gradient [..., 7]: d clearance / d joints of that pair, u . (a_k x (x - o_k)) for the joints that move the link, 0 for the
+        others and the zero vector where the axes touch: k * gradient is a bias_rates for joint_rates() and track();
+        link_points [..., 4, 3]: shoulder, elbow, wrist, goal origin.
+        A row with a NaN or an infinity among its joints is NaN with nearest (-1, -1).  An obstacle row with a NaN, an infinity or a
+        negative radius is skipped; if all are: clearance +inf, nearest (-1, -1), gradient 0, witness NaN.
+        plan_only=True launches nothing and adds res["launch"], a zero-overhead re-launch callable (see plan())."""
+        if not isinstance(joints, torch.Tensor):
+            joints = torch.as_tensor(np.asarray(joints, dtype=np.float64))
+        if joints.dim() not in (2, 3) or joints.shape[-1] != 7:
+            raise ValueError("joints must have shape [n, 7] or [n_rep, n, 7]")
+        lead = tuple(int(v) for v in joints.shape[:-1])
+        n_rep, n = (1, lead[0]) if len(lead) == 1 else lead
+        if n_rep < 1:
+            raise ValueError("joints: at least one repetition")
+        want = tuple(want)
+        if not want or any(name not in self.CLEARANCE_OUTPUTS for name in want):
+            raise ValueError(f"want must name at least one of {self.CLEARANCE_OUTPUTS}")
+
+        def rows(t, width, most, name):
+            if t is None:
+                return None, 0
+            if not isinstance(t, torch.Tensor):
+                t = torch.as_tensor(np.asarray(t, dtype=np.float64))
+            if t.dim() != 2 or t.shape[1] != width or t.shape[0] > most:
+                raise ValueError(f"{name} must have shape [k, {width}] with k <= {most}")
+            count = int(t.shape[0])
+            return (self._dev_f64(t, (count, width), name) if count else None), count
+
+        spheres, n_spheres = rows(spheres, 4, self.CLEARANCE_MAX_SPHERES, "spheres")
+        capsules, n_capsules = rows(capsules, 7, self.CLEARANCE_MAX_CAPSULES, "capsules")
+        if n_spheres + n_capsules < 1:
+            raise ValueError("at least one obstacle: spheres [k, 4] or capsules [k, 7]")
+        rad, rad_p = None, None
+        if link_radius is not None:
+            rad = np.ascontiguousarray(link_radius.cpu().numpy() if isinstance(link_radius, torch.Tensor) else link_radius, dtype=np.float64)
+            if rad.shape != (3,) or not np.isfinite(rad).all() or not (rad >= 0.0).all():
+                raise ValueError("link_radius must be 3 finite values >= 0")
+            rad_p = rad.ctypes.data_as(C.POINTER(C.c_double))
+        joints = self._dev_f64(joints, lead + (7,), "joints")
+        arm = self._arm_ids(arm, n)
+        shapes = {"clearance": lead, "nearest": lead + (2,), "gradient": lead + (7,), "witness": lead + (2, 3), "link_points": lead + (4, 3)}
+        res = {name: self._out_buf(out, name, shapes[name], torch.int32 if name == "nearest" else _F64)
+               for name in self.CLEARANCE_OUTPUTS if name in want}
+        cargs = (n, n_rep, _ptr(joints), _ptr(arm), int(arm_uniform), rad_p, n_spheres, _ptr(spheres), n_capsules, _ptr(capsules)) \
+            + tuple(_ptr(res.get(name)) for name in self.CLEARANCE_OUTPUTS)
+        return self._finish(res, "rsik_clearance", cargs, plan_only, (joints, arm, spheres, capsules, rad))
+
     # ------------------------------------------------------------------ measurement hooks
     def clock_monitor(self, seconds: float, n_waves: int = 64, stream: Optional[torch.cuda.Stream] = None):
         """Starts rsik_debug_math op 8 on `stream` (a side stream, so that it runs BESIDE whatever the main stream is

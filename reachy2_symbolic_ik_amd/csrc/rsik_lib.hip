@@ -42,6 +42,7 @@
 #include "rsik_kernel_jacobian.hpp"
 #include "rsik_kernel_joint_rates.hpp"
 #include "rsik_kernel_track.hpp"
+#include "rsik_kernel_clearance.hpp"
 
 // =====================================================================================
 // C ABI
@@ -1099,6 +1100,52 @@ int rsik_track(rsik_ctx* ctx, int64_t n, int64_t n_steps, const double* m12_step
             with_bool(rest_joints != nullptr, [&](auto REST) { with_bool(limits_host != nullptr, [&](auto LIM) {
                 constexpr int OUTS = (WJ() ? rsik::kTrackJoints : 0) | (WR() ? rsik::kTrackRates : 0) | (WE() ? rsik::kTrackErr : 0);
                 hipLaunchKernelGGL((rsik::track_kernel<MIXED(), OUTS, FF(), REST(), LIM()>), grid, block, 0, ctx->stream, K); }); }); }); }); }); }); });
+    return launch_end(ctx);
+}
+
+int rsik_clearance(rsik_ctx* ctx, int64_t n, int64_t n_rep, const double* joints, const uint8_t* arm, int arm_uniform,
+                   const double* link_radius_host, int n_spheres, const double* spheres, int n_capsules, const double* capsules,
+                   double* clearance, int32_t* nearest, double* gradient, double* witness, double* link_points) {
+    if (!ctx) return RSIK_E_INVALID;
+    const char* who = "rsik_clearance";
+    if (n < 0) return fail(ctx, RSIK_E_INVALID, "rsik_clearance: n < 0");
+    if (n_rep < 1) return fail(ctx, RSIK_E_INVALID, "rsik_clearance: n_rep < 1");
+    if (n_spheres < 0 || n_spheres > rsik::kClrMaxSpheres) return fail(ctx, RSIK_E_INVALID, "rsik_clearance: n_spheres must be 0 ... 4096");
+    if (n_capsules < 0 || n_capsules > rsik::kClrMaxCapsules) return fail(ctx, RSIK_E_INVALID, "rsik_clearance: n_capsules must be 0 ... 256");
+    if (n_spheres + n_capsules < 1) return fail(ctx, RSIK_E_INVALID, "rsik_clearance: at least one obstacle");
+    for (int l = 0; link_radius_host && l < 3; l++)
+        if (!(std::isfinite(link_radius_host[l]) && link_radius_host[l] >= 0.0))
+            return fail(ctx, RSIK_E_INVALID, "rsik_clearance: every link radius must be finite and >= 0");
+    if (n == 0) return RSIK_OK;
+    if (!joints || (!clearance && !nearest && !gradient && !witness && !link_points))
+        return fail(ctx, RSIK_E_INVALID, "rsik_clearance: joints or all five outputs are NULL");
+    if ((n_spheres > 0 && !spheres) || (n_capsules > 0 && !capsules))
+        return fail(ctx, RSIK_E_INVALID, "rsik_clearance: spheres or capsules is NULL with a count above 0");
+    if (((uintptr_t)nearest & 7) != 0) return fail(ctx, RSIK_E_INVALID, "rsik_clearance: nearest must be aligned to 8 bytes");
+    int rc = check_arms(ctx, arm, arm_uniform, who);
+    if (rc != RSIK_OK) return rc;
+    rsik::ClearanceArgs K;
+    std::memset(&K, 0, sizeof K);
+    K.n = n;
+    K.arm = arm;
+    K.spheres = spheres; K.capsules = capsules; K.n_spheres = n_spheres; K.n_capsules = n_capsules;
+    for (int l = 0; l < 3; l++) K.link_radius[l] = link_radius_host ? link_radius_host[l] : 0.0;
+    bind_arms(ctx, arm, arm_uniform, K.arms);
+    dim3 grid, block(rsik::kBlock);
+    if ((rc = launch_begin(ctx, n, &grid, who)) != RSIK_OK) return rc;
+    // the repetition is the grid's y, as in rsik_jacobian: one launch per 65535 repetitions, each on its own slice
+    for (int64_t rep0 = 0; rep0 < n_rep; rep0 += 65535) {
+        const int64_t first = rep0 * n;
+        grid.y = (unsigned)std::min<int64_t>(n_rep - rep0, 65535);
+        K.joints = joints + first * 7;
+        K.clearance = clearance ? clearance + first : nullptr;
+        K.nearest = nearest ? nearest + first * 2 : nullptr;
+        K.gradient = gradient ? gradient + first * 7 : nullptr;
+        K.witness = witness ? witness + first * 6 : nullptr;
+        K.link_points = link_points ? link_points + first * 12 : nullptr;
+        with_bool(arm != nullptr, [&](auto MIXED) { with_bool(gradient != nullptr || witness != nullptr, [&](auto WIT) {
+            hipLaunchKernelGGL((rsik::clearance_kernel<MIXED(), WIT()>), grid, block, 0, ctx->stream, K); }); });
+    }
     return launch_end(ctx);
 }
 

@@ -495,6 +495,20 @@ class SymbolicIK:
         return _track_batch(self, {"arm_uniform": self.arm_id}, goals, start_joints, dt, kp, ko, damping, feedforward, rest_joints,
                             rest_gain, limits, want, out, plan_only)
 
+    def clearance_batch(self, joints: Any, spheres: Any = None, capsules: Any = None, link_radius: Any = None,
+                        want: Sequence[str] = ("clearance", "nearest"), out: Optional[Dict[str, torch.Tensor]] = None,
+                        plan_only: bool = False) -> Dict[str, torch.Tensor]:
+        """How far this arm is from a set of obstacles, in one launch (HipSolver.clearance, rsik_clearance).  The arm is three
+        capsules (shoulder -> elbow -> wrist -> goal origin) of the radii link_radius (3 values, None for zeros); joints: [n,7], or
+        [K,n,7] as sweep_batch and path_batch return them (judged in place); spheres [S,4] rows (x, y, z, r), capsules [Cp,7] rows
+        (a, b, r), in the torso frame, shared by every row, at least one in all.  Returns the outputs named in want, of
+        HipSolver.CLEARANCE_OUTPUTS: clearance [...] (axis distance minus both radii of the nearest pair, negative inside),
+        nearest [...,2] int32 (link, obstacle index; capsule j is S + j), witness [...,2,3] (the point on the link's axis and the point
+        on the obstacle's), gradient [...,7] (d clearance / d joints of that pair, zero where the axes touch; k * gradient is a
+        bias_rates for joint_rates_batch and track_batch), link_points [...,4,3] (shoulder, elbow, wrist, goal origin).  A row of
+        joints that is not numbers is NaN with nearest (-1, -1); an obstacle that is not numbers or has a negative radius is skipped."""
+        return _clearance_batch(self, {"arm_uniform": self.arm_id}, joints, spheres, capsules, link_radius, want, out, plan_only)
+
     def fk_residual_batch(self, poses: Any, joints: Any) -> torch.Tensor:
         """err [n,2] = (position error m, rotation error rad) of FK(joints) against the poses they were solved for."""
         self._upload()
@@ -607,6 +621,23 @@ def _track_batch(ik, arm, goals, start_joints, dt, kp, ko, damping, feedforward,
                             rest_gain=rest_gain, limits=limits, want=want, out=out, plan_only=plan_only, **arm)
 
 
+def _clearance_batch(ik, arm, joints, spheres, capsules, link_radius, want, out, plan_only):
+    ik._upload()
+    return ik._solver.clearance(joints, spheres=spheres, capsules=capsules, link_radius=link_radius, want=want, out=out,
+                                plan_only=plan_only, **arm)
+
+
+def arm_capsules(link_points: torch.Tensor, link_radius: Any = None) -> torch.Tensor:
+    """The three capsules [3,7] (a, b, r) of an arm from ONE row of clearance_batch's link_points [4,3] and its link radii (3
+    values, None for zeros): what the other arm takes as obstacles.  Stays on link_points' device; nothing waits."""
+    p = link_points.reshape(4, 3)
+    if link_radius is None:
+        r = torch.zeros(3, dtype=p.dtype)
+    else:
+        r = link_radius if isinstance(link_radius, torch.Tensor) else torch.as_tensor(np.asarray(link_radius, dtype=np.float64))
+    return torch.cat([p[:3], p[1:], r.to(device=p.device, dtype=p.dtype).reshape(3, 1)], dim=1)
+
+
 def unpack_reach_mask(mask: torch.Tensor, n_rot: int) -> torch.Tensor:
     """The `mask` of reach_map_batch / HipSolver.reach_map, [n_pos, ceil(n_rot/64)] int64, as a bool tensor [n_pos, n_rot]:
     entry (i, j) is pose (i, j)'s reachable flag."""
@@ -701,6 +732,31 @@ class DualArmIK:
         final_err [n,2], as named in want."""
         return _track_batch(self, {"arm": arm_ids}, goals, start_joints, dt, kp, ko, damping, feedforward, rest_joints, rest_gain,
                             limits, want, out, plan_only)
+
+    def clearance_batch(self, arm_ids: Any, joints: Any, spheres: Any = None, capsules: Any = None, link_radius: Any = None,
+                        other_arm: Optional[Tuple[int, Any]] = None, want: Sequence[str] = ("clearance", "nearest"),
+                        out: Optional[Dict[str, torch.Tensor]] = None, plan_only: bool = False) -> Dict[str, torch.Tensor]:
+        """SymbolicIK.clearance_batch for rows of both arms (arm_ids [n] uint8, one byte per row, shared by every repetition of
+        joints [K,n,7]): clearance [...], nearest [...,2] int32 (link, obstacle index), witness [...,2,3], gradient [...,7] (k *
+        gradient is a bias_rates for joint_rates_batch and track_batch), link_points [...,4,3], as named in want.
+        other_arm = (arm_id, joints7): adds the three capsules of that arm (0 = r, 1 = l) at the one row of joints [7] to the obstacle
+        list, behind the caller's capsules (their obstacle indices are S + Cp ... S + Cp + 2, link 0 first), with the radii
+        link_radius.  They are built on the device from that arm's link_points (one launch more, nothing waits) and meet EVERY row, so
+        the rows should be the opposite arm's: a row of the same arm finds itself at distance 0."""
+        if other_arm is not None:
+            side, q = other_arm
+            self._upload()
+            dev = self._solver.device
+            q = (q if isinstance(q, torch.Tensor) else torch.as_tensor(np.asarray(q, dtype=np.float64))).to(device=dev, dtype=torch.float64)
+            lp = self._solver.clearance(q.reshape(1, 7), spheres=torch.zeros((1, 4), dtype=torch.float64, device=dev),
+                                        arm_uniform=int(side), want=("link_points",))["link_points"]
+            extra = arm_capsules(lp[0], link_radius)
+            if capsules is None:
+                capsules = extra
+            else:
+                given = capsules if isinstance(capsules, torch.Tensor) else torch.as_tensor(np.asarray(capsules, dtype=np.float64))
+                capsules = torch.cat([given.to(device=dev, dtype=torch.float64).reshape(-1, 7), extra], dim=0)
+        return _clearance_batch(self, {"arm": arm_ids}, joints, spheres, capsules, link_radius, want, out, plan_only)
 
     def theta_from_joints_batch(self, arm_ids: Any, poses: Any, current_joints: Any, preferred_theta: Optional[Sequence[float]] = None,
                                 out: Optional[Dict[str, torch.Tensor]] = None, plan_only: bool = False) -> Dict[str, torch.Tensor]:
