@@ -941,7 +941,10 @@ int rsik_joint_rates(rsik_ctx *ctx, int64_t n, int64_t n_rep, const double *join
  * trajectory NaN and changes nothing else.  A step whose goal or feed-forward holds a NaN or an infinity is skipped: q is held,
  * joints_steps[t] = q, rates_steps[t] = 0, err_steps[t] = NaN, and the trajectory goes on from there with the bits of the same run
  * without that step; final_err is NaN if the last goal is such a goal.  A finite angle of any size is answered as rsik_jacobian
- * answers it.
+ * answers it.  A goal or a feed-forward that is finite but so large that the arithmetic overflows is not an error: a step whose
+ * rates q' (step 5) do not come out finite is held like a skipped step (q held, rates_steps[t] = 0, err_steps[t] = NaN), with
+ * and without limits, and err_steps[t][0] and final_err[0] are +infinity where |e_p|^2 overflows (|e_p| >= 1.34e154) on a step
+ * that is taken.
  * n == 0 launches nothing; n < 0, n_steps outside 1 ... 65536, m12_steps == NULL, start_joints == NULL, all outputs NULL, a dt, gain,
  * damping_host or limit outside the above give RSIK_E_INVALID, the arm checks and their codes are rsik_jacobian's (RSIK_E_NOT_SET
  * included).  Enqueued on the context's stream; allocates nothing and never waits for the device.

@@ -130,7 +130,7 @@ __device__ __forceinline__ void track_chain(const Acc<MIXED>& A, double (&j)[7],
 //              rest posture and the limits exist.  A variant holds no register and issues no instruction for a term it does not
 //              have.  final_joints and final_err cost nothing per step: they are a uniform test of the pointer in the trip after the
 //              last step (final_err: the chain and the pose error once more).
-// A skipped step (goal or feed-forward not numbers) selects: joints held, rates 0, err NaN; no branch depends on data but the far-angle
+// A skipped step (goal or feed-forward not numbers, or rates that do not come out finite) selects: joints held, rates 0, err NaN; no branch depends on data but the far-angle
 // one of the chain, the order of every sum is fixed, so a trajectory's bits depend on the trajectory alone, and those of an output
 // do not depend on which others exist.
 template <bool MIXED, int OUTS, bool FF, bool REST, bool LIM>
@@ -171,7 +171,7 @@ __global__ __launch_bounds__(kTrackBlock, 1) void track_kernel(const TrackArgs K
     const double l2 = lambda * lambda;
     bool bad = !all_finite(q) || !damping_usable(lambda);
     if constexpr (REST) bad = bad || !all_finite(rest);
-    if (bad) {  // (a trajectory that is NaN everywhere: NaN from the start and kept NaN by step 7, with an infinite q_min or q_max too,
+    if (bad) {  // (a trajectory that is NaN everywhere: NaN from the start, and every step of it is held, since its rates are NaN; also
                 // so that an infinity does not walk the far-angle path every step)
 #pragma unroll
         for (int k = 0; k < 7; k++) q[k] = nan;
@@ -248,7 +248,9 @@ __global__ __launch_bounds__(kTrackBlock, 1) void track_kernel(const TrackArgs K
         const double s2 = dot(w, w), ep2 = dot(ep, ep);
         const double s = s2 > 0.0 ? sqrt_cr(s2) : 0.0;
         const double angle = fast_atan2(s, c);
-        double err[2] = {ep2 > 0.0 ? sqrt_cr(ep2) : 0.0, angle};
+        // (|e_p|^2 overflows from |e_p| = 1.34e154 on: sqrt_cr is for finite arguments, the answer there is +infinity)
+        const double ep_norm = ep2 < __builtin_inf() ? sqrt_cr(ep2) : __builtin_inf();
+        double err[2] = {ep2 > 0.0 ? ep_norm : 0.0, angle};
         if (last_look) {
 #pragma unroll
             for (int k = 0; k < 2; k++) err[k] = (bad || skip) ? nan : err[k];
@@ -335,6 +337,11 @@ __global__ __launch_bounds__(kTrackBlock, 1) void track_kernel(const TrackArgs K
             qd[k] = sum;
         }
 
+        // Rates that are not numbers (a finite goal or feed-forward so large that the twist or the solve overflows): the step is held
+        // like a skipped one.  Without this the clamp of step 7 would turn a NaN into q_min (fmin and fmax drop a NaN), and without
+        // a box the joints would be NaN from here on.  A trajectory that is NaN (bad) is held here at every step, and stays NaN.
+        skip = skip || !all_finite(qd);
+
         // 6. rate limit: one factor for the seven joints, so the direction is kept
         if constexpr (LIM) {
             double m = fabs(qd[0]) / K.rate_max[0];
@@ -349,10 +356,9 @@ __global__ __launch_bounds__(kTrackBlock, 1) void track_kernel(const TrackArgs K
 #pragma unroll
         for (int k = 0; k < 7; k++) {
             double moved = fma(K.dt, qd[k], q[k]);
-            if constexpr (LIM) {  // (fmin and fmax drop a NaN for the bound: a trajectory that is NaN stays NaN here too)
-                const double inside = fmin(fmax(moved, K.q_min[k]), K.q_max[k]);
-                moved = bad ? nan : inside;
-            }
+            // (fmin and fmax drop a NaN for the bound, but rates that are NaN never come here: the step is held, and a trajectory that
+            // is NaN, whose rates are NaN at every step, keeps its NaN joints)
+            if constexpr (LIM) moved = fmin(fmax(moved, K.q_min[k]), K.q_max[k]);
             q[k] = skip ? q[k] : moved;
             qd[k] = skip ? 0.0 : qd[k];
         }

@@ -15,86 +15,15 @@ import arm_pairs
 import jacobian_workload as JW
 import track_workload as TW
 from compare import bits
-from gpu_support import T, abi, arm_kwargs, last_error, ptr, raw_call, torch_mod  # noqa: F401
+from gpu_support import T, abi, last_error, ptr, raw_call, torch_mod  # noqa: F401
+from track_support import ALL, CONFIGS, NONE, OUTS, inputs, kind_arm, launch, row_alone, same, solver_of
+from track_support import solvers_do_not_outlive_the_module  # noqa: F401
+from track_workload import check_every_step, reference_terms
 
 pytestmark = pytest.mark.gpu
 
 SIZES = (1, 63, 64, 65, 257)
 STEPS = (1, 2, 33)
-OUTS = ("joints", "rates", "err", "final_joints", "final_err")
-NONE, ALL = (), ("ff", "rest", "limits")
-CONFIGS = tuple(itertools.product(TW.LAMBDAS, (NONE, ALL)))
-
-_SOLVERS = {}
-
-
-def solver_of(pair):
-    """The pair's solver, uploaded once for this module (the fixture below closes it when the module is done)."""
-    if pair not in _SOLVERS:
-        _SOLVERS[pair] = arm_pairs.upload(pair, **({"check": lambda p, b: None} if pair == "default/default" else {}))
-    return _SOLVERS[pair]
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _solvers_do_not_outlive_the_module(torch_mod):
-    yield
-    torch_mod.cuda.synchronize()
-    while _SOLVERS:
-        _SOLVERS.popitem()[1].close()
-    torch_mod.cuda.empty_cache()
-
-
-def kind_arm(kind, n):
-    return {"r": np.zeros(n, dtype=np.uint8), "l": np.ones(n, dtype=np.uint8), "mixed": JW.arm_bytes()[:n]}[kind]
-
-
-def inputs(pair, n, n_steps, arm, terms):
-    """The seeded inputs of a launch on the first n rows: dict of m12 [T,12,n], start [n,7], R, p and the terms' arrays."""
-    R, p = TW.goals_of(pair, n_steps, arm)
-    d = dict(R=R, p=p, m12=TW.m12_of(R, p), start=TW.starts()[:n], ff=None, rest=None, rest_gain=0.0, limits=None)
-    if "ff" in terms:
-        d["ff"] = np.ascontiguousarray(TW.feedforwards(n_steps)[:, :n])
-    if "rest" in terms:
-        d["rest"], d["rest_gain"] = TW.rests()[:n], TW.REST_GAIN
-    if "limits" in terms:
-        d["limits"] = TW.LIMITS
-    return d
-
-
-def launch(torch, pair, kind, arm, d, lam, want=OUTS, dt=TW.DT, kp=TW.KP, ko=TW.KO):
-    """One launch through HipSolver.track; lam a float or an array [n]; the results on the host."""
-    t = lambda a: None if a is None else T(a, torch)  # noqa: E731
-    res = solver_of(pair).track(T(d["m12"], torch), T(d["start"], torch), dt, kp, ko, damping=lam if isinstance(lam, float) else T(lam, torch),
-                                feedforward=t(d["ff"]), rest_joints=t(d["rest"]), rest_gain=d["rest_gain"], limits=d["limits"],
-                                want=want, **arm_kwargs(kind, arm, torch))
-    torch.cuda.synchronize()
-    assert tuple(res) == tuple(o for o in OUTS if o in want)
-    return {k: a.cpu().numpy() for k, a in res.items()}
-
-
-def same(a, b, what):
-    for k in b:
-        assert a[k].shape == b[k].shape and np.array_equal(bits(a[k]), bits(b[k])), (what, k)
-
-
-def reference_terms(d, t):
-    return dict(ff=None if d["ff"] is None else d["ff"][t], rest=d["rest"], rest_gain=d["rest_gain"], limits=d["limits"])
-
-
-def check_every_step(pair, arm, d, lam, got, what):
-    """The per-step check: the device's own joints_steps[t - 1] fed into one_step, joints_steps[t] within tol_t, err_steps[t] within
-    (E_p, E_o) of the reference's error at those joints.  Returns the worst error / tol_t."""
-    worst = 0.0
-    for t in range(len(d["m12"])):
-        before = d["start"] if t == 0 else got["joints"][t - 1]
-        ref = TW.step_by_arm(pair, arm, before, d["R"][t], d["p"][t], lam, **reference_terms(d, t))
-        e = np.linalg.norm(got["joints"][t] - ref["joints"], axis=1)
-        worst = max(worst, float((e / ref["tol"]).max()))
-        assert (e <= ref["tol"]).all(), (what, t, "joints", float((e / ref["tol"]).max()))
-        de = np.abs(got["err"][t] - ref["err"])
-        assert (de[:, 0] <= TW.E_P).all() and (de[:, 1] <= TW.E_O).all(), (what, t, "err", de.max(axis=0).tolist())
-        assert (ref["err"][:, 1] < 1.0).all(), (what, t, "the rotation error is to stay far below pi")
-    return worst
 
 
 # ------------------------------------------------------------------------------------------ 1. values and bits per shape
@@ -128,9 +57,7 @@ def test_every_shape_values_and_bits(torch_mod, pair):
                     print(f"{what}: every step within tol_t, worst error / tol_t {worst:.3g}")
                 if n == 257:
                     for i in (0, 64, 256):
-                        one = {k: (a if a is None or k in ("rest_gain", "limits") else np.ascontiguousarray(
-                            a[:, i:i + 1] if k in ("R", "p", "ff") else a[..., i:i + 1] if k == "m12" else a[i:i + 1])) for k, a in d.items()}
-                        alone = launch(torch, pair, kind, arm[i:i + 1], one, lam)
+                        alone = launch(torch, pair, kind, arm[i:i + 1], row_alone(d, i), lam)
                         for o in OUTS:
                             pick = got[o][:, i:i + 1] if got[o].ndim == 3 else got[o][i:i + 1]
                             assert np.array_equal(bits(alone[o]), bits(pick)), (what, o, f"trajectory {i} launched alone")

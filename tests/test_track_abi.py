@@ -162,3 +162,118 @@ def test_rotation_vector_helper_against_scipy():
     e_o, _ = TW.rotvec(tiny)
     w = 0.5 * np.stack([tiny[:, 2, 1] - tiny[:, 1, 2], tiny[:, 0, 2] - tiny[:, 2, 0], tiny[:, 1, 0] - tiny[:, 0, 1]], axis=1)
     assert np.array_equal(e_o, w)
+
+
+# ------------------------------------------------------------------------------------------ rotation errors of any size
+LADDER_ROWS = 64
+
+
+def _ladder_case(k):
+    """Rung k on LADDER_ROWS rows of custom/custom, r block: (R_g [n,3,3], R [n,3,3]) with seeded unit axes."""
+    block = JW.blocks_of("custom/custom")[0]
+    q = TW.starts(LADDER_ROWS)
+    axes = np.random.default_rng(7308 + k).normal(size=(LADDER_ROWS, 3))
+    axes /= np.linalg.norm(axes, axis=1, keepdims=True)
+    R_g, _ = TW.rotated_goals(block, q, axes, np.full(LADDER_ROWS, TW.LADDER[k]))
+    return R_g, JW.fk(block, q)[1]
+
+
+def test_the_ladder_keeps_clear_of_the_switch_near_pi():
+    """The ladder's band condition: |s^2 2^52 - 1| >= 2^-6 on every row that is not near 0, on the rows the GPU test launches (every
+    pair, an arm byte per row) and on the rows of the checks below, so that an s that differs by 3 e takes the same branch of e_o;
+    and the padded ladder holds every rung at least six times."""
+    angles, axes, rung = TW.ladder()
+    assert len(TW.LADDER) == 20 and np.bincount(rung).min() >= 6 and np.allclose(np.linalg.norm(axes, axis=1), 1.0, atol=1e-15)
+    for pair in TW.PAIRS:
+        g = TW.ladder_goals(pair, JW.arm_bytes()[:TW.N_LADDER], TW.starts()[:TW.N_LADDER])
+        margin = TW.band_margin(g["s"])[rung >= TW.NEAR_ZERO_RUNGS]
+        print(f"{pair}: smallest |s^2 2^52 - 1| away from 0: {margin.min():.4f}")
+        assert (margin >= TW.BAND).all(), pair
+        assert (6.0 * TW.FK_ENTRY / g["s"][(rung >= TW.NEAR_ZERO_RUNGS) & (rung < 19)] < TW.BAND / 64).all()
+    for k in range(TW.NEAR_ZERO_RUNGS, len(TW.LADDER)):
+        R_g, R = _ladder_case(k)
+        assert (TW.band_margin(TW.w_norm(R_g @ R.transpose(0, 2, 1))) >= TW.BAND).all(), k
+
+
+def test_e_o_bound_bounds_the_movement_of_the_reference():
+    """R perturbed by seeded noise of e = FK_ENTRY per entry: at every rung e_o moves by at most e_o_bound (2-norm) and the angle by
+    at most E_ANGLE, on 64 rows of custom/custom.  Measured: the worst movement / bound is 0.42, at the pi rung (0.18 at
+    pi - 2^-26 (1 + 2^-6), where the bound is 1.2e-5); the angle moves by at most 1.2e-14."""
+    noise = np.random.default_rng(7309).uniform(-TW.FK_ENTRY, TW.FK_ENTRY, size=(LADDER_ROWS, 3, 3))
+    worst = 0.0
+    for k, a in enumerate(TW.LADDER):
+        R_g, R = _ladder_case(k)
+        D = R_g @ R.transpose(0, 2, 1)
+        e_o, angle = TW.rotvec(D)
+        e_o2, angle2 = TW.rotvec(R_g @ (R + noise).transpose(0, 2, 1))
+        bound = TW.e_o_bound(angle, TW.w_norm(D))
+        ratio = float((np.linalg.norm(e_o2 - e_o, axis=1) / bound).max())
+        worst = max(worst, ratio)
+        print(f"rung {k:2d} angle {a!r}: e_o moves by at most {ratio:.3g} of e_o_bound ({bound.max():.3e}), the angle by {np.abs(angle2 - angle).max():.3e}")
+        assert ratio <= 1.0, (k, ratio)
+        assert (np.abs(angle2 - angle) <= TW.E_ANGLE).all(), k
+    print(f"worst movement / bound {worst:.3g}")
+
+
+def test_the_reference_angle_against_mpmath_and_at_a_half_turn():
+    """rotvec's angle against mpmath's angle of the same (R_g, R) pair at 50 digits, at every rung, 8 rows each: 4 ulp(pi) = 1.8e-15.
+    At the pi rung the reference's |e_o| is below 3 e and its angle within E_ANGLE of pi."""
+    import mpmath as mp
+
+    worst = 0.0
+    for k in range(len(TW.LADDER)):
+        R_g, R = (a[:8] for a in _ladder_case(k))
+        e_o, angle = TW.rotvec(R_g @ R.transpose(0, 2, 1))
+        with mp.workdps(50):
+            for i in range(len(R)):
+                D = mp.matrix(R_g[i].tolist()) * mp.matrix(R[i].tolist()).T
+                w = [(D[2, 1] - D[1, 2]) / 2, (D[0, 2] - D[2, 0]) / 2, (D[1, 0] - D[0, 1]) / 2]
+                want = mp.atan2(mp.sqrt(sum(x * x for x in w)), (D[0, 0] + D[1, 1] + D[2, 2] - 1) / 2)
+                worst = max(worst, abs(float(mp.mpf(float(angle[i])) - want)))
+                assert abs(float(mp.mpf(float(angle[i])) - want)) <= 4.0 * np.spacing(np.pi), (k, i)
+        if k == len(TW.LADDER) - 1:
+            assert (np.linalg.norm(e_o, axis=1) < 3.0 * TW.FK_ENTRY).all() and (np.abs(angle - np.pi) <= TW.E_ANGLE).all()
+    print(f"the reference's angle against mpmath: {worst:.3e}")
+
+
+def test_step_tolerance_takes_e_o_per_row():
+    """step_tolerance with the default is what it was; with e_o per row it is linear in it."""
+    block = JW.blocks_of("custom/custom")[0]
+    n = 16
+    q = TW.starts(n)
+    R, p = (g[0, :n] for g in TW.side_goals("custom/custom", 1)[0])
+    s = TW.one_step(block, q, R, p, 0.05)
+    t = W.tolerances(s["J"], s["v"], 0.05, None)
+    base = TW.DT * (t["tol_row"] + t["g"] * (TW.KP * TW.E_P + TW.KO * TW.E_O)) + 4.0 * TW.EPS * np.linalg.norm(q, axis=1)
+    assert np.array_equal(TW.step_tolerance(s, q, 0.05), base)
+    e_o = np.linspace(1.0, 2.0, n) * TW.E_O
+    assert np.allclose(TW.step_tolerance(s, q, 0.05, e_o=e_o) - base, TW.DT * t["g"] * TW.KO * (e_o - TW.E_O), rtol=1e-12, atol=0.0)
+
+
+# ------------------------------------------------------------------------------------------ finite values that overflow
+@pytest.mark.parametrize("lam", TW.LAMBDAS)
+def test_which_far_rungs_overflow_in_the_reference(lam):
+    """The far rungs of the GPU test on the reference alone (custom/custom, the far rows, step 1 from the reference's own step 0):
+    the rates are not finite exactly on track_workload.FAR_HELD, with lstsq and with the float64 restatement of the device's
+    algorithm alike; such a row is held like a skipped one (joints kept, rates 0, err NaN) instead of NaN joints; on the other rungs
+    the step is taken, with limits every |rate_k| <= rate_max_k (1 + 2^-52), and err[0] is +infinity from |e_p| = 1.3e154 on."""
+    pair, n = "custom/custom", TW.N_FAR
+    arm = JW.arm_bytes()[:n]
+    rows = list(TW.FAR_ROWS)
+    R, p = TW.goals_of(pair, TW.T_FAR, arm)
+    clean = dict(R=R, p=p, m12=TW.m12_of(R, p), ff=np.ascontiguousarray(TW.feedforwards(TW.T_FAR)[:, :n]))
+    q1 = TW.step_by_arm(pair, arm[rows], TW.starts()[rows], R[0][rows], p[0][rows], lam, ff=clean["ff"][0][rows], limits=TW.LIMITS)["joints"]
+    for kind, value in TW.FAR_RUNGS:
+        d = TW.far_inputs(clean, kind, value)
+        assert np.array_equal(np.flatnonzero((d["m12"] != clean["m12"]).any(axis=(0, 1)) | (d["ff"] != clean["ff"]).any(axis=(0, 2))), rows)
+        assert np.array_equal(TW.m12_of(d["R"], d["p"]), d["m12"])
+        for solver in ("lstsq", "restatement"):
+            s = TW.step_by_arm(pair, arm[rows], q1, d["R"][1][rows], d["p"][1][rows], lam, ff=d["ff"][1][rows], limits=TW.LIMITS, solver=solver)
+            held = (kind, value) in TW.FAR_HELD
+            assert (s["overflow"] == held).all(), (kind, value, solver, s["overflow"].tolist())
+            if held:
+                assert np.array_equal(s["joints"], q1) and (s["rates"] == 0.0).all() and np.isnan(s["err"]).all(), (kind, value, solver)
+            else:
+                assert np.isfinite(s["rates"]).all() and (np.abs(s["rates"]) <= TW.LIMITS[0] * (1 + 2.0 ** -52)).all(), (kind, value, solver)
+                far = kind == "goal" and value >= TW.EP2_OVERFLOWS
+                assert (np.isposinf(s["err"][:, 0]) if far else np.isfinite(s["err"][:, 0])).all(), (kind, value, solver, s["err"].tolist())
