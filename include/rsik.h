@@ -1005,6 +1005,58 @@ int rsik_clearance(rsik_ctx *ctx, int64_t n, int64_t n_rep, const double *joints
                    double *clearance, int32_t *nearest, double *gradient, double *witness, double *link_points);
 
 /*
+ * rsik_track_avoid — rsik_track with obstacle avoidance inside the loop: at every step the clearance of the joints the loop has
+ * reached against a static set of obstacles (what rsik_clearance computes), and, where it is below an influence distance, its joint
+ * gradient as a push in the bias of the damped least-squares rates — the null-space avoidance that rsik_clearance's gradient is for,
+ * at the joints that exist only inside the launch (added within ABI version 8: one symbol, no option, no workspace).  The reference
+ * has nothing of the kind.
+ *
+ * Every argument rsik_track has means what it means there: the layouts, the rules for damping, rest_joints and limits_host, what is
+ * not a number, skipped and held steps, the refusals.  The new ones:
+ *   link_radius_host, n_spheres, spheres, n_capsules, capsules   exactly as rsik_clearance, with smaller counts: 0 ... 256 spheres and
+ *                    0 ... 64 capsules, at least one obstacle in all (without obstacles the call to make is rsik_track); anything
+ *                    else is RSIK_E_INVALID.  The obstacles are static: shared by every trajectory and every step.  A row with a
+ *                    NaN, an infinity or a negative radius is skipped, as there.
+ *   influence        finite, >= 0, in m: the push acts where the clearance is below it
+ *   avoid_gain       finite, >= 0: rad/s of bias per metre of (influence - clearance) and unit of gradient
+ *   clearance_steps  [n_steps][n] or NULL: the clearance every step saw, before it moved
+ *   nearest_steps    [n_steps][n][2] int32 or NULL, aligned to 8 bytes: (link, obstacle index) of that clearance
+ *   min_clearance    [n] or NULL: the minimum of clearance_steps[0 ... n_steps - 1] and of the clearance at the final joints; +infinity
+ *                    if every obstacle is skipped
+ * Definition, per trajectory and step: steps 1-3 and 5-8 are rsik_track's, word for word; step 4 is
+ *   4a. (d, link, obstacle, g) = clearance, nearest and gradient as rsik_clearance defines them for the current q (pair order, first
+ *       minimum, skipped obstacles: the same).  clearance_steps[t] = d, nearest_steps[t] = (link, obstacle).  They depend on q alone
+ *       and are written on a skipped or held step too, with the held q.
+ *   4b. q0 = rest_gain (rest_joints - q), or 0 without rest_joints.  Where d < influence: a = avoid_gain (influence - d) and
+ *       q0_k := q0_k + a g_k (a product, then a sum).  Where d >= influence, or no obstacle is usable (d = +infinity), q0 is left
+ *       alone: a select, not a multiplication by zero.
+ * Step 5 is rsik_joint_rates' rates for (q, v, lambda, q0), as before.  The push is a bias, not a constraint: the damped solve weighs
+ * it against the twist with lambda^2, so it moves the arm in the null space of the task first and gives way to the task elsewhere.
+ * min_clearance costs one more pass over the obstacles, after the last step, and only when it is asked for.
+ * Any output may be NULL, all eight NULL is RSIK_E_INVALID.  Beyond what rsik_track states of its outputs (any subset, n, the
+ * neighbours, two launches: the same bits): clearance_steps[t] and nearest_steps[t] are bit for bit what rsik_clearance returns for
+ * the joints before step t (start_joints, then joints_steps[t - 1]) with the same obstacles and radii, and a trajectory on which the
+ * push never acts has rsik_track's bits in the five outputs the two share (where neither a rest posture nor a push is there the
+ * bias is left out of the solve, as rsik_track leaves it out; the sign of a zero is the one place where the two could ever differ).
+ * A trajectory that is NaN (start_joints, rest_joints, damping) is NaN in every double output and (-1, -1) in nearest_steps.
+ * n == 0 launches nothing; the refusals of rsik_track, a count outside its range, no obstacle, a NULL obstacle array with a count
+ * above 0, an influence, avoid_gain or link radius that is negative or not finite, a nearest_steps that is not aligned give
+ * RSIK_E_INVALID; the arm checks and their codes are rsik_jacobian's (RSIK_E_NOT_SET included).  Enqueued on the context's stream;
+ * allocates nothing and never waits for the device.
+ */
+int rsik_track_avoid(rsik_ctx *ctx, int64_t n, int64_t n_steps, const double *m12_steps,
+                     const uint8_t *arm, int arm_uniform, const double *start_joints,
+                     double dt, double kp, double ko, const double *feedforward_steps,
+                     double damping_host, const double *damping,
+                     const double *rest_joints, double rest_gain, const double *limits_host,
+                     const double *link_radius_host,
+                     int n_spheres, const double *spheres, int n_capsules, const double *capsules,
+                     double influence, double avoid_gain,
+                     double *joints_steps, double *rates_steps, double *err_steps,
+                     double *clearance_steps, int32_t *nearest_steps,
+                     double *final_joints, double *final_err, double *min_clearance);
+
+/*
  * Multi-GPU.  Poses are independent, so a job is sharded across the GPUs of a node — one process and one
  * rsik context per GPU — with no data-path collective; the only exchange is the all-gather of the final arrays
  * (joints [n,7], state [n]) over RCCL / xGMI.  The reference has nothing distributed (single-threaded Python).  Python

@@ -1015,6 +1015,110 @@ class HipSolver:
                  damping_host, _ptr(damping), _ptr(rest_joints), rest_gain, lim_p) + tuple(_ptr(res.get(name)) for name in self.TRACK_OUTPUTS)
         return self._finish(res, "rsik_track", cargs, plan_only, (m12_steps, start_joints, feedforward, damping, rest_joints, arm, lim))
 
+    # ------------------------------------------------------------------ rsik_track_avoid
+    TRACK_AVOID_OUTPUTS = ("joints", "rates", "err", "clearance", "nearest", "final_joints", "final_err", "min_clearance")
+    TRACK_AVOID_MAX_SPHERES, TRACK_AVOID_MAX_CAPSULES = 256, 64
+
+    def track_avoid(
+        self,
+        m12_steps: torch.Tensor,
+        start_joints: torch.Tensor,
+        dt: float,
+        kp: float,
+        ko: float,
+        damping: Any = None,
+        spheres: Optional[torch.Tensor] = None,
+        capsules: Optional[torch.Tensor] = None,
+        link_radius: Any = None,
+        influence: float = 0.0,
+        avoid_gain: float = 0.0,
+        feedforward: Optional[torch.Tensor] = None,
+        rest_joints: Optional[torch.Tensor] = None,
+        rest_gain: float = 0.0,
+        limits: Any = None,
+        arm: Optional[torch.Tensor] = None,
+        arm_uniform: int = 0,
+        want: Sequence[str] = ("joints",),
+        out: Optional[Dict[str, torch.Tensor]] = None,
+        plan_only: bool = False,
+    ) -> Dict[str, torch.Tensor]:
+        """track() with obstacle avoidance inside the loop, every step in one launch (rsik_track_avoid).  Every argument of track()
+        means what it means there; spheres [S, 4], capsules [Cp, 7] and link_radius are clearance()'s, static and shared by every
+        trajectory and step, with S <= 256, Cp <= 64 and at least one obstacle (without obstacles: track()).
+        Per step, (d, nearest, g) = clearance, nearest and gradient of clearance() at the current joints; the bias is
+        q0 = rest_gain (rest_joints - q), and where d < influence (m, >= 0) q0 += avoid_gain (influence - d) g; the rates are
+        joint_rates(q, v, lambda, q0) as in track().  The push is a bias: it acts in the null space of the task first.
+        `want`: which of TRACK_AVOID_OUTPUTS to compute, at least one; the bits of one do not depend on the others.  Beside track()'s
+        five: clearance [T, n] and nearest [T, n, 2] int32 (link, obstacle index) that each step saw before it moved, bit for bit
+        clearance()'s at those joints, and min_clearance [n], the minimum of clearance over the steps and at the final joints.
+        A trajectory the push never acts on has track()'s bits.
+        plan_only=True launches nothing and adds res["launch"], a zero-overhead re-launch callable (see plan())."""
+        if not isinstance(m12_steps, torch.Tensor):
+            m12_steps = torch.as_tensor(np.asarray(m12_steps, dtype=np.float64))
+        if m12_steps.dim() != 3 or m12_steps.shape[1] != 12:
+            raise ValueError("m12_steps must have shape [n_steps, 12, n]")
+        n_steps, n = int(m12_steps.shape[0]), int(m12_steps.shape[2])
+        if not 1 <= n_steps <= 65536:
+            raise ValueError("m12_steps: between 1 and 65536 steps")
+        want = tuple(want)
+        if not want or any(name not in self.TRACK_AVOID_OUTPUTS for name in want):
+            raise ValueError(f"want must name at least one of {self.TRACK_AVOID_OUTPUTS}")
+        if damping is None:
+            raise ValueError("damping: a float > 0 or a tensor with one lambda per trajectory")
+        dt, kp, ko, rest_gain, influence, avoid_gain = float(dt), float(kp), float(ko), float(rest_gain), float(influence), float(avoid_gain)
+        if not (np.isfinite(dt) and dt > 0.0):
+            raise ValueError("dt must be finite and > 0")
+        for name, gain in (("kp", kp), ("ko", ko), ("rest_gain", rest_gain), ("influence", influence), ("avoid_gain", avoid_gain)):
+            if not (np.isfinite(gain) and gain >= 0.0):
+                raise ValueError(f"{name} must be finite and >= 0")
+
+        def rows(t, width, most, name):
+            if t is None:
+                return None, 0
+            if not isinstance(t, torch.Tensor):
+                t = torch.as_tensor(np.asarray(t, dtype=np.float64))
+            if t.dim() != 2 or t.shape[1] != width or t.shape[0] > most:
+                raise ValueError(f"{name} must have shape [k, {width}] with k <= {most}")
+            count = int(t.shape[0])
+            return (self._dev_f64(t, (count, width), name) if count else None), count
+
+        spheres, n_spheres = rows(spheres, 4, self.TRACK_AVOID_MAX_SPHERES, "spheres")
+        capsules, n_capsules = rows(capsules, 7, self.TRACK_AVOID_MAX_CAPSULES, "capsules")
+        if n_spheres + n_capsules < 1:
+            raise ValueError("at least one obstacle: spheres [k, 4] or capsules [k, 7] (without obstacles: track())")
+        rad, rad_p = None, None
+        if link_radius is not None:
+            rad = np.ascontiguousarray(link_radius.cpu().numpy() if isinstance(link_radius, torch.Tensor) else link_radius, dtype=np.float64)
+            if rad.shape != (3,) or not np.isfinite(rad).all() or not (rad >= 0.0).all():
+                raise ValueError("link_radius must be 3 finite values >= 0")
+            rad_p = rad.ctypes.data_as(C.POINTER(C.c_double))
+        m12_steps = self._dev_f64(m12_steps, (n_steps, 12, n), "m12_steps")
+        start_joints = self._dev_f64(start_joints, (n, 7), "start_joints")
+        feedforward = None if feedforward is None else self._dev_f64(feedforward, (n_steps, n, 6), "feedforward")
+        rest_joints = None if rest_joints is None else self._dev_f64(rest_joints, (n, 7), "rest_joints")
+        if isinstance(damping, (int, float)):
+            damping_host, damping = float(damping), None
+            if not (np.isfinite(damping_host) and damping_host > 0.0):
+                raise ValueError("damping must be finite and > 0")
+        else:
+            damping_host, damping = 0.0, self._dev_f64(damping, (n,), "damping")
+        lim, lim_p = None, None
+        if limits is not None:
+            lim = np.ascontiguousarray(limits.cpu().numpy() if isinstance(limits, torch.Tensor) else limits, dtype=np.float64)
+            if lim.shape != (3, 7) or np.isnan(lim).any() or not (lim[0] > 0.0).all() or not (lim[1] <= lim[2]).all():
+                raise ValueError("limits must be [3, 7]: rate_max > 0, q_min <= q_max, no NaN")
+            lim_p = lim.ctypes.data_as(C.POINTER(C.c_double))
+        arm = self._arm_ids(arm, n)
+        shapes = {"joints": (n_steps, n, 7), "rates": (n_steps, n, 7), "err": (n_steps, n, 2), "clearance": (n_steps, n),
+                  "nearest": (n_steps, n, 2), "final_joints": (n, 7), "final_err": (n, 2), "min_clearance": (n,)}
+        res = {name: self._out_buf(out, name, shapes[name], torch.int32 if name == "nearest" else _F64)
+               for name in self.TRACK_AVOID_OUTPUTS if name in want}
+        cargs = (n, n_steps, _ptr(m12_steps), _ptr(arm), int(arm_uniform), _ptr(start_joints), dt, kp, ko, _ptr(feedforward),
+                 damping_host, _ptr(damping), _ptr(rest_joints), rest_gain, lim_p, rad_p, n_spheres, _ptr(spheres), n_capsules,
+                 _ptr(capsules), influence, avoid_gain) + tuple(_ptr(res.get(name)) for name in self.TRACK_AVOID_OUTPUTS)
+        return self._finish(res, "rsik_track_avoid", cargs, plan_only,
+                            (m12_steps, start_joints, feedforward, damping, rest_joints, arm, lim, spheres, capsules, rad))
+
     # ------------------------------------------------------------------ rsik_clearance
     CLEARANCE_OUTPUTS = ("clearance", "nearest", "gradient", "witness", "link_points")
     CLEARANCE_MAX_SPHERES, CLEARANCE_MAX_CAPSULES = 4096, 256

@@ -43,6 +43,7 @@
 #include "rsik_kernel_joint_rates.hpp"
 #include "rsik_kernel_track.hpp"
 #include "rsik_kernel_clearance.hpp"
+#include "rsik_kernel_track_avoid.hpp"
 
 // =====================================================================================
 // C ABI
@@ -1100,6 +1101,62 @@ int rsik_track(rsik_ctx* ctx, int64_t n, int64_t n_steps, const double* m12_step
             with_bool(rest_joints != nullptr, [&](auto REST) { with_bool(limits_host != nullptr, [&](auto LIM) {
                 constexpr int OUTS = (WJ() ? rsik::kTrackJoints : 0) | (WR() ? rsik::kTrackRates : 0) | (WE() ? rsik::kTrackErr : 0);
                 hipLaunchKernelGGL((rsik::track_kernel<MIXED(), OUTS, FF(), REST(), LIM()>), grid, block, 0, ctx->stream, K); }); }); }); }); }); }); });
+    return launch_end(ctx);
+}
+
+int rsik_track_avoid(rsik_ctx* ctx, int64_t n, int64_t n_steps, const double* m12_steps, const uint8_t* arm, int arm_uniform,
+                     const double* start_joints, double dt, double kp, double ko, const double* feedforward_steps, double damping_host,
+                     const double* damping, const double* rest_joints, double rest_gain, const double* limits_host,
+                     const double* link_radius_host, int n_spheres, const double* spheres, int n_capsules, const double* capsules,
+                     double influence, double avoid_gain, double* joints_steps, double* rates_steps, double* err_steps,
+                     double* clearance_steps, int32_t* nearest_steps, double* final_joints, double* final_err, double* min_clearance) {
+    if (!ctx) return RSIK_E_INVALID;
+    const char* who = "rsik_track_avoid";
+    const auto gain_ok = [](double g) { return std::isfinite(g) && g >= 0.0; };
+    if (n < 0) return fail(ctx, RSIK_E_INVALID, "rsik_track_avoid: n < 0");
+    if (n_steps < 1 || n_steps > 65536) return fail(ctx, RSIK_E_INVALID, "rsik_track_avoid: n_steps must be 1 ... 65536");
+    if (n_spheres < 0 || n_spheres > rsik::kAvoidMaxSpheres) return fail(ctx, RSIK_E_INVALID, "rsik_track_avoid: n_spheres must be 0 ... 256");
+    if (n_capsules < 0 || n_capsules > rsik::kAvoidMaxCapsules) return fail(ctx, RSIK_E_INVALID, "rsik_track_avoid: n_capsules must be 0 ... 64");
+    if (n_spheres + n_capsules < 1) return fail(ctx, RSIK_E_INVALID, "rsik_track_avoid: at least one obstacle (without obstacles: rsik_track)");
+    for (int l = 0; link_radius_host && l < 3; l++)
+        if (!gain_ok(link_radius_host[l])) return fail(ctx, RSIK_E_INVALID, "rsik_track_avoid: every link radius must be finite and >= 0");
+    if (!gain_ok(influence) || !gain_ok(avoid_gain))
+        return fail(ctx, RSIK_E_INVALID, "rsik_track_avoid: influence and avoid_gain must be finite and >= 0");
+    if (n == 0) return RSIK_OK;
+    if (!m12_steps || !start_joints) return fail(ctx, RSIK_E_INVALID, "rsik_track_avoid: m12_steps or start_joints is NULL");
+    if (!joints_steps && !rates_steps && !err_steps && !clearance_steps && !nearest_steps && !final_joints && !final_err && !min_clearance)
+        return fail(ctx, RSIK_E_INVALID, "rsik_track_avoid: all eight outputs are NULL");
+    if ((n_spheres > 0 && !spheres) || (n_capsules > 0 && !capsules))
+        return fail(ctx, RSIK_E_INVALID, "rsik_track_avoid: spheres or capsules is NULL with a count above 0");
+    if (((uintptr_t)nearest_steps & 7) != 0) return fail(ctx, RSIK_E_INVALID, "rsik_track_avoid: nearest_steps must be aligned to 8 bytes");
+    if (!(std::isfinite(dt) && dt > 0.0)) return fail(ctx, RSIK_E_INVALID, "rsik_track_avoid: dt must be finite and > 0");
+    if (!gain_ok(kp) || !gain_ok(ko)) return fail(ctx, RSIK_E_INVALID, "rsik_track_avoid: kp and ko must be finite and >= 0");
+    if (rest_joints && !gain_ok(rest_gain)) return fail(ctx, RSIK_E_INVALID, "rsik_track_avoid: rest_gain must be finite and >= 0");
+    if (!damping && !rsik::damping_usable(damping_host))
+        return fail(ctx, RSIK_E_INVALID, "rsik_track_avoid: damping_host must be finite and > 0 (its square a normal double)");
+    for (int k = 0; limits_host && k < 7; k++) {
+        const double rate_max = limits_host[k], q_min = limits_host[7 + k], q_max = limits_host[14 + k];
+        if (!(rate_max > 0.0) || !(q_min <= q_max))  // (a NaN fails both)
+            return fail(ctx, RSIK_E_INVALID, "rsik_track_avoid: limits_host needs rate_max > 0 and q_min <= q_max, and no NaN");
+    }
+    int rc = check_arms(ctx, arm, arm_uniform, who);
+    if (rc != RSIK_OK) return rc;
+    rsik::TrackAvoidArgs K;
+    std::memset(&K, 0, sizeof K);
+    K.n = n; K.n_steps = n_steps; K.m12_steps = m12_steps; K.arm = arm; K.start_joints = start_joints;
+    K.feedforward = feedforward_steps; K.damping = damping; K.rest_joints = rest_joints;
+    K.spheres = spheres; K.capsules = capsules; K.n_spheres = n_spheres; K.n_capsules = n_capsules;
+    K.joints_steps = joints_steps; K.rates_steps = rates_steps; K.err_steps = err_steps; K.clearance_steps = clearance_steps;
+    K.nearest_steps = nearest_steps; K.final_joints = final_joints; K.final_err = final_err; K.min_clearance = min_clearance;
+    K.damping_host = damping ? 0.0 : damping_host; K.dt = dt; K.kp = kp; K.ko = ko; K.rest_gain = rest_joints ? rest_gain : 0.0;
+    K.influence = influence; K.avoid_gain = avoid_gain;
+    for (int l = 0; l < 3; l++) K.link_radius[l] = link_radius_host ? link_radius_host[l] : 0.0;
+    if (limits_host) { fill7(K.rate_max, limits_host, 0.0); fill7(K.q_min, limits_host + 7, 0.0); fill7(K.q_max, limits_host + 14, 0.0); }
+    bind_arms(ctx, arm, arm_uniform, K.arms);
+    dim3 grid, block(rsik::kTrackBlock);
+    if ((rc = launch_begin(ctx, n, &grid, who, rsik::kTrackBlock)) != RSIK_OK) return rc;
+    with_bool(arm != nullptr, [&](auto MIXED) { with_bool(feedforward_steps != nullptr, [&](auto FF) { with_bool(limits_host != nullptr, [&](auto LIM) {
+        hipLaunchKernelGGL((rsik::track_avoid_kernel<MIXED(), FF(), LIM()>), grid, block, 0, ctx->stream, K); }); }); });
     return launch_end(ctx);
 }
 

@@ -495,6 +495,21 @@ class SymbolicIK:
         return _track_batch(self, {"arm_uniform": self.arm_id}, goals, start_joints, dt, kp, ko, damping, feedforward, rest_joints,
                             rest_gain, limits, want, out, plan_only)
 
+    def track_avoid_batch(self, goals: Any, start_joints: Any, dt: float, kp: float, ko: float, damping: Any, spheres: Any = None,
+                          capsules: Any = None, link_radius: Any = None, influence: float = 0.0, avoid_gain: float = 0.0,
+                          feedforward: Any = None, rest_joints: Any = None, rest_gain: float = 0.0, limits: Any = None,
+                          want: Sequence[str] = ("joints",), out: Optional[Dict[str, torch.Tensor]] = None,
+                          plan_only: bool = False) -> Dict[str, torch.Tensor]:
+        """track_batch with obstacle avoidance inside the loop, every step in one launch (HipSolver.track_avoid, rsik_track_avoid).
+        goals, start_joints, dt, kp, ko, damping, feedforward, rest_joints, rest_gain and limits are track_batch's; spheres [S,4]
+        (S <= 256), capsules [Cp,7] (Cp <= 64) and link_radius are clearance_batch's, static, at least one in all.  Per step the
+        clearance d of the current joints and its gradient g are clearance_batch's, and where d < influence the bias of the rates
+        gains avoid_gain (influence - d) g: the arm moves away in the null space of the task.  Returns the outputs named in want, of
+        HipSolver.TRACK_AVOID_OUTPUTS: track_batch's five, clearance [T,n] and nearest [T,n,2] int32 (what each step saw before it
+        moved) and min_clearance [n] (over the steps and at the final joints)."""
+        return _track_avoid_batch(self, {"arm_uniform": self.arm_id}, goals, start_joints, dt, kp, ko, damping, spheres, capsules,
+                                  link_radius, influence, avoid_gain, feedforward, rest_joints, rest_gain, limits, want, out, plan_only)
+
     def clearance_batch(self, joints: Any, spheres: Any = None, capsules: Any = None, link_radius: Any = None,
                         want: Sequence[str] = ("clearance", "nearest"), out: Optional[Dict[str, torch.Tensor]] = None,
                         plan_only: bool = False) -> Dict[str, torch.Tensor]:
@@ -621,6 +636,19 @@ def _track_batch(ik, arm, goals, start_joints, dt, kp, ko, damping, feedforward,
                             rest_gain=rest_gain, limits=limits, want=want, out=out, plan_only=plan_only, **arm)
 
 
+def _track_avoid_batch(ik, arm, goals, start_joints, dt, kp, ko, damping, spheres, capsules, link_radius, influence, avoid_gain,
+                       feedforward, rest_joints, rest_gain, limits, want, out, plan_only):
+    g = goals if isinstance(goals, torch.Tensor) else torch.as_tensor(np.asarray(goals, dtype=np.float64))
+    g = g.to(device=ik._solver.device, dtype=torch.float64)
+    if g.dim() == 4 and tuple(g.shape[2:]) == (4, 4):  # [T,n,4,4] -> [T,12,n]
+        g = torch.cat([g[..., :3, :3].reshape(g.shape[0], g.shape[1], 9), g[..., :3, 3]], dim=2).permute(0, 2, 1).contiguous()
+    ik._upload()
+    return ik._solver.track_avoid(g, start_joints, dt, kp, ko, damping=damping, spheres=spheres, capsules=capsules,
+                                  link_radius=link_radius, influence=influence, avoid_gain=avoid_gain, feedforward=feedforward,
+                                  rest_joints=rest_joints, rest_gain=rest_gain, limits=limits, want=want, out=out, plan_only=plan_only,
+                                  **arm)
+
+
 def _clearance_batch(ik, arm, joints, spheres, capsules, link_radius, want, out, plan_only):
     ik._upload()
     return ik._solver.clearance(joints, spheres=spheres, capsules=capsules, link_radius=link_radius, want=want, out=out,
@@ -732,6 +760,17 @@ class DualArmIK:
         final_err [n,2], as named in want."""
         return _track_batch(self, {"arm": arm_ids}, goals, start_joints, dt, kp, ko, damping, feedforward, rest_joints, rest_gain,
                             limits, want, out, plan_only)
+
+    def track_avoid_batch(self, arm_ids: Any, goals: Any, start_joints: Any, dt: float, kp: float, ko: float, damping: Any,
+                          spheres: Any = None, capsules: Any = None, link_radius: Any = None, influence: float = 0.0,
+                          avoid_gain: float = 0.0, feedforward: Any = None, rest_joints: Any = None, rest_gain: float = 0.0,
+                          limits: Any = None, want: Sequence[str] = ("joints",), out: Optional[Dict[str, torch.Tensor]] = None,
+                          plan_only: bool = False) -> Dict[str, torch.Tensor]:
+        """SymbolicIK.track_avoid_batch for trajectories of both arms (arm_ids [n] uint8, one byte per trajectory): track_batch with
+        the static obstacles spheres [S,4] and capsules [Cp,7] of clearance_batch pushed away from inside the loop (the bias gains
+        avoid_gain (influence - clearance) gradient where the clearance is below influence), in one launch: track_batch's outputs, clearance [T,n], nearest [T,n,2] int32 and min_clearance [n], as named in want."""
+        return _track_avoid_batch(self, {"arm": arm_ids}, goals, start_joints, dt, kp, ko, damping, spheres, capsules, link_radius,
+                                  influence, avoid_gain, feedforward, rest_joints, rest_gain, limits, want, out, plan_only)
 
     def clearance_batch(self, arm_ids: Any, joints: Any, spheres: Any = None, capsules: Any = None, link_radius: Any = None,
                         other_arm: Optional[Tuple[int, Any]] = None, want: Sequence[str] = ("clearance", "nearest"),
