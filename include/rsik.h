@@ -1057,6 +1057,55 @@ int rsik_track_avoid(rsik_ctx *ctx, int64_t n, int64_t n_steps, const double *m1
                      double *final_joints, double *final_err, double *min_clearance);
 
 /*
+ * rsik_track_pair — rsik_track_avoid for n_pairs robots of two arms that avoid each other: both arms of a robot are tracked in the
+ * same launch, and at every step each arm has, beside the static obstacles, the other arm's three links as capsules, at the joints
+ * the other arm has reached at that step — joints that exist only inside the launch (added within ABI version 8: one symbol, no
+ * option, no workspace).  The reference has nothing of the kind.
+ *
+ * Rows: there are n = 2 n_pairs rows; row 2i is the right arm of robot i (RSIK_ARM_R), row 2i + 1 its left arm (RSIK_ARM_L).  Every
+ * array has exactly rsik_track_avoid's layout for n rows (m12_steps [n_steps][12][n], start_joints [n][7], feedforward_steps
+ * [n_steps][n][6], damping [n], rest_joints [n][7], the eight outputs), so one set of buffers can feed rsik_track_avoid with the arm
+ * bytes 0, 1, 0, 1, ... and then this call.  There is no arm argument; both arms' constants must be set (rsik_set_arm), otherwise
+ * RSIK_E_NOT_SET.  Both arms live in the torso frame, as their RSIK_C_SHOULDER constants say.  Every other argument means what it
+ * means in rsik_track_avoid, with one difference:
+ *   n_spheres, spheres, n_capsules, capsules   0 ... 256 spheres and 0 ... 64 capsules; NO static obstacle is allowed here, because the
+ *                    partner is always an obstacle
+ * Definition, per row and step: steps 1-3 and 5-8 are rsik_track's, word for word; step 4b is rsik_track_avoid's, word for word;
+ * step 4a is rsik_clearance's minimum, nearest pair and gradient over a longer list of obstacles:
+ *     the spheres, indices 0 ... n_spheres - 1; the capsules, indices n_spheres ... n_spheres + n_capsules - 1; then the partner's
+ *     three links as capsules, indices n_spheres + n_capsules + l for l = 0, 1, 2.
+ *   The partner's link l is the capsule (P_l, P_{l+1}, link_radius_host[l]), P the partner's link_points as rsik_clearance returns
+ *   them for the partner's joints BEFORE step t: both arms look at each other's state before the step, so the order of the arms does
+ *   not matter.  Its direction is P_{l+1} - P_l, formed from those two points as a capsule's is from its row.  Pair order and "first
+ *   minimum wins" are unchanged, the partner's links come last.  The gradient is with respect to the row's own joints only: the
+ *   partner counts as standing still during the step.
+ * clearance_steps[t] and nearest_steps[t] are therefore bit for bit what rsik_clearance returns for the row's joints before step t
+ * with the static spheres, and the static capsules followed by those three, as its obstacles; on a held step of the partner they
+ * see the held partner.  min_clearance includes the partner at the final joints.
+ * A partner that is not numbers (a NaN or an infinity in its start_joints or rest_joints row, an unusable damping) is NaN in its own
+ * outputs, as in rsik_track_avoid, and its three capsules are skipped exactly like an obstacle row that holds a NaN: never the
+ * nearest, and they change nothing else.  The live arm then has rsik_track_avoid's bits for the same static scene; without a static
+ * scene its clearance is +infinity, its nearest (-1, -1), and the five outputs it shares with rsik_track have rsik_track's bits.
+ * Any output may be NULL, all eight NULL is RSIK_E_INVALID.  Any subset of the outputs gives the same bits, two launches give the
+ * same bits, and a pair's bits depend neither on n_pairs, nor on its place in the launch, nor on the other pairs.
+ * n_pairs == 0 launches nothing; n_pairs < 0 is RSIK_E_INVALID, and so is everything rsik_track_avoid refuses apart from "no
+ * obstacle": n_steps outside 1 ... 65536, a count outside its range, m12_steps == NULL, start_joints == NULL, a NULL obstacle array
+ * with a count above 0, a dt, gain, damping_host, limit, influence, avoid_gain or link radius outside its range, a nearest_steps that
+ * is not aligned to 8 bytes.  Enqueued on the context's stream; allocates nothing and never waits for the device.
+ */
+int rsik_track_pair(rsik_ctx *ctx, int64_t n_pairs, int64_t n_steps, const double *m12_steps,
+                    const double *start_joints,
+                    double dt, double kp, double ko, const double *feedforward_steps,
+                    double damping_host, const double *damping,
+                    const double *rest_joints, double rest_gain, const double *limits_host,
+                    const double *link_radius_host,
+                    int n_spheres, const double *spheres, int n_capsules, const double *capsules,
+                    double influence, double avoid_gain,
+                    double *joints_steps, double *rates_steps, double *err_steps,
+                    double *clearance_steps, int32_t *nearest_steps,
+                    double *final_joints, double *final_err, double *min_clearance);
+
+/*
  * Multi-GPU.  Poses are independent, so a job is sharded across the GPUs of a node — one process and one
  * rsik context per GPU — with no data-path collective; the only exchange is the all-gather of the final arrays
  * (joints [n,7], state [n]) over RCCL / xGMI.  The reference has nothing distributed (single-threaded Python).  Python

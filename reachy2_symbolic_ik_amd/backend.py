@@ -1053,6 +1053,14 @@ class HipSolver:
         clearance()'s at those joints, and min_clearance [n], the minimum of clearance over the steps and at the final joints.
         A trajectory the push never acts on has track()'s bits.
         plan_only=True launches nothing and adds res["launch"], a zero-overhead re-launch callable (see plan())."""
+        return self._track_avoid("rsik_track_avoid", m12_steps, start_joints, dt, kp, ko, damping, spheres, capsules, link_radius, influence,
+                                 avoid_gain, feedforward, rest_joints, rest_gain, limits, arm, arm_uniform, want, out, plan_only)
+
+    def _track_avoid(self, symbol, m12_steps, start_joints, dt, kp, ko, damping, spheres, capsules, link_radius, influence, avoid_gain,
+                     feedforward, rest_joints, rest_gain, limits, arm, arm_uniform, want, out, plan_only):
+        """What track_avoid() and track_pair() share: the checks, the buffers and the call.  rsik_track_pair takes no arm arguments,
+        an even number of rows, and no static obstacle is allowed."""
+        pairs = symbol == "rsik_track_pair"
         if not isinstance(m12_steps, torch.Tensor):
             m12_steps = torch.as_tensor(np.asarray(m12_steps, dtype=np.float64))
         if m12_steps.dim() != 3 or m12_steps.shape[1] != 12:
@@ -1060,6 +1068,8 @@ class HipSolver:
         n_steps, n = int(m12_steps.shape[0]), int(m12_steps.shape[2])
         if not 1 <= n_steps <= 65536:
             raise ValueError("m12_steps: between 1 and 65536 steps")
+        if pairs and n % 2:
+            raise ValueError("m12_steps: an even number of rows, the right arm of robot i in row 2 i and its left arm in row 2 i + 1")
         want = tuple(want)
         if not want or any(name not in self.TRACK_AVOID_OUTPUTS for name in want):
             raise ValueError(f"want must name at least one of {self.TRACK_AVOID_OUTPUTS}")
@@ -1084,7 +1094,7 @@ class HipSolver:
 
         spheres, n_spheres = rows(spheres, 4, self.TRACK_AVOID_MAX_SPHERES, "spheres")
         capsules, n_capsules = rows(capsules, 7, self.TRACK_AVOID_MAX_CAPSULES, "capsules")
-        if n_spheres + n_capsules < 1:
+        if not pairs and n_spheres + n_capsules < 1:
             raise ValueError("at least one obstacle: spheres [k, 4] or capsules [k, 7] (without obstacles: track())")
         rad, rad_p = None, None
         if link_radius is not None:
@@ -1108,16 +1118,60 @@ class HipSolver:
             if lim.shape != (3, 7) or np.isnan(lim).any() or not (lim[0] > 0.0).all() or not (lim[1] <= lim[2]).all():
                 raise ValueError("limits must be [3, 7]: rate_max > 0, q_min <= q_max, no NaN")
             lim_p = lim.ctypes.data_as(C.POINTER(C.c_double))
-        arm = self._arm_ids(arm, n)
+        arm = None if pairs else self._arm_ids(arm, n)
         shapes = {"joints": (n_steps, n, 7), "rates": (n_steps, n, 7), "err": (n_steps, n, 2), "clearance": (n_steps, n),
                   "nearest": (n_steps, n, 2), "final_joints": (n, 7), "final_err": (n, 2), "min_clearance": (n,)}
         res = {name: self._out_buf(out, name, shapes[name], torch.int32 if name == "nearest" else _F64)
                for name in self.TRACK_AVOID_OUTPUTS if name in want}
-        cargs = (n, n_steps, _ptr(m12_steps), _ptr(arm), int(arm_uniform), _ptr(start_joints), dt, kp, ko, _ptr(feedforward),
-                 damping_host, _ptr(damping), _ptr(rest_joints), rest_gain, lim_p, rad_p, n_spheres, _ptr(spheres), n_capsules,
-                 _ptr(capsules), influence, avoid_gain) + tuple(_ptr(res.get(name)) for name in self.TRACK_AVOID_OUTPUTS)
-        return self._finish(res, "rsik_track_avoid", cargs, plan_only,
+        rows = (n // 2, n_steps, _ptr(m12_steps)) if pairs else (n, n_steps, _ptr(m12_steps), _ptr(arm), int(arm_uniform))
+        cargs = rows + (_ptr(start_joints), dt, kp, ko, _ptr(feedforward),
+                        damping_host, _ptr(damping), _ptr(rest_joints), rest_gain, lim_p, rad_p, n_spheres, _ptr(spheres), n_capsules,
+                        _ptr(capsules), influence, avoid_gain) + tuple(_ptr(res.get(name)) for name in self.TRACK_AVOID_OUTPUTS)
+        return self._finish(res, symbol, cargs, plan_only,
                             (m12_steps, start_joints, feedforward, damping, rest_joints, arm, lim, spheres, capsules, rad))
+
+    # ------------------------------------------------------------------ rsik_track_pair
+    TRACK_PAIR_OUTPUTS = TRACK_AVOID_OUTPUTS
+
+    def track_pair(
+        self,
+        m12_steps: torch.Tensor,
+        start_joints: torch.Tensor,
+        dt: float,
+        kp: float,
+        ko: float,
+        damping: Any = None,
+        spheres: Optional[torch.Tensor] = None,
+        capsules: Optional[torch.Tensor] = None,
+        link_radius: Any = None,
+        influence: float = 0.0,
+        avoid_gain: float = 0.0,
+        feedforward: Optional[torch.Tensor] = None,
+        rest_joints: Optional[torch.Tensor] = None,
+        rest_gain: float = 0.0,
+        limits: Any = None,
+        want: Sequence[str] = ("joints",),
+        out: Optional[Dict[str, torch.Tensor]] = None,
+        plan_only: bool = False,
+    ) -> Dict[str, torch.Tensor]:
+        """track_avoid() for robots of two arms that avoid each other, every step of both arms in one launch (rsik_track_pair).
+        The n = 2 n_pairs rows of every array are interleaved: row 2 i is the right arm of robot i, row 2 i + 1 its left arm; there
+        is no arm argument, and both arms' constants must be set.  Every other argument means what it means in track_avoid():
+        m12_steps [T, 12, n], start_joints [n, 7], damping a float or [n], feedforward [T, n, 6], rest_joints [n, 7], limits [3, 7],
+        spheres [S, 4] and capsules [Cp, 7] with S <= 256, Cp <= 64 — and here no static obstacle at all is allowed, because the
+        partner is always one.
+        Per step each arm's obstacles are the spheres, the capsules, and then the other arm's three links as capsules (its
+        link_points of clearance() at the joints it has reached, with link_radius), obstacle indices S + Cp + l; both arms look at
+        each other's joints from before the step.  influence, avoid_gain and the push are track_avoid()'s; the gradient is with
+        respect to the row's own joints.
+        `want`: which of TRACK_PAIR_OUTPUTS (= TRACK_AVOID_OUTPUTS) to compute, at least one; the bits of one do not depend on the
+        others: joints, rates [T, n, 7], err [T, n, 2], clearance [T, n], nearest [T, n, 2] int32, final_joints [n, 7], final_err
+        [n, 2], min_clearance [n].  clearance and nearest are bit for bit clearance()'s for the row's joints before the step with
+        the static capsules followed by the partner's three.  An arm that is NaN (start, rest, damping) is NaN in its own outputs and
+        no obstacle for its partner, which then has track_avoid()'s bits for the static scene.
+        plan_only=True launches nothing and adds res["launch"], a zero-overhead re-launch callable (see plan())."""
+        return self._track_avoid("rsik_track_pair", m12_steps, start_joints, dt, kp, ko, damping, spheres, capsules, link_radius, influence,
+                                 avoid_gain, feedforward, rest_joints, rest_gain, limits, None, 0, want, out, plan_only)
 
     # ------------------------------------------------------------------ rsik_clearance
     CLEARANCE_OUTPUTS = ("clearance", "nearest", "gradient", "witness", "link_points")

@@ -44,6 +44,7 @@
 #include "rsik_kernel_track.hpp"
 #include "rsik_kernel_clearance.hpp"
 #include "rsik_kernel_track_avoid.hpp"
+#include "rsik_kernel_track_pair.hpp"
 
 // =====================================================================================
 // C ABI
@@ -1104,44 +1105,52 @@ int rsik_track(rsik_ctx* ctx, int64_t n, int64_t n_steps, const double* m12_step
     return launch_end(ctx);
 }
 
-int rsik_track_avoid(rsik_ctx* ctx, int64_t n, int64_t n_steps, const double* m12_steps, const uint8_t* arm, int arm_uniform,
-                     const double* start_joints, double dt, double kp, double ko, const double* feedforward_steps, double damping_host,
-                     const double* damping, const double* rest_joints, double rest_gain, const double* limits_host,
-                     const double* link_radius_host, int n_spheres, const double* spheres, int n_capsules, const double* capsules,
-                     double influence, double avoid_gain, double* joints_steps, double* rates_steps, double* err_steps,
-                     double* clearance_steps, int32_t* nearest_steps, double* final_joints, double* final_err, double* min_clearance) {
-    if (!ctx) return RSIK_E_INVALID;
-    const char* who = "rsik_track_avoid";
+// What rsik_track_avoid and rsik_track_pair share: the checks on everything but the arms, in the order that is part of the ABI, and the
+// argument block.  `rows` names the count in the messages ("n" or "n_pairs"; n is the number of rows either way); need_obstacle:
+// rsik_track_avoid refuses a call without a static obstacle, rsik_track_pair always has the partner.  *launch is false where the call is
+// valid and there is nothing to launch (n == 0).
+static int check_track_avoid(rsik_ctx* ctx, const std::string& who, const char* rows, bool need_obstacle, int64_t n, int64_t n_steps,
+                             const double* m12_steps, const double* start_joints, double dt, double kp, double ko, double damping_host,
+                             const double* damping, const double* rest_joints, double rest_gain, const double* limits_host,
+                             const double* link_radius_host, int n_spheres, const double* spheres, int n_capsules, const double* capsules,
+                             double influence, double avoid_gain, bool any_output, const int32_t* nearest_steps, bool* launch) {
     const auto gain_ok = [](double g) { return std::isfinite(g) && g >= 0.0; };
-    if (n < 0) return fail(ctx, RSIK_E_INVALID, "rsik_track_avoid: n < 0");
-    if (n_steps < 1 || n_steps > 65536) return fail(ctx, RSIK_E_INVALID, "rsik_track_avoid: n_steps must be 1 ... 65536");
-    if (n_spheres < 0 || n_spheres > rsik::kAvoidMaxSpheres) return fail(ctx, RSIK_E_INVALID, "rsik_track_avoid: n_spheres must be 0 ... 256");
-    if (n_capsules < 0 || n_capsules > rsik::kAvoidMaxCapsules) return fail(ctx, RSIK_E_INVALID, "rsik_track_avoid: n_capsules must be 0 ... 64");
-    if (n_spheres + n_capsules < 1) return fail(ctx, RSIK_E_INVALID, "rsik_track_avoid: at least one obstacle (without obstacles: rsik_track)");
+    *launch = false;
+    if (n < 0) return fail(ctx, RSIK_E_INVALID, who + ": " + rows + " < 0");
+    if (n_steps < 1 || n_steps > 65536) return fail(ctx, RSIK_E_INVALID, who + ": n_steps must be 1 ... 65536");
+    if (n_spheres < 0 || n_spheres > rsik::kAvoidMaxSpheres) return fail(ctx, RSIK_E_INVALID, who + ": n_spheres must be 0 ... 256");
+    if (n_capsules < 0 || n_capsules > rsik::kAvoidMaxCapsules) return fail(ctx, RSIK_E_INVALID, who + ": n_capsules must be 0 ... 64");
+    if (need_obstacle && n_spheres + n_capsules < 1) return fail(ctx, RSIK_E_INVALID, who + ": at least one obstacle (without obstacles: rsik_track)");
     for (int l = 0; link_radius_host && l < 3; l++)
-        if (!gain_ok(link_radius_host[l])) return fail(ctx, RSIK_E_INVALID, "rsik_track_avoid: every link radius must be finite and >= 0");
+        if (!gain_ok(link_radius_host[l])) return fail(ctx, RSIK_E_INVALID, who + ": every link radius must be finite and >= 0");
     if (!gain_ok(influence) || !gain_ok(avoid_gain))
-        return fail(ctx, RSIK_E_INVALID, "rsik_track_avoid: influence and avoid_gain must be finite and >= 0");
+        return fail(ctx, RSIK_E_INVALID, who + ": influence and avoid_gain must be finite and >= 0");
     if (n == 0) return RSIK_OK;
-    if (!m12_steps || !start_joints) return fail(ctx, RSIK_E_INVALID, "rsik_track_avoid: m12_steps or start_joints is NULL");
-    if (!joints_steps && !rates_steps && !err_steps && !clearance_steps && !nearest_steps && !final_joints && !final_err && !min_clearance)
-        return fail(ctx, RSIK_E_INVALID, "rsik_track_avoid: all eight outputs are NULL");
+    if (!m12_steps || !start_joints) return fail(ctx, RSIK_E_INVALID, who + ": m12_steps or start_joints is NULL");
+    if (!any_output) return fail(ctx, RSIK_E_INVALID, who + ": all eight outputs are NULL");
     if ((n_spheres > 0 && !spheres) || (n_capsules > 0 && !capsules))
-        return fail(ctx, RSIK_E_INVALID, "rsik_track_avoid: spheres or capsules is NULL with a count above 0");
-    if (((uintptr_t)nearest_steps & 7) != 0) return fail(ctx, RSIK_E_INVALID, "rsik_track_avoid: nearest_steps must be aligned to 8 bytes");
-    if (!(std::isfinite(dt) && dt > 0.0)) return fail(ctx, RSIK_E_INVALID, "rsik_track_avoid: dt must be finite and > 0");
-    if (!gain_ok(kp) || !gain_ok(ko)) return fail(ctx, RSIK_E_INVALID, "rsik_track_avoid: kp and ko must be finite and >= 0");
-    if (rest_joints && !gain_ok(rest_gain)) return fail(ctx, RSIK_E_INVALID, "rsik_track_avoid: rest_gain must be finite and >= 0");
+        return fail(ctx, RSIK_E_INVALID, who + ": spheres or capsules is NULL with a count above 0");
+    if (((uintptr_t)nearest_steps & 7) != 0) return fail(ctx, RSIK_E_INVALID, who + ": nearest_steps must be aligned to 8 bytes");
+    if (!(std::isfinite(dt) && dt > 0.0)) return fail(ctx, RSIK_E_INVALID, who + ": dt must be finite and > 0");
+    if (!gain_ok(kp) || !gain_ok(ko)) return fail(ctx, RSIK_E_INVALID, who + ": kp and ko must be finite and >= 0");
+    if (rest_joints && !gain_ok(rest_gain)) return fail(ctx, RSIK_E_INVALID, who + ": rest_gain must be finite and >= 0");
     if (!damping && !rsik::damping_usable(damping_host))
-        return fail(ctx, RSIK_E_INVALID, "rsik_track_avoid: damping_host must be finite and > 0 (its square a normal double)");
+        return fail(ctx, RSIK_E_INVALID, who + ": damping_host must be finite and > 0 (its square a normal double)");
     for (int k = 0; limits_host && k < 7; k++) {
         const double rate_max = limits_host[k], q_min = limits_host[7 + k], q_max = limits_host[14 + k];
         if (!(rate_max > 0.0) || !(q_min <= q_max))  // (a NaN fails both)
-            return fail(ctx, RSIK_E_INVALID, "rsik_track_avoid: limits_host needs rate_max > 0 and q_min <= q_max, and no NaN");
+            return fail(ctx, RSIK_E_INVALID, who + ": limits_host needs rate_max > 0 and q_min <= q_max, and no NaN");
     }
-    int rc = check_arms(ctx, arm, arm_uniform, who);
-    if (rc != RSIK_OK) return rc;
-    rsik::TrackAvoidArgs K;
+    *launch = true;
+    return RSIK_OK;
+}
+static void fill_track_avoid(rsik::TrackAvoidArgs& K, int64_t n, int64_t n_steps, const double* m12_steps, const uint8_t* arm,
+                             const double* start_joints, double dt, double kp, double ko, const double* feedforward_steps,
+                             double damping_host, const double* damping, const double* rest_joints, double rest_gain,
+                             const double* limits_host, const double* link_radius_host, int n_spheres, const double* spheres,
+                             int n_capsules, const double* capsules, double influence, double avoid_gain, double* joints_steps,
+                             double* rates_steps, double* err_steps, double* clearance_steps, int32_t* nearest_steps,
+                             double* final_joints, double* final_err, double* min_clearance) {
     std::memset(&K, 0, sizeof K);
     K.n = n; K.n_steps = n_steps; K.m12_steps = m12_steps; K.arm = arm; K.start_joints = start_joints;
     K.feedforward = feedforward_steps; K.damping = damping; K.rest_joints = rest_joints;
@@ -1152,11 +1161,62 @@ int rsik_track_avoid(rsik_ctx* ctx, int64_t n, int64_t n_steps, const double* m1
     K.influence = influence; K.avoid_gain = avoid_gain;
     for (int l = 0; l < 3; l++) K.link_radius[l] = link_radius_host ? link_radius_host[l] : 0.0;
     if (limits_host) { fill7(K.rate_max, limits_host, 0.0); fill7(K.q_min, limits_host + 7, 0.0); fill7(K.q_max, limits_host + 14, 0.0); }
+}
+
+int rsik_track_avoid(rsik_ctx* ctx, int64_t n, int64_t n_steps, const double* m12_steps, const uint8_t* arm, int arm_uniform,
+                     const double* start_joints, double dt, double kp, double ko, const double* feedforward_steps, double damping_host,
+                     const double* damping, const double* rest_joints, double rest_gain, const double* limits_host,
+                     const double* link_radius_host, int n_spheres, const double* spheres, int n_capsules, const double* capsules,
+                     double influence, double avoid_gain, double* joints_steps, double* rates_steps, double* err_steps,
+                     double* clearance_steps, int32_t* nearest_steps, double* final_joints, double* final_err, double* min_clearance) {
+    if (!ctx) return RSIK_E_INVALID;
+    const char* who = "rsik_track_avoid";
+    const bool any_output = joints_steps || rates_steps || err_steps || clearance_steps || nearest_steps || final_joints || final_err || min_clearance;
+    bool launch;
+    int rc = check_track_avoid(ctx, who, "n", true, n, n_steps, m12_steps, start_joints, dt, kp, ko, damping_host, damping, rest_joints,
+                               rest_gain, limits_host, link_radius_host, n_spheres, spheres, n_capsules, capsules, influence,
+                               avoid_gain, any_output, nearest_steps, &launch);
+    if (rc != RSIK_OK || !launch) return rc;
+    if ((rc = check_arms(ctx, arm, arm_uniform, who)) != RSIK_OK) return rc;
+    rsik::TrackAvoidArgs K;
+    fill_track_avoid(K, n, n_steps, m12_steps, arm, start_joints, dt, kp, ko, feedforward_steps, damping_host, damping, rest_joints,
+                     rest_gain, limits_host, link_radius_host, n_spheres, spheres, n_capsules, capsules, influence, avoid_gain,
+                     joints_steps, rates_steps, err_steps, clearance_steps, nearest_steps, final_joints, final_err, min_clearance);
     bind_arms(ctx, arm, arm_uniform, K.arms);
     dim3 grid, block(rsik::kTrackBlock);
     if ((rc = launch_begin(ctx, n, &grid, who, rsik::kTrackBlock)) != RSIK_OK) return rc;
     with_bool(arm != nullptr, [&](auto MIXED) { with_bool(feedforward_steps != nullptr, [&](auto FF) { with_bool(limits_host != nullptr, [&](auto LIM) {
         hipLaunchKernelGGL((rsik::track_avoid_kernel<MIXED(), FF(), LIM()>), grid, block, 0, ctx->stream, K); }); }); });
+    return launch_end(ctx);
+}
+
+int rsik_track_pair(rsik_ctx* ctx, int64_t n_pairs, int64_t n_steps, const double* m12_steps, const double* start_joints, double dt,
+                    double kp, double ko, const double* feedforward_steps, double damping_host, const double* damping,
+                    const double* rest_joints, double rest_gain, const double* limits_host, const double* link_radius_host,
+                    int n_spheres, const double* spheres, int n_capsules, const double* capsules, double influence, double avoid_gain,
+                    double* joints_steps, double* rates_steps, double* err_steps, double* clearance_steps, int32_t* nearest_steps,
+                    double* final_joints, double* final_err, double* min_clearance) {
+    if (!ctx) return RSIK_E_INVALID;
+    const char* who = "rsik_track_pair";
+    if (n_pairs > 0x3fffffffffffffffLL) return fail(ctx, RSIK_E_INVALID, "rsik_track_pair: n too large for one launch");
+    const int64_t n = n_pairs < 0 ? -1 : 2 * n_pairs;  // rows: 2i the right arm of robot i, 2i + 1 its left arm
+    const bool any_output = joints_steps || rates_steps || err_steps || clearance_steps || nearest_steps || final_joints || final_err || min_clearance;
+    bool launch;
+    int rc = check_track_avoid(ctx, who, "n_pairs", false, n, n_steps, m12_steps, start_joints, dt, kp, ko, damping_host, damping,
+                               rest_joints, rest_gain, limits_host, link_radius_host, n_spheres, spheres, n_capsules, capsules,
+                               influence, avoid_gain, any_output, nearest_steps, &launch);
+    if (rc != RSIK_OK || !launch) return rc;
+    if (!ctx->have_arm[RSIK_ARM_R] || !ctx->have_arm[RSIK_ARM_L])
+        return fail(ctx, RSIK_E_NOT_SET, "rsik_track_pair: both arms' constants are needed (rsik_set_arm)");
+    rsik::TrackAvoidArgs K;  // (K.arm stays NULL: the arm of a row is its parity)
+    fill_track_avoid(K, n, n_steps, m12_steps, nullptr, start_joints, dt, kp, ko, feedforward_steps, damping_host, damping, rest_joints,
+                     rest_gain, limits_host, link_radius_host, n_spheres, spheres, n_capsules, capsules, influence, avoid_gain,
+                     joints_steps, rates_steps, err_steps, clearance_steps, nearest_steps, final_joints, final_err, min_clearance);
+    K.arms[0] = ctx->arms[RSIK_ARM_R]; K.arms[1] = ctx->arms[RSIK_ARM_L];
+    dim3 grid, block(rsik::kTrackBlock);
+    if ((rc = launch_begin(ctx, n, &grid, who, rsik::kTrackBlock)) != RSIK_OK) return rc;
+    with_bool(feedforward_steps != nullptr, [&](auto FF) { with_bool(limits_host != nullptr, [&](auto LIM) {
+        hipLaunchKernelGGL((rsik::track_pair_kernel<FF(), LIM()>), grid, block, 0, ctx->stream, K); }); });
     return launch_end(ctx);
 }
 

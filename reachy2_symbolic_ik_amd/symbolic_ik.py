@@ -649,6 +649,25 @@ def _track_avoid_batch(ik, arm, goals, start_joints, dt, kp, ko, damping, sphere
                                   **arm)
 
 
+def _m12_steps(goals, device):
+    """Goals [T,12,n] or matrices [T,n,4,4] -> [T,12,n] float64 on the device."""
+    g = goals if isinstance(goals, torch.Tensor) else torch.as_tensor(np.asarray(goals, dtype=np.float64))
+    g = g.to(device=device, dtype=torch.float64)
+    if g.dim() == 4 and tuple(g.shape[2:]) == (4, 4):
+        g = torch.cat([g[..., :3, :3].reshape(g.shape[0], g.shape[1], 9), g[..., :3, 3]], dim=2).permute(0, 2, 1)
+    return g
+
+
+def _interleave(r, l, dim, device):
+    """Two per-arm arrays -> one with row 2 i from r and row 2 i + 1 from l along `dim`."""
+    r, l = ((t if isinstance(t, torch.Tensor) else torch.as_tensor(np.asarray(t, dtype=np.float64))).to(device=device, dtype=torch.float64)
+            for t in (r, l))
+    if r.shape != l.shape:
+        raise ValueError("the right and the left arm's arrays must have the same shape")
+    dim = dim % r.dim()
+    return torch.stack([r, l], dim=dim + 1).reshape(r.shape[:dim] + (2 * r.shape[dim],) + r.shape[dim + 1:]).contiguous()
+
+
 def _clearance_batch(ik, arm, joints, spheres, capsules, link_radius, want, out, plan_only):
     ik._upload()
     return ik._solver.clearance(joints, spheres=spheres, capsules=capsules, link_radius=link_radius, want=want, out=out,
@@ -771,6 +790,49 @@ class DualArmIK:
         avoid_gain (influence - clearance) gradient where the clearance is below influence), in one launch: track_batch's outputs, clearance [T,n], nearest [T,n,2] int32 and min_clearance [n], as named in want."""
         return _track_avoid_batch(self, {"arm": arm_ids}, goals, start_joints, dt, kp, ko, damping, spheres, capsules, link_radius,
                                   influence, avoid_gain, feedforward, rest_joints, rest_gain, limits, want, out, plan_only)
+
+    def track_pair_batch(self, goals_r: Any, goals_l: Any, start_r: Any, start_l: Any, dt: float, kp: float, ko: float, damping: Any,
+                         spheres: Any = None, capsules: Any = None, link_radius: Any = None, influence: float = 0.0,
+                         avoid_gain: float = 0.0, feedforward: Any = None, rest_joints: Any = None, rest_gain: float = 0.0,
+                         limits: Any = None, want: Sequence[str] = ("joints",), out: Optional[Dict[str, torch.Tensor]] = None,
+                         plan_only: bool = False) -> Dict[str, Any]:
+        """Both arms of n_pairs robots tracked in one launch, avoiding each other (HipSolver.track_pair, rsik_track_pair):
+        track_avoid_batch in which every arm has, beside the static spheres [S,4] and capsules [Cp,7] (none at all is allowed),
+        the other arm's three links as obstacles at every step, at the joints that arm has reached; influence, avoid_gain and
+        link_radius as in track_avoid_batch.
+        goals_r, goals_l: [T,12,n_pairs] or matrices [T,n_pairs,4,4], per arm; start_r, start_l: [n_pairs,7].  They are interleaved
+        (row 2 i the right arm of robot i, row 2 i + 1 its left arm).  With goals_l = None and start_l = None, goals_r and start_r are
+        taken as already interleaved arrays of 2 n_pairs rows.  damping, feedforward and rest_joints: a float (damping), an
+        interleaved array ([2 n_pairs], [T, 2 n_pairs, 6], [2 n_pairs, 7]), or a pair (right, left) of per-arm arrays.
+        Returns HipSolver.TRACK_PAIR_OUTPUTS as named in want — joints, rates [T,n_pairs,7], err [T,n_pairs,2], clearance
+        [T,n_pairs], nearest [T,n_pairs,2] int32 (link, obstacle index: S + Cp + l is the partner's link l), final_joints
+        [n_pairs,7], final_err [n_pairs,2], min_clearance [n_pairs] — each as {"r": ..., "l": ...}, two strided views of the
+        launch's interleaved tensor, which `out` takes as HipSolver.track_pair does.  plan_only adds "launch"."""
+        dev = self._solver.device
+        if (goals_l is None) != (start_l is None):
+            raise ValueError("goals_l and start_l: both per arm, or both None for interleaved goals_r and start_r")
+        if goals_l is None:
+            goals, start = _m12_steps(goals_r, dev), start_r
+        else:
+            goals, start = _interleave(_m12_steps(goals_r, dev), _m12_steps(goals_l, dev), 2, dev), _interleave(start_r, start_l, 0, dev)
+
+        def rows(x, dim):
+            return _interleave(x[0], x[1], dim, dev) if isinstance(x, (tuple, list)) and len(x) == 2 else x
+
+        self._upload()
+        res = self._solver.track_pair(goals.contiguous(), start, dt, kp, ko, damping=rows(damping, 0), spheres=spheres, capsules=capsules,
+                                      link_radius=link_radius, influence=influence, avoid_gain=avoid_gain,
+                                      feedforward=rows(feedforward, 1), rest_joints=rows(rest_joints, 0), rest_gain=rest_gain,
+                                      limits=limits, want=want, out=out, plan_only=plan_only)
+        split = {}
+        for name, x in res.items():
+            if name not in HipSolver.TRACK_PAIR_OUTPUTS:
+                split[name] = x
+            elif name in ("final_joints", "final_err", "min_clearance"):
+                split[name] = {"r": x[0::2], "l": x[1::2]}
+            else:
+                split[name] = {"r": x[:, 0::2], "l": x[:, 1::2]}
+        return split
 
     def clearance_batch(self, arm_ids: Any, joints: Any, spheres: Any = None, capsules: Any = None, link_radius: Any = None,
                         other_arm: Optional[Tuple[int, Any]] = None, want: Sequence[str] = ("clearance", "nearest"),
