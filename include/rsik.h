@@ -502,6 +502,67 @@ int rsik_solve_path(rsik_ctx *ctx, int64_t n, int64_t n_steps, const double *con
                     double *interval, uint8_t *reachable, uint8_t *state);
 
 /*
+ * rsik_solve_path_clear — rsik_solve_path among obstacles: the least-motion way through the samples that keep the arm at least
+ * min_clearance away from a static scene, with a price on coming nearer than `influence`, from one launch.  What a planner otherwise
+ * composes from rsik_solve_sweep, rsik_clearance over the n_theta * n_steps * n joints and a dynamic programme of its own.  Added within
+ * ABI version 8: a new symbol, no new option, nothing else changed.
+ *
+ * Every argument rsik_solve_path has means exactly what it means there: the layouts, both flags, the skip rule, the refusals and "Rows
+ * that are not numbers".  The workspace is rsik_solve_path's, and rsik_solve_path_workspace_bytes answers for both calls.
+ *   link_radius_host, n_spheres, spheres, n_capsules, capsules
+ *                    as rsik_track_avoid: 0 ... 256 spheres [n_spheres][4] and 0 ... 64 capsules [n_capsules][7] (device), at least one
+ *                    obstacle in all, 3 link radii on the host or NULL for zeros.  The scene is static and shared by every path,
+ *                    waypoint and sample.  An obstacle row with a NaN, an infinity or a negative radius is skipped, as there.
+ *   min_clearance    m: the hard constraint; finite, or -infinity for none
+ *   influence        m, finite and >= 0, and
+ *   clearance_gain   rad^2 per m^2, finite and >= 0: the soft term; a gain of 0 turns it off
+ *
+ * Definition, on top of rsik_solve_path's and as independent of the kernel's layout:
+ *   d(k) of sample k of waypoint (t, i) is, bit for bit, the `clearance` rsik_clearance returns for that sample's joints as
+ *   rsik_solve_sweep writes them (before any unwinding), with the path's arm, the same radii and the same obstacles; +infinity if every
+ *   obstacle is skipped.
+ *   A sample is a CANDIDATE iff it is one for rsik_solve_path and d(k) >= min_clearance (false for a NaN).  A waypoint whose samples
+ *   are all excluded is SKIPPED like any other, and stays `reachable`.
+ *   The node penalty is p(k) = (clearance_gain * u) * u with u = influence - d(k) where d(k) < influence, 0 elsewhere: a select,
+ *   unfused, in that order.
+ *   At a path's first solved waypoint A(k) = c(start_joints[i], J[k]) + p(k); without start_joints A(k) = p(k).
+ *   At every later solved waypoint A(j) = (min over i of (A(i) + c(J_prev[i], J[j]))) + p(j): the minimum first, then one more sum.
+ *   Ties go to the lowest i among equal values, and at the end to the lowest j, as in rsik_solve_path.
+ *   `cost` is the minimal A, penalties included; `step_cost` stays the root of the transition cost alone.
+ *
+ * Outputs beside rsik_solve_path's, any of them NULL (index, theta and joints all NULL remains RSIK_E_INVALID):
+ *   clearance        [n_steps][n]: d of the winning sample, NaN at a skipped waypoint
+ *   nearest          [n_steps][n][2] int32, aligned to 8 bytes: rsik_clearance's (link, obstacle index) for the winning sample; (-1, -1)
+ *                    at a skipped waypoint and where every obstacle is skipped
+ *   blocked          [n_steps][n] uint8: how many of the n_theta samples satisfy rsik_solve_path's candidate rule and fail
+ *                    d >= min_clearance; 0 on a lost path and at an invalid pose.  It tells why a waypoint was skipped.
+ *
+ * Guarantees:
+ *   Any subset of the outputs gives the same bits, and two launches give the same bits.
+ *   A path's bits depend neither on n nor on the other paths.
+ *   clearance and nearest are bit for bit what rsik_clearance returns for the `joints` this call returns without RSIK_PATH_UNWIND.
+ *   With min_clearance = -infinity and clearance_gain = 0 every output shared with rsik_solve_path has rsik_solve_path's bits.
+ *   index, cost and clearance do not depend on the order of the obstacles; nearest's obstacle index does.
+ *
+ * RSIK_E_INVALID, the first fault in this order, nothing written: what rsik_solve_path refuses of n, n_steps, n_theta, theta_policy,
+ * flags, weights and arms; n_spheres or n_capsules outside its range; no obstacle; a link radius, influence or clearance_gain that is
+ * negative or not finite; a min_clearance that is a NaN or +infinity; then, for n > 0, what rsik_solve_path refuses of its pointers and
+ * workspace; a NULL obstacle array with a count above 0; a `nearest` that is not aligned to 8 bytes.
+ * n == 0 launches nothing.  Enqueued on the context's stream; allocates nothing and never waits for the device.
+ */
+int rsik_solve_path_clear(rsik_ctx *ctx, int64_t n, int64_t n_steps, const double *const pose_soa[6],
+                          const uint8_t *arm, int arm_uniform,
+                          int n_theta, int theta_policy, const double *theta_in, int theta_per_pose,
+                          const double *start_joints, const double *weights_host, int flags,
+                          const double *link_radius_host, int n_spheres, const double *spheres, int n_capsules, const double *capsules,
+                          double min_clearance, double influence, double clearance_gain,
+                          void *workspace, size_t workspace_bytes,
+                          int32_t *index, double *theta, double *joints, double *elbow, uint8_t *projected,
+                          double *step_cost, double *cost, int32_t *n_solved,
+                          double *interval, uint8_t *reachable, uint8_t *state,
+                          double *clearance, int32_t *nearest, uint8_t *blocked);
+
+/*
  * rsik_reach_map — a reachability map (capability map): for each of n_pos positions, over one set of n_rot hand orientations, how
  * many of the orientations are reachable, which ones, with which is_reachable outcome, and how much elbow freedom is left.  What the
  * reference's task_space_test builds pose by pose (src/benchmark/ik_comparison.py:137-181), from one launch and with a few bytes of

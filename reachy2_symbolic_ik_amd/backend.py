@@ -407,6 +407,14 @@ class HipSolver:
         n_solved [n] int32, and interval [T, n, 2], reachable [T, n] u8, state [T, n] u8 as solve().
         The workspace is allocated here, with torch, from rsik_solve_path_workspace_bytes; a plan keeps it alive.
         plan_only=True launches nothing and adds res["launch"], a zero-overhead re-launch callable (see plan())."""
+        return self._solve_path(None, pose_soa, thetas, start_joints, policy, weights, skip_projected, unwind, arm, arm_uniform,
+                                want_elbow, out, plan_only)
+
+    def _solve_path(self, scene, pose_soa, thetas, start_joints, policy, weights, skip_projected, unwind, arm, arm_uniform, want_elbow,
+                    out, plan_only):
+        """What solve_path() and solve_path_clear() share: the checks, the workspace, the buffers and the call.  scene: None
+        (rsik_solve_path), or (tensors to keep alive, the C arguments between flags and the workspace) for rsik_solve_path_clear, which
+        has three outputs more."""
         if pose_soa.dim() != 3 or pose_soa.shape[0] != 6:
             raise ValueError("pose_soa must have shape [6, T, n]")
         code = self._policy_code(policy)
@@ -432,13 +440,83 @@ class HipSolver:
         self._reach_outs(res, out, (t, n))
         cols = self._cols(pose_soa, 6)
         flags = (_abi.PATH_SKIP_PROJECTED if skip_projected else 0) | (_abi.PATH_UNWIND if unwind else 0)
-        cargs = (n, t, cols, _ptr(arm), int(arm_uniform), k, code, _ptr(thetas), int(per_pose), _ptr(start_joints), wp, flags,
-                 _ptr(workspace), ws_bytes,
-                 _ptr(res["index"]), _ptr(res["theta"]), _ptr(res["joints"]), _ptr(res.get("elbow")), _ptr(res["projected"]),
-                 _ptr(res["step_cost"]), _ptr(res["cost"]), _ptr(res["n_solved"]),
-                 _ptr(res["interval"]), _ptr(res["reachable"]), _ptr(res["state"]))
+        cargs = (n, t, cols, _ptr(arm), int(arm_uniform), k, code, _ptr(thetas), int(per_pose), _ptr(start_joints), wp, flags)
+        keep, symbol = (pose_soa, arm, thetas, cols, start_joints, w, workspace), "rsik_solve_path"
+        if scene is not None:
+            res["clearance"] = self._out_buf(out, "clearance", (t, n), _F64)
+            res["nearest"] = self._out_buf(out, "nearest", (t, n, 2), torch.int32)
+            res["blocked"] = self._out_buf(out, "blocked", (t, n), _U8)
+            cargs, keep, symbol = cargs + scene[1], keep + scene[0], "rsik_solve_path_clear"
+        cargs += (_ptr(workspace), ws_bytes,
+                  _ptr(res["index"]), _ptr(res["theta"]), _ptr(res["joints"]), _ptr(res.get("elbow")), _ptr(res["projected"]),
+                  _ptr(res["step_cost"]), _ptr(res["cost"]), _ptr(res["n_solved"]),
+                  _ptr(res["interval"]), _ptr(res["reachable"]), _ptr(res["state"]))
+        if scene is not None:
+            cargs += (_ptr(res["clearance"]), _ptr(res["nearest"]), _ptr(res["blocked"]))
         # (the workspace: torch allocated it on the launch's stream and hands it out again in stream order; a plan keeps it)
-        return self._finish(res, "rsik_solve_path", cargs, plan_only, (pose_soa, arm, thetas, cols, start_joints, w, workspace))
+        return self._finish(res, symbol, cargs, plan_only, keep)
+
+    # ------------------------------------------------------------------ rsik_solve_path_clear
+    def solve_path_clear(
+        self,
+        pose_soa: torch.Tensor,
+        thetas: torch.Tensor,
+        start_joints: Optional[torch.Tensor] = None,
+        *,
+        spheres: Optional[torch.Tensor] = None,
+        capsules: Optional[torch.Tensor] = None,
+        link_radius: Any = None,
+        min_clearance: float = -float("inf"),
+        influence: float = 0.0,
+        clearance_gain: float = 0.0,
+        policy: str = "fraction",
+        weights: Optional[Sequence[float]] = None,
+        skip_projected: bool = False,
+        unwind: bool = False,
+        arm: Optional[torch.Tensor] = None,
+        arm_uniform: int = 0,
+        want_elbow: bool = True,
+        out: Optional[Dict[str, torch.Tensor]] = None,
+        plan_only: bool = False,
+    ) -> Dict[str, torch.Tensor]:
+        """solve_path() among obstacles, from one launch (rsik_solve_path_clear): the least-motion way through the samples that keep
+        the arm at least min_clearance away from a static scene.  Every argument of solve_path() means what it means there;
+        spheres [S, 4], capsules [C, 7] and link_radius are track_avoid()'s (S <= 256, C <= 64, at least one obstacle, shared by
+        every path, waypoint and sample).
+        d of a sample is clearance()'s `clearance` of its joints.  A sample with d < min_clearance (m; -inf: no constraint) is no
+        candidate; a waypoint left without one is skipped, index -1.  A sample with d < influence (m) adds
+        clearance_gain (influence - d)^2 (rad^2 per m^2) to the cost of every path through it; cost includes these penalties,
+        step_cost does not.  With min_clearance = -inf and clearance_gain = 0 the result is solve_path()'s, bit for bit.
+        Returns solve_path()'s dict and clearance [T, n], nearest [T, n, 2] int32 (link, obstacle index) — clearance()'s bits for
+        the returned joints (without unwind); NaN and (-1, -1) at a skipped waypoint — and blocked [T, n] u8: how many of the K
+        samples solve_path() would have taken as candidates fail d >= min_clearance.
+        The workspace is handled as in solve_path(); a plan keeps it and the obstacle tensors alive.
+        plan_only=True launches nothing and adds res["launch"], a zero-overhead re-launch callable (see plan())."""
+
+        def rows(t, width, most, message):
+            if t is None:
+                return None, 0
+            if not isinstance(t, torch.Tensor):
+                t = torch.as_tensor(np.asarray(t, dtype=np.float64))
+            if t.dim() != 2 or t.shape[1] != width or t.shape[0] > most:
+                raise ValueError(message)
+            count = int(t.shape[0])
+            return (self._dev_f64(t, (count, width), message.split()[0]) if count else None), count
+
+        spheres, n_spheres = rows(spheres, 4, self.TRACK_AVOID_MAX_SPHERES, "spheres must have shape [S, 4] with S <= 256")
+        capsules, n_capsules = rows(capsules, 7, self.TRACK_AVOID_MAX_CAPSULES, "capsules must have shape [C, 7] with C <= 64")
+        if n_spheres + n_capsules < 1:
+            raise ValueError("at least one obstacle: spheres [S, 4] or capsules [C, 7] (without obstacles: solve_path())")
+        rad, rad_p = None, None
+        if link_radius is not None:
+            rad = np.ascontiguousarray(link_radius.cpu().numpy() if isinstance(link_radius, torch.Tensor) else link_radius, dtype=np.float64)
+            if rad.shape != (3,):
+                raise ValueError("link_radius must have 3 entries")
+            rad_p = rad.ctypes.data_as(C.POINTER(C.c_double))
+        scene = ((spheres, capsules, rad),
+                 (rad_p, n_spheres, _ptr(spheres), n_capsules, _ptr(capsules), float(min_clearance), float(influence), float(clearance_gain)))
+        return self._solve_path(scene, pose_soa, thetas, start_joints, policy, weights, skip_projected, unwind, arm, arm_uniform,
+                                want_elbow, out, plan_only)
 
     # ------------------------------------------------------------------ rsik_reach_map
     REACH_MAP_OUTPUTS = ("count", "state_count", "theta_measure", "mask")

@@ -1,9 +1,14 @@
 // rsik_kernel_path.hpp — rsik_solve_path: n paths of n_steps waypoints, n_theta elbow angles per waypoint, and of the n_theta ^ n_steps
-// ways through them the one whose joints move least (solve_path_kernel)
+// ways through them the one whose joints move least (solve_path_kernel); rsik_solve_path_clear: the same kernel over PathClearArgs,
+// where a sample too close to a static set of obstacles is no candidate and one inside the influence distance pays a penalty
 #pragma once
 
+#include <type_traits>
+
 #include "rsik_goal.hpp"
+#include "rsik_kernel_clearance.hpp"    // clr_point, clr_segment, ClrBest
 #include "rsik_kernel_nearest.hpp"
+#include "rsik_kernel_track_avoid.hpp"  // kAvoidMaxSpheres, kAvoidMaxCapsules
 #include "rsik_rows.hpp"
 #include "rsik_tables.hpp"
 
@@ -36,6 +41,45 @@ struct PathArgs {
     uint8_t* reachable;  // [n_steps][n] or NULL
     uint8_t* state;      // [n_steps][n] or NULL
     ArmC arms[2];        // as SolveArgs.arms
+};
+
+// rsik_solve_path_clear's argument block: PathArgs' fields by the same names (solve_path_kernel reads either), then the scene, the
+// constraint and the three outputs that go with it.
+struct PathClearArgs {
+    int64_t n;
+    int64_t n_steps;
+    const double* in[6];
+    const uint8_t* arm;
+    int theta_policy;
+    int n_theta;
+    int theta_per_pose;
+    int skip_projected;
+    int unwind;
+    const double* theta_in;
+    double prev[7];
+    const double* start;
+    double weights[7];
+    uint8_t* back;
+    int32_t* index;
+    double* theta;
+    double* joints;
+    double* elbow;
+    uint8_t* projected;
+    double* step_cost;
+    double* cost;
+    int32_t* n_solved;
+    double* interval;
+    uint8_t* reachable;
+    uint8_t* state;
+    const double* spheres;   // [n_spheres][4]: x, y, z, r
+    const double* capsules;  // [n_capsules][7]: a, b, r
+    double* clearance;       // [n_steps][n] or NULL: d of the winning sample
+    int32_t* nearest;        // [n_steps][n][2] or NULL: (link, obstacle) of the winning sample
+    uint8_t* blocked;        // [n_steps][n] or NULL: candidates of rsik_solve_path that fail d >= min_clearance
+    int n_spheres, n_capsules;
+    double min_clearance, influence, clearance_gain;
+    double link_radius[3];
+    ArmC arms[2];
 };
 
 // This kernel's own constant accessor, for AccSweep's reason.
@@ -94,6 +138,100 @@ __device__ __forceinline__ double path_cost_at(const double (&w)[7], const doubl
     for (int q = 0; q < 7; q++) a[q] = p[q];
     return path_cost(w, b, a);
 }
+// The links of the arm at joints j as clearance_kernel forms them (its chain, restated as avoid_chain restates it and for the reason
+// written above jr_columns: the same expressions on the same operands, so the same bits): start points P[0 ... 2], directions e.
+template <class ACC>
+__device__ __forceinline__ void path_links(const ACC& A, double (&j)[7], V3 (&P)[4], V3 (&e)[3]) {
+    {
+        double far = fabs(j[0]);
+#pragma unroll
+        for (int k = 1; k < 7; k++) far = fmax(far, fabs(j[k]));
+        if (RSIK_RARE(far >= kFarAngle)) {  // one copy of the reduction: the seven values rotate through it
+#pragma clang loop unroll(disable)
+            for (int q = 0; q < 7; q++) {
+                const double t = j[0];
+                j[0] = j[1]; j[1] = j[2]; j[2] = j[3]; j[3] = j[4]; j[4] = j[5]; j[5] = j[6];
+                j[6] = near_angle(t);
+            }
+        }
+    }
+    double sn[7], cs[7];
+    {
+        const double a[4] = {j[0], j[1], j[2], j[3]}, b[3] = {j[4], j[5], j[6]};
+        double s1[4], c1[4], s2[3], c2[3];
+        fast_sincos_n<4>(a, s1, c1);
+        fast_sincos_n<3>(b, s2, c2);
+#pragma unroll
+        for (int k = 0; k < 4; k++) { sn[k] = s1[k]; cs[k] = c1[k]; }
+#pragma unroll
+        for (int k = 0; k < 3; k++) { sn[4 + k] = s2[k]; cs[4 + k] = c2[k]; }
+    }
+    auto mul = [](const double (&X)[9], const double (&Y)[9], double (&Z)[9]) {
+#pragma unroll
+        for (int rr = 0; rr < 3; rr++)
+#pragma unroll
+            for (int c = 0; c < 3; c++) Z[3 * rr + c] = fma(X[3 * rr], Y[c], fma(X[3 * rr + 1], Y[3 + c], X[3 * rr + 2] * Y[6 + c]));
+    };
+    const double c0 = cs[0], s0 = sn[0], c1 = cs[1], s1 = sn[1], c2 = cs[2], s2 = sn[2], c3 = cs[3], s3 = sn[3];
+    const double c4 = cs[4], s4 = sn[4], c5 = cs[5], s5 = sn[5], c6 = cs[6], s6 = sn[6];
+    const double Gt[9] = {c0 * c1, -c0 * s1, s0, s1, c1, 0.0, -s0 * c1, s0 * s1, c0};
+    const double H[9] = {c3, 0.0, s3, -s2 * s3, c2, s2 * c3, -c2 * s3, -s2, c2 * c3};
+    const double Kt[9] = {c4 * c5, -s4, c4 * s5, s4 * c5, c4, s4 * s5, -s5, 0.0, c5};
+    double Ms[9];
+#pragma unroll
+    for (int rr = 0; rr < 3; rr++)
+#pragma unroll
+        for (int c = 0; c < 3; c++) Ms[3 * rr + c] = A(RSIK_C_MST + 3 * c + rr);
+    double MG[9], MGH[9], Rt[9];
+    mul(Ms, Gt, MG);
+    mul(MG, H, MGH);
+    mul(MGH, Kt, Rt);
+    const auto column = [](const double (&M)[9], int c) { return V3{M[c], M[3 + c], M[6 + c]}; };
+    // goal axes as forward_kinematics forms them: x = Rt . (0, s6, c6), z = -Rt[:,0], y = z x x
+    const V3 xg = {fma(Rt[1], s6, Rt[2] * c6), fma(Rt[4], s6, Rt[5] * c6), fma(Rt[7], s6, Rt[8] * c6)};
+    const V3 zg = column(Rt, 0) * -1.0;
+    const V3 yg = cross(zg, xg);
+    const V3 tl = cvec(A, RSIK_C_TIPL);
+    const double u = A(RSIK_C_UPPER_ARM), f = A(RSIK_C_FOREARM);
+    const V3 ux = column(MG, 0), fx = column(MGH, 0);
+    e[0] = ux * u;
+    e[1] = fx * f;
+    e[2] = {-fma(xg.x, tl.x, fma(yg.x, tl.y, zg.x * tl.z)), -fma(xg.y, tl.x, fma(yg.y, tl.y, zg.y * tl.z)),
+            -fma(xg.z, tl.x, fma(yg.z, tl.y, zg.z * tl.z))};  // goal origin - wrist
+    P[0] = cvec(A, RSIK_C_SHOULDER);
+#pragma unroll
+    for (int l = 0; l < 3; l++) P[l + 1] = P[l] + e[l];
+}
+
+// clearance_kernel's pair loop over the obstacles a workgroup staged (track_avoid_kernel's layout), in its order: the clearance and
+// the code 4 * obstacle + link of the first minimum, -1 where every obstacle is skipped.  No witness: (s, t) are not kept.
+__device__ __forceinline__ ClrBest path_pairs(const V3 (&P)[4], const V3 (&e)[3], const double (&rl)[3], int n_spheres, int n_capsules,
+                                              const double* lds_sph, const double* lds_cap) {
+    double ee[3], inv_ee[3];
+#pragma unroll
+    for (int l = 0; l < 3; l++) { ee[l] = dot(e[l], e[l]); inv_ee[l] = clr_rcp(ee[l]); }
+    ClrBest B = {__builtin_inf(), 0.0, 0.0, -1};
+#pragma unroll 4  // (as track_avoid_kernel: four spheres' chains in flight; the capsule loop stays rolled)
+    for (int o = 0; o < n_spheres; o++) {
+        const V3 C = {lds_sph[o * 4], lds_sph[o * 4 + 1], lds_sph[o * 4 + 2]};
+        const double ro = lds_sph[o * 4 + 3];
+#pragma unroll
+        for (int l = 0; l < 3; l++) clr_point<false>(B, P[l], e[l], inv_ee[l], rl[l], C, ro, 4 * o + l);
+    }
+#pragma clang loop unroll(disable)
+    for (int o = 0; o < n_capsules; o++) {
+        const V3 Q0 = {lds_cap[o * 8], lds_cap[o * 8 + 1], lds_cap[o * 8 + 2]};
+        const V3 Q1 = {lds_cap[o * 8 + 3], lds_cap[o * 8 + 4], lds_cap[o * 8 + 5]};
+        const double ro = lds_cap[o * 8 + 6];
+        const V3 fq = Q1 - Q0;
+        const double ff = dot(fq, fq), inv_ff = clr_rcp(ff);
+#pragma unroll
+        for (int l = 0; l < 3; l++)
+            clr_segment<false>(B, P[l], e[l], ee[l], inv_ee[l], rl[l], Q0, fq, ff, inv_ff, ro, 4 * (n_spheres + o) + l);
+    }
+    return B;
+}
+
 __device__ __forceinline__ void path_lds_fence() {  // the wave's LDS writes are done before any lane reads another lane's
     wave_lds_fence();
     branch_stores_stay();
@@ -118,18 +256,51 @@ __device__ __forceinline__ void path_lds_fence() {  // the wave's LDS writes are
 #ifndef RSIK_PATH_MIN_WAVES
 #define RSIK_PATH_MIN_WAVES 1
 #endif
-template <int MIXED, bool TIPZ>
-__global__ __launch_bounds__(kBlock, RSIK_PATH_MIN_WAVES) void solve_path_kernel(const PathArgs K) {
+//
+// ARGS = PathClearArgs (rsik_solve_path_clear; `if constexpr (CLEAR)` below, nothing of it in rsik_solve_path's instantiations):
+//   obstacles  staged ONCE per workgroup ahead of the tables' barrier, as track_avoid_kernel stages them and with its validity test (a NaN
+//              in the radius of a skipped row, capsules padded to 8 doubles): 12 KiB beside the four waves' row sets.
+//   per trip   where some lane holds a candidate (forward pass), or a winner and clearance / nearest are asked for (output pass), a
+//              wave-uniform test: path_links and path_pairs on the lane's joints, d = the clearance rsik_clearance returns for them.
+//   forward    a candidate with !(d >= min_clearance) is none; `blocked` is the difference of the two ballots, stored by lane 0; the
+//              penalty p = (gain u) u, u = influence - d where d < influence, is added to A AFTER the minimum over the previous rows.
+//   output     d and the (link, obstacle) word of the winning sample, one store each per lane; NaN and (-1, -1) at a skipped waypoint.
+template <int MIXED, bool TIPZ, class ARGS = PathArgs>
+__global__ __launch_bounds__(kBlock, RSIK_PATH_MIN_WAVES) void solve_path_kernel(const ARGS K) {
+    constexpr bool CLEAR = std::is_same<ARGS, PathClearArgs>::value;
     constexpr int PB = kBlock / 64;  // paths per workgroup
     __shared__ SharedTables lds_tab;
     __shared__ __attribute__((aligned(16))) double lds[PB][kPathLds];
+    __shared__ __attribute__((aligned(16))) double lds_sph[CLEAR ? kAvoidMaxSpheres * 4 : 1];
+    __shared__ __attribute__((aligned(16))) double lds_cap[CLEAR ? kAvoidMaxCapsules * 8 : 1];
+    static_assert(sizeof(SharedTables) + sizeof(g_sincos_tab) + sizeof(double) * (PB * kPathLds + (kAvoidMaxSpheres * 4 + kAvoidMaxCapsules * 8)) <= 64 * 1024,
+                  "the static LDS of a workgroup: tables, row sets and the staged scene");
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int64_t path = (int64_t)blockIdx.x * PB + wave;
     const int64_t pc = path < K.n ? path : K.n - 1;  // (a wave past the end stages the tables with the others, then leaves)
 
-    warm_and_stage_tables<MIXED>(K, lds_tab);
-    const AccPath<MIXED> A = kernarg_acc<AccPath<MIXED>, PathArgs>(lds_tab, (MIXED != 0 && K.arm[pc] != 0) ? 1 : 0);
+    if constexpr (CLEAR) {  // the scene, once: n_spheres <= kAvoidMaxSpheres and n_capsules <= kAvoidMaxCapsules (the host refuses anything else)
+        for (int o = threadIdx.x; o < K.n_spheres; o += kBlock) {
+            double v[4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) v[k] = K.spheres[(int64_t)o * 4 + k];
+            if (!(all_finite(v) && v[3] >= 0.0)) v[3] = __builtin_nan("");
+#pragma unroll
+            for (int k = 0; k < 4; k++) lds_sph[o * 4 + k] = v[k];
+        }
+        for (int o = threadIdx.x; o < K.n_capsules; o += kBlock) {
+            double v[7];
+#pragma unroll
+            for (int k = 0; k < 7; k++) v[k] = K.capsules[(int64_t)o * 7 + k];
+            if (!(all_finite(v) && v[6] >= 0.0)) v[6] = __builtin_nan("");
+#pragma unroll
+            for (int k = 0; k < 7; k++) lds_cap[o * 8 + k] = v[k];
+            lds_cap[o * 8 + 7] = 0.0;
+        }
+    }
+    warm_and_stage_tables<MIXED>(K, lds_tab);  // (ends with the barrier that also stands behind the scene)
+    const AccPath<MIXED> A = kernarg_acc<AccPath<MIXED>, ARGS>(lds_tab, (MIXED != 0 && K.arm[pc] != 0) ? 1 : 0);
     if (path >= K.n) return;  // (wave-uniform; no workgroup barrier follows)
 
     double* lds_wave = lds[wave];
@@ -239,6 +410,34 @@ __global__ __launch_bounds__(kBlock, RSIK_PATH_MIN_WAVES) void solve_path_kernel
 #pragma unroll
             for (int q = 0; q < 7; q++) cand = cand && o.j[q] == o.j[q];  // "its joints are numbers"
         }
+        double pen = 0.0, clr = __builtin_nan("");  // CLEAR: p and d of this lane's sample
+        unsigned long long near_word = ~0ull;
+        if constexpr (CLEAR) {
+            const bool want_clr = K.clearance != nullptr || K.nearest != nullptr;
+            const bool sel = out ? (run && live) : cand;  // the lanes whose d is used
+            const unsigned long long pre = __builtin_amdgcn_ballot_w64(sel);
+            if (pre != 0 && (!out || want_clr)) {  // (scalar)
+                double jc[7];
+#pragma unroll
+                for (int q = 0; q < 7; q++) jc[q] = sel ? o.j[q] : 0.0;
+                const bool bad = !all_finite(jc);  // rsik_clearance: such a row is NaN
+                V3 P[4], e[3];
+                path_links(A, jc, P, e);
+                const ClrBest B = path_pairs(P, e, K.link_radius, K.n_spheres, K.n_capsules, lds_sph, lds_cap);
+                const bool none = B.code < 0;  // every obstacle was skipped
+                const int link = none ? 0 : (B.code & 3), obs = none ? 0 : (B.code >> 2);
+                clr = (bad || !sel) ? __builtin_nan("") : B.c;
+                near_word = (bad || none || !sel) ? ~0ull : ((unsigned long long)(unsigned)obs << 32) | (unsigned)link;  // (link, obstacle)
+            }
+            if (!out) {
+                cand = cand && clr >= K.min_clearance;  // (false for a NaN)
+                const double u = K.influence - clr;
+                const double p = (K.clearance_gain * u) * u;
+                pen = clr < K.influence ? p : 0.0;
+                const int n_blocked = __builtin_popcountll(pre) - __builtin_popcountll(__builtin_amdgcn_ballot_w64(cand));
+                if (K.blocked != nullptr && lane == 0) K.blocked[row] = (uint8_t)n_blocked;
+            }
+        }
 
         if (!out) {
             // ---- forward pass: A of this lane's sample, its backpointer
@@ -254,6 +453,7 @@ __global__ __launch_bounds__(kBlock, RSIK_PATH_MIN_WAVES) void solve_path_kernel
                     for (int q = 0; q < 7; q++) mine[q] = o.j[q];
                     if (solved == 0) {
                         a = has_start ? path_cost_at(w, o.j, carry) : 0.0;
+                        if constexpr (CLEAR) a = a + pen;
                         bp = kPathFirst;
                     } else {
                         // scalar: the candidates of the previous solved waypoint, ascending; the next one's row is read while this
@@ -273,6 +473,7 @@ __global__ __launch_bounds__(kBlock, RSIK_PATH_MIN_WAVES) void solve_path_kernel
                             pr = pr_next;
                             i = i_next;
                         }
+                        if constexpr (CLEAR) a = a + pen;  // the minimum first, then one more sum
                     }
                     mine[7] = a;
                 }
@@ -317,6 +518,10 @@ __global__ __launch_bounds__(kBlock, RSIK_PATH_MIN_WAVES) void solve_path_kernel
                 if (K.theta) st_stream(K.theta + row, theta);
                 if (K.projected) st_stream(K.projected + row, (uint8_t)(win_projected ? 1 : 0));
                 if (K.step_cost) st_stream(K.step_cost + row, step);
+                if constexpr (CLEAR) {
+                    if (K.clearance) st_stream(K.clearance + row, clr);
+                    if (K.nearest) st_stream((unsigned long long*)K.nearest + row, near_word);
+                }
             }
             path_lds_fence();  // (the carry row has been read)
             if (smask != 0) {

@@ -7,7 +7,7 @@
 // Every launching entry point reads: its own checks, in its own order (the return code and the message that wins are part of the
 // ABI), fill the kernel's argument block K, launch_begin, one launch line, launch_end.  What they share is below the memcpy entry
 // points: check_arms, bind_arms, copy_cols, launch_form / tip_on_z, launch_dims / launch_begin / launch_end; and, for the sampling
-// family (rsik_solve_sweep, rsik_solve_nearest, rsik_solve_path), check_samples, check_sample_inputs and fill_samples.
+// family (rsik_solve_sweep, rsik_solve_nearest, rsik_solve_path, rsik_solve_path_clear), check_samples, check_sample_inputs and fill_samples.
 //
 // Kernel shape: one pose per lane, 256-thread workgroups (4 wave64), SoA float64 inputs so that
 // every global load is a fully coalesced 512-B wave access; the [n,7] / [n,3] row outputs are
@@ -514,6 +514,49 @@ int rsik_solve_path_workspace_bytes(int64_t n, int64_t n_steps, int n_theta, siz
     return RSIK_OK;
 }
 
+// What rsik_solve_path and rsik_solve_path_clear share.  The checks come in two halves, in the order that is part of the ABI: those a call
+// with n == 0 makes too, and those on the inputs no launch of n > 0 goes without; rsik_solve_path_clear's own stand behind each half.
+static int check_path_shape(rsik_ctx* ctx, const char* who, int64_t n, int64_t n_steps, int n_theta, int theta_policy, int flags,
+                            const double* weights_host, const uint8_t* arm, int arm_uniform) {
+    const std::string w(who);
+    if (n < 0) return fail(ctx, RSIK_E_INVALID, w + ": n < 0");
+    if (n_steps < 1 || n_steps > 65536) return fail(ctx, RSIK_E_INVALID, w + ": n_steps must be in [1, 65536]");
+    return check_samples(ctx, who, n_theta, 64, theta_policy, flags, RSIK_PATH_SKIP_PROJECTED | RSIK_PATH_UNWIND, weights_host, arm, arm_uniform);
+}
+static int check_path_inputs(rsik_ctx* ctx, const char* who, int64_t n, int64_t n_steps, int n_theta, const double* const pose_soa[6],
+                             const double* theta_in, const void* workspace, size_t workspace_bytes, const int32_t* index,
+                             const double* theta, const double* joints) {
+    const std::string w(who);
+    const int rc = check_sample_inputs(ctx, who, pose_soa, theta_in);
+    if (rc != RSIK_OK) return rc;
+    if (!index && !theta && !joints) return fail(ctx, RSIK_E_INVALID, w + ": index, theta and joints are all NULL");
+    size_t need = 0;
+    if (!path_workspace_bytes(n, n_steps, n_theta, &need)) return fail(ctx, RSIK_E_INVALID, w + ": n * n_steps too large");
+    if (!workspace || workspace_bytes < need) return fail(ctx, RSIK_E_INVALID, w + ": workspace is NULL or smaller than rsik_solve_path_workspace_bytes");
+    return RSIK_OK;
+}
+extern "C++" {  // (templates)
+// PathArgs or PathClearArgs: the fields of the first, by name
+template <class ARGS>
+static int fill_path(rsik_ctx* ctx, const char* who, ARGS& K, int64_t n, int64_t n_steps, const double* const pose_soa[6], const uint8_t* arm,
+                     int arm_uniform, int n_theta, int theta_policy, const double* theta_in, int theta_per_pose, const double* start_joints,
+                     const double* weights_host, int flags, void* workspace, int32_t* index, double* theta, double* joints, double* elbow,
+                     uint8_t* projected, double* step_cost, double* cost, int32_t* n_solved, double* interval, uint8_t* reachable, uint8_t* state) {
+    const int rc = fill_samples(ctx, who, K, n, pose_soa, arm, arm_uniform, n_theta, theta_policy, theta_in, theta_per_pose, interval, reachable, state);
+    if (rc != RSIK_OK) return rc;
+    K.n_steps = n_steps;
+    K.skip_projected = (flags & RSIK_PATH_SKIP_PROJECTED) != 0;
+    K.unwind = (flags & RSIK_PATH_UNWIND) != 0;
+    fill7(K.prev, nullptr, 0.0);
+    K.start = start_joints;
+    fill7(K.weights, weights_host, 1.0);
+    K.back = static_cast<uint8_t*>(workspace);
+    K.index = index; K.theta = theta; K.joints = joints; K.elbow = elbow; K.projected = projected;
+    K.step_cost = step_cost; K.cost = cost; K.n_solved = n_solved;
+    return RSIK_OK;
+}
+}
+
 // rsik_solve_path: rsik_solve_sweep's samples at every waypoint of n paths, and the way through them that moves the joints least (rsik_kernel_path.hpp)
 int rsik_solve_path(rsik_ctx* ctx, int64_t n, int64_t n_steps, const double* const pose_soa[6], const uint8_t* arm, int arm_uniform,
                     int n_theta, int theta_policy, const double* theta_in, int theta_per_pose,
@@ -524,32 +567,63 @@ int rsik_solve_path(rsik_ctx* ctx, int64_t n, int64_t n_steps, const double* con
                     double* interval, uint8_t* reachable, uint8_t* state) {
     if (!ctx) return RSIK_E_INVALID;
     const char* who = "rsik_solve_path";
-    const std::string w(who);
-    if (n < 0) return fail(ctx, RSIK_E_INVALID, w + ": n < 0");
-    if (n_steps < 1 || n_steps > 65536) return fail(ctx, RSIK_E_INVALID, w + ": n_steps must be in [1, 65536]");
-    int rc = check_samples(ctx, who, n_theta, 64, theta_policy, flags, RSIK_PATH_SKIP_PROJECTED | RSIK_PATH_UNWIND, weights_host, arm, arm_uniform);
+    int rc = check_path_shape(ctx, who, n, n_steps, n_theta, theta_policy, flags, weights_host, arm, arm_uniform);
     if (rc != RSIK_OK) return rc;
     if (n == 0) return RSIK_OK;
-    if ((rc = check_sample_inputs(ctx, who, pose_soa, theta_in)) != RSIK_OK) return rc;
-    if (!index && !theta && !joints) return fail(ctx, RSIK_E_INVALID, w + ": index, theta and joints are all NULL");
-    size_t need = 0;
-    if (!path_workspace_bytes(n, n_steps, n_theta, &need)) return fail(ctx, RSIK_E_INVALID, w + ": n * n_steps too large");
-    if (!workspace || workspace_bytes < need) return fail(ctx, RSIK_E_INVALID, w + ": workspace is NULL or smaller than rsik_solve_path_workspace_bytes");
+    if ((rc = check_path_inputs(ctx, who, n, n_steps, n_theta, pose_soa, theta_in, workspace, workspace_bytes, index, theta, joints)) != RSIK_OK) return rc;
     rsik::PathArgs K;
-    if ((rc = fill_samples(ctx, who, K, n, pose_soa, arm, arm_uniform, n_theta, theta_policy, theta_in, theta_per_pose, interval, reachable, state)) != RSIK_OK) return rc;
-    K.n_steps = n_steps;
-    K.skip_projected = (flags & RSIK_PATH_SKIP_PROJECTED) != 0;
-    K.unwind = (flags & RSIK_PATH_UNWIND) != 0;
-    fill7(K.prev, nullptr, 0.0);
-    K.start = start_joints;
-    fill7(K.weights, weights_host, 1.0);
-    K.back = static_cast<uint8_t*>(workspace);
-    K.index = index; K.theta = theta; K.joints = joints; K.elbow = elbow; K.projected = projected;
-    K.step_cost = step_cost; K.cost = cost; K.n_solved = n_solved;
+    if ((rc = fill_path(ctx, who, K, n, n_steps, pose_soa, arm, arm_uniform, n_theta, theta_policy, theta_in, theta_per_pose, start_joints,
+                        weights_host, flags, workspace, index, theta, joints, elbow, projected, step_cost, cost, n_solved, interval, reachable, state)) != RSIK_OK) return rc;
     dim3 grid, block(rsik::kBlock);
     if ((rc = launch_begin(ctx, n, &grid, who, rsik::kBlock / 64)) != RSIK_OK) return rc;
     with_int3(launch_form(ctx, K.arms, arm), [&](auto FORM) { with_bool(tip_on_z(ctx, K.arms), [&](auto TIPZ) {
         hipLaunchKernelGGL((rsik::solve_path_kernel<FORM(), TIPZ()>), grid, block, 0, ctx->stream, K); }); });
+    return launch_end(ctx);
+}
+
+// rsik_solve_path_clear: rsik_solve_path where a sample nearer than min_clearance to a static scene is no candidate, and one nearer
+// than `influence` pays for it (solve_path_kernel over PathClearArgs, rsik_kernel_path.hpp).  The scene's limits and checks are rsik_track_avoid's.
+int rsik_solve_path_clear(rsik_ctx* ctx, int64_t n, int64_t n_steps, const double* const pose_soa[6], const uint8_t* arm, int arm_uniform,
+                          int n_theta, int theta_policy, const double* theta_in, int theta_per_pose,
+                          const double* start_joints, const double* weights_host, int flags,
+                          const double* link_radius_host, int n_spheres, const double* spheres, int n_capsules, const double* capsules,
+                          double min_clearance, double influence, double clearance_gain,
+                          void* workspace, size_t workspace_bytes,
+                          int32_t* index, double* theta, double* joints, double* elbow, uint8_t* projected,
+                          double* step_cost, double* cost, int32_t* n_solved,
+                          double* interval, uint8_t* reachable, uint8_t* state,
+                          double* clearance, int32_t* nearest, uint8_t* blocked) {
+    if (!ctx) return RSIK_E_INVALID;
+    const char* who = "rsik_solve_path_clear";
+    const std::string w(who);
+    const auto gain_ok = [](double g) { return std::isfinite(g) && g >= 0.0; };
+    int rc = check_path_shape(ctx, who, n, n_steps, n_theta, theta_policy, flags, weights_host, arm, arm_uniform);
+    if (rc != RSIK_OK) return rc;
+    if (n_spheres < 0 || n_spheres > rsik::kAvoidMaxSpheres) return fail(ctx, RSIK_E_INVALID, w + ": n_spheres must be 0 ... 256");
+    if (n_capsules < 0 || n_capsules > rsik::kAvoidMaxCapsules) return fail(ctx, RSIK_E_INVALID, w + ": n_capsules must be 0 ... 64");
+    if (n_spheres + n_capsules < 1) return fail(ctx, RSIK_E_INVALID, w + ": at least one obstacle (without obstacles: rsik_solve_path)");
+    for (int l = 0; link_radius_host && l < 3; l++)
+        if (!gain_ok(link_radius_host[l])) return fail(ctx, RSIK_E_INVALID, w + ": every link radius must be finite and >= 0");
+    if (!gain_ok(influence) || !gain_ok(clearance_gain))
+        return fail(ctx, RSIK_E_INVALID, w + ": influence and clearance_gain must be finite and >= 0");
+    if (!(min_clearance < __builtin_inf()))  // (a NaN fails it too)
+        return fail(ctx, RSIK_E_INVALID, w + ": min_clearance must be finite or -infinity");
+    if (n == 0) return RSIK_OK;
+    if ((rc = check_path_inputs(ctx, who, n, n_steps, n_theta, pose_soa, theta_in, workspace, workspace_bytes, index, theta, joints)) != RSIK_OK) return rc;
+    if ((n_spheres > 0 && !spheres) || (n_capsules > 0 && !capsules))
+        return fail(ctx, RSIK_E_INVALID, w + ": spheres or capsules is NULL with a count above 0");
+    if (((uintptr_t)nearest & 7) != 0) return fail(ctx, RSIK_E_INVALID, w + ": nearest must be aligned to 8 bytes");
+    rsik::PathClearArgs K;
+    if ((rc = fill_path(ctx, who, K, n, n_steps, pose_soa, arm, arm_uniform, n_theta, theta_policy, theta_in, theta_per_pose, start_joints,
+                        weights_host, flags, workspace, index, theta, joints, elbow, projected, step_cost, cost, n_solved, interval, reachable, state)) != RSIK_OK) return rc;
+    K.spheres = spheres; K.capsules = capsules; K.n_spheres = n_spheres; K.n_capsules = n_capsules;
+    K.clearance = clearance; K.nearest = nearest; K.blocked = blocked;
+    K.min_clearance = min_clearance; K.influence = influence; K.clearance_gain = clearance_gain;
+    for (int l = 0; l < 3; l++) K.link_radius[l] = link_radius_host ? link_radius_host[l] : 0.0;
+    dim3 grid, block(rsik::kBlock);
+    if ((rc = launch_begin(ctx, n, &grid, who, rsik::kBlock / 64)) != RSIK_OK) return rc;
+    with_int3(launch_form(ctx, K.arms, arm), [&](auto FORM) { with_bool(tip_on_z(ctx, K.arms), [&](auto TIPZ) {
+        hipLaunchKernelGGL((rsik::solve_path_kernel<FORM(), TIPZ(), rsik::PathClearArgs>), grid, block, 0, ctx->stream, K); }); });
     return launch_end(ctx);
 }
 

@@ -357,6 +357,22 @@ class SymbolicIK:
         return _path_batch(self, {"arm_uniform": self.arm_id}, poses, start_joints, n_theta, thetas, policy, weights, skip_projected,
                            unwind, want_elbow, out, plan_only)
 
+    def path_clear_batch(self, poses: Any, start_joints: Any = None, spheres: Any = None, capsules: Any = None, link_radius: Any = None,
+                         min_clearance: float = -float("inf"), influence: float = 0.0, clearance_gain: float = 0.0, n_theta: int = 16,
+                         thetas: Any = None, policy: str = "fraction", weights: Optional[Sequence[float]] = None,
+                         skip_projected: bool = False, unwind: bool = False, want_elbow: bool = True,
+                         out: Optional[Dict[str, torch.Tensor]] = None, plan_only: bool = False) -> Dict[str, torch.Tensor]:
+        """path_batch among obstacles, in one launch (HipSolver.solve_path_clear, rsik_solve_path_clear): the least-motion sequence
+        of elbow angles among the samples whose arm stays at least min_clearance (m; -inf: no constraint) away from the static
+        scene spheres [S,4] (S <= 256), capsules [Cp,7] (Cp <= 64) with link_radius (3 values), clearance_batch's obstacle
+        arguments, at least one obstacle in all.  A sample nearer than influence (m) adds clearance_gain (influence - d)^2 to the
+        cost of the paths through it.  Every other argument is path_batch's.
+        Returns path_batch's tensors and clearance [T,n], nearest [T,n,2] int32 — clearance_batch's for the returned joints — and
+        blocked [T,n] u8, the samples of a waypoint that only the constraint excluded."""
+        return _path_clear_batch(self, {"arm_uniform": self.arm_id}, poses, start_joints, spheres, capsules, link_radius, min_clearance,
+                                 influence, clearance_gain, n_theta, thetas, policy, weights, skip_projected, unwind, want_elbow, out,
+                                 plan_only)
+
     def reach_map_batch(self, positions: Any, orientations: Any, want: Sequence[str] = HipSolver.REACH_MAP_OUTPUTS,
                         out: Optional[Dict[str, torch.Tensor]] = None, plan_only: bool = False) -> Dict[str, torch.Tensor]:
         """A reachability map (capability map) of this arm in one launch: every position with every orientation of one set,
@@ -600,6 +616,17 @@ def _path_batch(ik, arm, poses, start_joints, n_theta, thetas, policy, weights, 
                                  unwind=unwind, want_elbow=want_elbow, out=out, plan_only=plan_only, **arm)
 
 
+def _path_clear_batch(ik, arm, poses, start_joints, spheres, capsules, link_radius, min_clearance, influence, clearance_gain, n_theta,
+                      thetas, policy, weights, skip_projected, unwind, want_elbow, out, plan_only):
+    soa = _path_soa(poses, ik._solver.device)
+    thetas = _default_grid(thetas, n_theta, 0.5)
+    ik._upload()
+    return ik._solver.solve_path_clear(soa, thetas, start_joints, spheres=spheres, capsules=capsules, link_radius=link_radius,
+                                       min_clearance=min_clearance, influence=influence, clearance_gain=clearance_gain, policy=policy,
+                                       weights=weights, skip_projected=skip_projected, unwind=unwind, want_elbow=want_elbow, out=out,
+                                       plan_only=plan_only, **arm)
+
+
 def _xyz_soa(rows: Any, device: Any, name: str) -> torch.Tensor:
     """[n,3] rows or SoA [3,n] -> SoA [3,n] float64 on the device (a [3,3] input is taken as rows)."""
     t = rows if isinstance(rows, torch.Tensor) else torch.as_tensor(np.asarray(rows, dtype=np.float64))
@@ -746,6 +773,19 @@ class DualArmIK:
         angles along every path (index [T, n] int32, theta, joints [T,n,7], step_cost, cost [n] ...)."""
         return _path_batch(self, {"arm": arm_ids}, poses, start_joints, n_theta, thetas, policy, weights, skip_projected, unwind,
                            want_elbow, out, plan_only)
+
+    def path_clear_batch(self, arm_ids: Any, poses: Any, start_joints: Any = None, spheres: Any = None, capsules: Any = None,
+                         link_radius: Any = None, min_clearance: float = -float("inf"), influence: float = 0.0,
+                         clearance_gain: float = 0.0, n_theta: int = 16, thetas: Any = None, policy: str = "fraction",
+                         weights: Optional[Sequence[float]] = None, skip_projected: bool = False, unwind: bool = False,
+                         want_elbow: bool = True, out: Optional[Dict[str, torch.Tensor]] = None,
+                         plan_only: bool = False) -> Dict[str, torch.Tensor]:
+        """SymbolicIK.path_clear_batch for paths of both arms (arm_ids [n] uint8, one byte per path): path_batch among the static
+        obstacles spheres [S,4] and capsules [Cp,7] of clearance_batch, samples nearer than min_clearance excluded and those nearer
+        than influence charged clearance_gain (influence - d)^2; path_batch's tensors and clearance [T,n], nearest [T,n,2] int32,
+        blocked [T,n] u8."""
+        return _path_clear_batch(self, {"arm": arm_ids}, poses, start_joints, spheres, capsules, link_radius, min_clearance, influence,
+                                 clearance_gain, n_theta, thetas, policy, weights, skip_projected, unwind, want_elbow, out, plan_only)
 
     def reach_map_batch(self, arm_ids: Any, positions: Any, orientations: Any, want: Sequence[str] = HipSolver.REACH_MAP_OUTPUTS,
                         out: Optional[Dict[str, torch.Tensor]] = None, plan_only: bool = False) -> Dict[str, torch.Tensor]:
