@@ -563,6 +563,77 @@ int rsik_solve_path_clear(rsik_ctx *ctx, int64_t n, int64_t n_steps, const doubl
                           double *clearance, int32_t *nearest, uint8_t *blocked);
 
 /*
+ * rsik_solve_path_pair — rsik_solve_path_clear for n_pairs robots of two arms that keep out of each other: the elbow angles along two
+ * hand paths, chosen together, so that neither arm comes nearer than min_clearance to a static scene or to the other arm, from one
+ * launch.  A state of the dynamic programme is a PAIR of samples, one per arm; the n_theta^2 arm-to-arm distances per waypoint stay
+ * on the device.  Added within ABI version 8: two new symbols, no new option, nothing else changed.
+ *
+ * Rows are rsik_track_pair's: n = 2 * n_pairs, row 2i the right arm of robot i, row 2i + 1 its left arm; there is no arm argument and
+ * both arms' constants must be set (RSIK_E_NOT_SET otherwise).  Every per-waypoint array has rsik_solve_path_clear's layout for n rows
+ * ([n_steps][n]...), so one set of buffers serves rsik_solve_path_clear with arm bytes 0, 1, 0, 1, ... and then this call;
+ * start_joints is [n][7]; weights_host, 7 doubles, is shared by both arms.  Per robot: cost [n_pairs], n_solved [n_pairs] and
+ * blocked [n_steps][n_pairs], uint16 (the count can reach 256).
+ * Every argument rsik_solve_path_clear has means what it means there — policies, both flags, "Rows that are not numbers" — but:
+ *   n_theta          1 ... 16 (a robot has at most 256 states); anything else: RSIK_E_INVALID
+ *   the scene        may be empty, as in rsik_track_pair: the partner is always an obstacle
+ *   workspace        at least rsik_solve_path_pair_workspace_bytes(n_pairs, n_steps, n_theta) bytes (n_pairs * n_steps *
+ *                    (n_theta^2 + 3): a backpointer byte per state, a flag and two winners per waypoint), monotone in each argument
+ *
+ * Definition (the result does not depend on how the kernel is laid out):
+ *   Sample a of row 2i and sample b of row 2i + 1 at waypoint t are rsik_solve_sweep's samples over the n_steps * n poses with arm
+ *   bytes 0, 1, 0, 1, ...; JR[a] and JL[b] are their joints.  Each is a ROW CANDIDATE by rsik_solve_path's rule (reachable, no NaN, flags).
+ *   dR(a, b) is, bit for bit, rsik_clearance's `clearance` of JR[a] with the right arm, the given radii, the static spheres, and the
+ *   static capsules followed by three more: (P_l, P_{l+1}, link_radius[l]), l = 0, 1, 2, with P the link_points rsik_clearance returns
+ *   for JL[b] — rsik_track_pair's construction, with its obstacle indices n_spheres + n_capsules + l.  dL(a, b) is the same with the
+ *   arms exchanged.  The two can differ in the last bit; both are kept.
+ *   (a, b) is a CANDIDATE PAIR iff both are row candidates, dR(a, b) >= min_clearance and dL(a, b) >= min_clearance (false for a NaN).
+ *   A waypoint with at least one candidate pair is SOLVED for both arms; any other is SKIPPED for both: index -1 and NaN in both
+ *   rows, and the path goes on as if the waypoint were not there.  (A stretch one arm cannot reach is planned for the other arm
+ *   alone with rsik_solve_path_clear.)
+ *   The penalty is p(a, b) = pR + pL, each rsik_solve_path_clear's select on its own d; pR first, then one sum.
+ *   At the first solved waypoint A(a, b) = (cR(startR, JR[a]) + cL(startL, JL[b])) + p(a, b); without start_joints A(a, b) = p(a, b).
+ *   c is rsik_solve_path's transition cost on the arm's own joints.
+ *   At every later solved waypoint, in two stages over the candidate pairs of the previous solved waypoint:
+ *     1. B(a, b') = min over b with (a, b) a candidate pair of (A(a, b) + cL(JLprev[b], JL[b'])), the lowest b among equal values;
+ *     2. A'(a', b') = (min over a for which B(a, b') exists of (B(a, b') + cR(JRprev[a], JR[a']))) + p(a', b'), the lowest a among
+ *        equal values.  The backpointer of (a', b') is (a, the b stage 1 chose for (a, b')).
+ *   The path ends in the candidate pair with the smallest A, the lowest a * n_theta + b among equal values; the other winners follow
+ *   the backpointers.  `cost` is that A; `step_cost` is, per row, the root of that arm's own transition cost.
+ *   RSIK_PATH_UNWIND acts per row, as in rsik_solve_path.
+ *   A NaN or an infinity in either start row loses the whole robot: n_solved 0, index -1, cost NaN, blocked 0; no other robot changes.
+ *
+ * Outputs, any of them NULL (index, theta and joints all NULL: RSIK_E_INVALID):
+ *   index, theta, joints, elbow, projected   of row r at (t, r): the bits of the sweep's winning sample of that row
+ *   clearance        [n_steps][n]: clearance[t][2i] = dR of the winning pair, clearance[t][2i + 1] = dL; NaN at a skipped waypoint
+ *   nearest          [n_steps][n][2] int32, aligned to 8 bytes: the (link, obstacle) of each view; (-1, -1) at a skipped waypoint
+ *   blocked          [n_steps][n_pairs] uint16: the pairs (a, b) that are both row candidates and no candidate pair
+ *   interval, reachable, state   as rsik_solve for the n_steps * n poses: a waypoint can be reachable for both arms and skipped
+ *
+ * Guarantees:
+ *   Any subset of the outputs gives the same bits, and two launches give the same bits.
+ *   A robot's bits depend neither on n_pairs, nor on its place in the launch, nor on the other robots.
+ *   clearance and nearest of a row are bit for bit rsik_clearance's for the row's returned joints (without RSIK_PATH_UNWIND), with the
+ *   static scene followed by the three capsules built from the partner's returned joints.
+ *
+ * RSIK_E_INVALID, the first fault in this order, nothing written: n_pairs < 0; then what rsik_solve_path_clear refuses, in its order,
+ * with n_theta above 16 refused and "no obstacle" not.  n_pairs == 0 launches nothing.  Enqueued on the context's stream; allocates
+ * nothing and never waits for the device.
+ *
+ * rsik_solve_path_pair_workspace_bytes — RSIK_E_INVALID for a NULL `bytes` or arguments rsik_solve_path_pair refuses.
+ */
+int rsik_solve_path_pair_workspace_bytes(int64_t n_pairs, int64_t n_steps, int n_theta, size_t *bytes);
+int rsik_solve_path_pair(rsik_ctx *ctx, int64_t n_pairs, int64_t n_steps, const double *const pose_soa[6],
+                         int n_theta, int theta_policy, const double *theta_in, int theta_per_pose,
+                         const double *start_joints, const double *weights_host, int flags,
+                         const double *link_radius_host, int n_spheres, const double *spheres, int n_capsules, const double *capsules,
+                         double min_clearance, double influence, double clearance_gain,
+                         void *workspace, size_t workspace_bytes,
+                         int32_t *index, double *theta, double *joints, double *elbow, uint8_t *projected,
+                         double *step_cost, double *cost, int32_t *n_solved,
+                         double *interval, uint8_t *reachable, uint8_t *state,
+                         double *clearance, int32_t *nearest, uint16_t *blocked);
+
+/*
  * rsik_reach_map — a reachability map (capability map): for each of n_pos positions, over one set of n_rot hand orientations, how
  * many of the orientations are reachable, which ones, with which is_reachable outcome, and how much elbow freedom is left.  What the
  * reference's task_space_test builds pose by pose (src/benchmark/ik_comparison.py:137-181), from one launch and with a few bytes of

@@ -68,6 +68,10 @@ PROTOTYPES = {
     "rsik_solve_path_clear": (C.c_int, [_vp, C.c_int64, C.c_int64, C.POINTER(_vp), _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _dp, C.c_int,
                                         _dp, C.c_int, _vp, C.c_int, _vp, C.c_double, C.c_double, C.c_double,
                                         _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rsik_solve_path_pair_workspace_bytes": (C.c_int, [C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_size_t)]),
+    "rsik_solve_path_pair": (C.c_int, [_vp, C.c_int64, C.c_int64, C.POINTER(_vp), C.c_int, C.c_int, _vp, C.c_int, _vp, _dp, C.c_int,
+                                       _dp, C.c_int, _vp, C.c_int, _vp, C.c_double, C.c_double, C.c_double,
+                                       _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rsik_reach_map": (C.c_int, [_vp, C.c_int64, C.POINTER(_vp), _vp, C.c_int, C.c_int, C.POINTER(_vp), _vp, _vp, _vp, _vp]),
     "rsik_control_discrete_rows": (C.c_int, [_vp, C.c_int64, C.POINTER(_vp), _vp, C.c_int, C.c_int, C.c_double, C.c_int, _vp,
                                              _vp, C.c_double, _vp, _vp, _vp, _vp]),

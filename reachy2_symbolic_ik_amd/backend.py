@@ -456,6 +456,32 @@ class HipSolver:
         # (the workspace: torch allocated it on the launch's stream and hands it out again in stream order; a plan keeps it)
         return self._finish(res, symbol, cargs, plan_only, keep)
 
+    def _path_scene(self, spheres, capsules, link_radius, need_obstacle: bool):
+        """The static scene of solve_path_clear() and solve_path_pair(): (tensors to keep alive, the C arguments link_radius_host,
+        n_spheres, spheres, n_capsules, capsules).  need_obstacle: solve_path_clear() refuses a call without one."""
+
+        def rows(t, width, most, message):
+            if t is None:
+                return None, 0
+            if not isinstance(t, torch.Tensor):
+                t = torch.as_tensor(np.asarray(t, dtype=np.float64))
+            if t.dim() != 2 or t.shape[1] != width or t.shape[0] > most:
+                raise ValueError(message)
+            count = int(t.shape[0])
+            return (self._dev_f64(t, (count, width), message.split()[0]) if count else None), count
+
+        spheres, n_spheres = rows(spheres, 4, self.TRACK_AVOID_MAX_SPHERES, "spheres must have shape [S, 4] with S <= 256")
+        capsules, n_capsules = rows(capsules, 7, self.TRACK_AVOID_MAX_CAPSULES, "capsules must have shape [C, 7] with C <= 64")
+        if need_obstacle and n_spheres + n_capsules < 1:
+            raise ValueError("at least one obstacle: spheres [S, 4] or capsules [C, 7] (without obstacles: solve_path())")
+        rad, rad_p = None, None
+        if link_radius is not None:
+            rad = np.ascontiguousarray(link_radius.cpu().numpy() if isinstance(link_radius, torch.Tensor) else link_radius, dtype=np.float64)
+            if rad.shape != (3,):
+                raise ValueError("link_radius must have 3 entries")
+            rad_p = rad.ctypes.data_as(C.POINTER(C.c_double))
+        return (spheres, capsules, rad), (rad_p, n_spheres, _ptr(spheres), n_capsules, _ptr(capsules))
+
     # ------------------------------------------------------------------ rsik_solve_path_clear
     def solve_path_clear(
         self,
@@ -493,30 +519,94 @@ class HipSolver:
         The workspace is handled as in solve_path(); a plan keeps it and the obstacle tensors alive.
         plan_only=True launches nothing and adds res["launch"], a zero-overhead re-launch callable (see plan())."""
 
-        def rows(t, width, most, message):
-            if t is None:
-                return None, 0
-            if not isinstance(t, torch.Tensor):
-                t = torch.as_tensor(np.asarray(t, dtype=np.float64))
-            if t.dim() != 2 or t.shape[1] != width or t.shape[0] > most:
-                raise ValueError(message)
-            count = int(t.shape[0])
-            return (self._dev_f64(t, (count, width), message.split()[0]) if count else None), count
-
-        spheres, n_spheres = rows(spheres, 4, self.TRACK_AVOID_MAX_SPHERES, "spheres must have shape [S, 4] with S <= 256")
-        capsules, n_capsules = rows(capsules, 7, self.TRACK_AVOID_MAX_CAPSULES, "capsules must have shape [C, 7] with C <= 64")
-        if n_spheres + n_capsules < 1:
-            raise ValueError("at least one obstacle: spheres [S, 4] or capsules [C, 7] (without obstacles: solve_path())")
-        rad, rad_p = None, None
-        if link_radius is not None:
-            rad = np.ascontiguousarray(link_radius.cpu().numpy() if isinstance(link_radius, torch.Tensor) else link_radius, dtype=np.float64)
-            if rad.shape != (3,):
-                raise ValueError("link_radius must have 3 entries")
-            rad_p = rad.ctypes.data_as(C.POINTER(C.c_double))
-        scene = ((spheres, capsules, rad),
-                 (rad_p, n_spheres, _ptr(spheres), n_capsules, _ptr(capsules), float(min_clearance), float(influence), float(clearance_gain)))
+        keep, scene_args = self._path_scene(spheres, capsules, link_radius, True)
+        scene = (keep, scene_args + (float(min_clearance), float(influence), float(clearance_gain)))
         return self._solve_path(scene, pose_soa, thetas, start_joints, policy, weights, skip_projected, unwind, arm, arm_uniform,
                                 want_elbow, out, plan_only)
+
+    # ------------------------------------------------------------------ rsik_solve_path_pair
+    PATH_PAIR_MAX_THETA = 16
+
+    def solve_path_pair_workspace_bytes(self, n_pairs: int, n_steps: int, n_theta: int) -> int:
+        """rsik_solve_path_pair_workspace_bytes: the device workspace a solve_path_pair of this shape needs."""
+        b = C.c_size_t(0)
+        rc = self.lib.rsik_solve_path_pair_workspace_bytes(int(n_pairs), int(n_steps), int(n_theta), C.byref(b))
+        if rc != _abi.RSIK_OK:
+            raise _abi.RsikError(rc, "rsik_solve_path_pair_workspace_bytes: n_pairs >= 0, n_steps 1 ... 65536, n_theta 1 ... 16")
+        return int(b.value)
+
+    def solve_path_pair(
+        self,
+        pose_soa: torch.Tensor,
+        thetas: torch.Tensor,
+        start_joints: Optional[torch.Tensor] = None,
+        *,
+        spheres: Optional[torch.Tensor] = None,
+        capsules: Optional[torch.Tensor] = None,
+        link_radius: Any = None,
+        min_clearance: float = -float("inf"),
+        influence: float = 0.0,
+        clearance_gain: float = 0.0,
+        policy: str = "fraction",
+        weights: Optional[Sequence[float]] = None,
+        skip_projected: bool = False,
+        unwind: bool = False,
+        want_elbow: bool = True,
+        out: Optional[Dict[str, torch.Tensor]] = None,
+        plan_only: bool = False,
+    ) -> Dict[str, torch.Tensor]:
+        """solve_path_clear() for robots of two arms that keep out of each other, from one launch (rsik_solve_path_pair): the
+        elbow angles of both arms chosen together, a state being a pair of samples (a of the right arm, b of the left).
+        pose_soa: [6, T, n] with n = 2 n_pairs rows, row 2 i the right arm of robot i and row 2 i + 1 its left arm (track_pair()'s
+        rows; there is no arm argument).  thetas: [K] or [K, T, n], K <= 16.  start_joints: [n, 7] or None.  spheres [S, 4],
+        capsules [C, 7] (both may be missing: the partner is always an obstacle), link_radius and every other keyword as in
+        solve_path_clear().
+        A pair whose right arm's clearance() to the static scene and the left arm's three links, or the left arm's to the scene and
+        the right arm's links, is below min_clearance is no candidate; a waypoint without a candidate pair is skipped for both arms.
+        Each view nearer than influence adds clearance_gain (influence - d)^2 to the cost.
+        Returns solve_path_clear()'s dict with index, theta, joints ... [T, n, ...] per row, clearance [T, n] and nearest [T, n, 2]
+        int32 (link, obstacle index: S + C + l is the partner's link l) per view, and per robot cost [n_pairs], n_solved [n_pairs]
+        int32 and blocked [T, n_pairs] int16 (the count of a uint16: pairs of row candidates that are no candidate pair).
+        plan_only=True launches nothing and adds res["launch"], a zero-overhead re-launch callable (see plan())."""
+        if pose_soa.dim() != 3 or pose_soa.shape[0] != 6:
+            raise ValueError("pose_soa must have shape [6, T, n]")
+        code = self._policy_code(policy)
+        t, n = int(pose_soa.shape[1]), int(pose_soa.shape[2])
+        if n % 2:
+            raise ValueError("pose_soa: an even number of rows, row 2 i the right arm of robot i and row 2 i + 1 its left arm")
+        if not 1 <= t <= 65536:
+            raise ValueError("pose_soa: between 1 and 65536 waypoints per path")
+        n_pairs = n // 2
+        pose_soa = self._dev_cols(pose_soa.reshape(6, t * n), 6, t * n, "pose_soa")
+        thetas, k, per_pose = self._theta_grid(thetas, (t, n), "T, n", self.PATH_PAIR_MAX_THETA, "waypoint")
+        if start_joints is not None:
+            start_joints = self._dev_f64(start_joints, (n, 7), "start_joints")
+        scene_keep, scene_args = self._path_scene(spheres, capsules, link_radius, False)
+        w, wp = self._weights7(weights)
+        ws_bytes = self.solve_path_pair_workspace_bytes(n_pairs, t, k)
+        workspace = torch.empty((max(ws_bytes, 1),), dtype=_U8, device=self.device)
+        res = {"index": self._out_buf(out, "index", (t, n), torch.int32), "theta": self._out_buf(out, "theta", (t, n), _F64),
+               "joints": self._out_buf(out, "joints", (t, n, 7), _F64)}
+        if want_elbow:
+            res["elbow"] = self._out_buf(out, "elbow", (t, n, 3), _F64)
+        res["projected"] = self._out_buf(out, "projected", (t, n), _U8)
+        res["step_cost"] = self._out_buf(out, "step_cost", (t, n), _F64)
+        res["cost"] = self._out_buf(out, "cost", (n_pairs,), _F64)
+        res["n_solved"] = self._out_buf(out, "n_solved", (n_pairs,), torch.int32)
+        self._reach_outs(res, out, (t, n))
+        res["clearance"] = self._out_buf(out, "clearance", (t, n), _F64)
+        res["nearest"] = self._out_buf(out, "nearest", (t, n, 2), torch.int32)
+        res["blocked"] = self._out_buf(out, "blocked", (t, n_pairs), torch.int16)
+        cols = self._cols(pose_soa, 6)
+        flags = (_abi.PATH_SKIP_PROJECTED if skip_projected else 0) | (_abi.PATH_UNWIND if unwind else 0)
+        cargs = (n_pairs, t, cols, k, code, _ptr(thetas), int(per_pose), _ptr(start_joints), wp, flags,
+                 *scene_args, float(min_clearance), float(influence), float(clearance_gain), _ptr(workspace), ws_bytes,
+                 _ptr(res["index"]), _ptr(res["theta"]), _ptr(res["joints"]), _ptr(res.get("elbow")), _ptr(res["projected"]),
+                 _ptr(res["step_cost"]), _ptr(res["cost"]), _ptr(res["n_solved"]),
+                 _ptr(res["interval"]), _ptr(res["reachable"]), _ptr(res["state"]),
+                 _ptr(res["clearance"]), _ptr(res["nearest"]), _ptr(res["blocked"]))
+        return self._finish(res, "rsik_solve_path_pair", cargs, plan_only,
+                            (pose_soa, thetas, cols, start_joints, w, workspace) + scene_keep)
 
     # ------------------------------------------------------------------ rsik_reach_map
     REACH_MAP_OUTPUTS = ("count", "state_count", "theta_measure", "mask")

@@ -45,6 +45,7 @@
 #include "rsik_kernel_clearance.hpp"
 #include "rsik_kernel_track_avoid.hpp"
 #include "rsik_kernel_track_pair.hpp"
+#include "rsik_kernel_path_pair.hpp"
 
 // =====================================================================================
 // C ABI
@@ -624,6 +625,93 @@ int rsik_solve_path_clear(rsik_ctx* ctx, int64_t n, int64_t n_steps, const doubl
     if ((rc = launch_begin(ctx, n, &grid, who, rsik::kBlock / 64)) != RSIK_OK) return rc;
     with_int3(launch_form(ctx, K.arms, arm), [&](auto FORM) { with_bool(tip_on_z(ctx, K.arms), [&](auto TIPZ) {
         hipLaunchKernelGGL((rsik::solve_path_kernel<FORM(), TIPZ(), rsik::PathClearArgs>), grid, block, 0, ctx->stream, K); }); });
+    return launch_end(ctx);
+}
+
+// rsik_solve_path_pair's workspace: a backpointer byte per (robot, waypoint, pair of samples), a flag byte per (robot, waypoint) and
+// the two winners of each
+static bool path_pair_workspace_bytes(int64_t n_pairs, int64_t n_steps, int n_theta, size_t* bytes) {
+    if (n_pairs < 0 || n_pairs > 0x3fffffffffffffffLL || n_steps < 1 || n_steps > 65536 || n_theta < 1 || n_theta > rsik::kPairMaxTheta) return false;
+    const unsigned __int128 b = (unsigned __int128)n_pairs * (unsigned __int128)n_steps * (unsigned)(n_theta * n_theta + 3);
+    if (b > (unsigned __int128)SIZE_MAX) return false;
+    *bytes = (size_t)b;
+    return true;
+}
+int rsik_solve_path_pair_workspace_bytes(int64_t n_pairs, int64_t n_steps, int n_theta, size_t* bytes) {
+    if (!bytes || !path_pair_workspace_bytes(n_pairs, n_steps, n_theta, bytes)) return RSIK_E_INVALID;
+    return RSIK_OK;
+}
+
+// rsik_solve_path_pair: rsik_solve_path_clear for robots of two arms, each arm an obstacle to the other; a state is a pair of samples
+// (solve_path_pair_kernel, rsik_kernel_path_pair.hpp).  The checks are rsik_solve_path_clear's in its order, without "no obstacle".
+int rsik_solve_path_pair(rsik_ctx* ctx, int64_t n_pairs, int64_t n_steps, const double* const pose_soa[6],
+                         int n_theta, int theta_policy, const double* theta_in, int theta_per_pose,
+                         const double* start_joints, const double* weights_host, int flags,
+                         const double* link_radius_host, int n_spheres, const double* spheres, int n_capsules, const double* capsules,
+                         double min_clearance, double influence, double clearance_gain,
+                         void* workspace, size_t workspace_bytes,
+                         int32_t* index, double* theta, double* joints, double* elbow, uint8_t* projected,
+                         double* step_cost, double* cost, int32_t* n_solved,
+                         double* interval, uint8_t* reachable, uint8_t* state,
+                         double* clearance, int32_t* nearest, uint16_t* blocked) {
+    if (!ctx) return RSIK_E_INVALID;
+    const char* who = "rsik_solve_path_pair";
+    const std::string w(who);
+    const auto gain_ok = [](double g) { return std::isfinite(g) && g >= 0.0; };
+    if (n_pairs < 0) return fail(ctx, RSIK_E_INVALID, w + ": n_pairs < 0");
+    if (n_pairs > 0x3fffffffffffffffLL) return fail(ctx, RSIK_E_INVALID, w + ": n too large for one launch");
+    if (n_steps < 1 || n_steps > 65536) return fail(ctx, RSIK_E_INVALID, w + ": n_steps must be in [1, 65536]");
+    if (n_theta < 1 || n_theta > rsik::kPairMaxTheta) return fail(ctx, RSIK_E_INVALID, w + ": n_theta must be in [1, 16]");
+    if (theta_policy != RSIK_THETA_EXPLICIT && theta_policy != RSIK_THETA_FRACTION)
+        return fail(ctx, RSIK_E_INVALID, w + ": theta_policy must be RSIK_THETA_EXPLICIT or RSIK_THETA_FRACTION");
+    if (flags & ~(RSIK_PATH_SKIP_PROJECTED | RSIK_PATH_UNWIND)) return fail(ctx, RSIK_E_INVALID, w + ": unknown bits in flags");
+    for (int q = 0; weights_host && q < 7; q++)
+        if (!(weights_host[q] >= 0.0 && std::isfinite(weights_host[q]))) return fail(ctx, RSIK_E_INVALID, w + ": every weight must be finite and >= 0");
+    if (!ctx->have_arm[RSIK_ARM_R] || !ctx->have_arm[RSIK_ARM_L])
+        return fail(ctx, RSIK_E_NOT_SET, w + ": both arms' constants are needed (rsik_set_arm)");
+    if (n_spheres < 0 || n_spheres > rsik::kAvoidMaxSpheres) return fail(ctx, RSIK_E_INVALID, w + ": n_spheres must be 0 ... 256");
+    if (n_capsules < 0 || n_capsules > rsik::kAvoidMaxCapsules) return fail(ctx, RSIK_E_INVALID, w + ": n_capsules must be 0 ... 64");
+    for (int l = 0; link_radius_host && l < 3; l++)
+        if (!gain_ok(link_radius_host[l])) return fail(ctx, RSIK_E_INVALID, w + ": every link radius must be finite and >= 0");
+    if (!gain_ok(influence) || !gain_ok(clearance_gain))
+        return fail(ctx, RSIK_E_INVALID, w + ": influence and clearance_gain must be finite and >= 0");
+    if (!(min_clearance < __builtin_inf()))  // (a NaN fails it too)
+        return fail(ctx, RSIK_E_INVALID, w + ": min_clearance must be finite or -infinity");
+    if (n_pairs == 0) return RSIK_OK;
+    int rc = check_sample_inputs(ctx, who, pose_soa, theta_in);
+    if (rc != RSIK_OK) return rc;
+    if (!index && !theta && !joints) return fail(ctx, RSIK_E_INVALID, w + ": index, theta and joints are all NULL");
+    size_t need = 0;
+    if (!path_pair_workspace_bytes(n_pairs, n_steps, n_theta, &need)) return fail(ctx, RSIK_E_INVALID, w + ": n_pairs * n_steps too large");
+    if (!workspace || workspace_bytes < need)
+        return fail(ctx, RSIK_E_INVALID, w + ": workspace is NULL or smaller than rsik_solve_path_pair_workspace_bytes");
+    if ((n_spheres > 0 && !spheres) || (n_capsules > 0 && !capsules))
+        return fail(ctx, RSIK_E_INVALID, w + ": spheres or capsules is NULL with a count above 0");
+    if (((uintptr_t)nearest & 7) != 0) return fail(ctx, RSIK_E_INVALID, w + ": nearest must be aligned to 8 bytes");
+    const int64_t n = 2 * n_pairs;  // rows: 2i the right arm of robot i, 2i + 1 its left arm
+    rsik::PathPairArgs K;  // (K.arm stays NULL: the arm of a row is its parity)
+    K.n = n;
+    if ((rc = copy_cols(ctx, who, "pose_soa", "a pose_soa column", pose_soa, K.in, 6)) != RSIK_OK) return rc;
+    K.n_steps = n_steps; K.arm = nullptr;
+    K.theta_policy = theta_policy; K.n_theta = n_theta; K.theta_per_pose = theta_per_pose != 0; K.theta_in = theta_in;
+    K.skip_projected = (flags & RSIK_PATH_SKIP_PROJECTED) != 0;
+    K.unwind = (flags & RSIK_PATH_UNWIND) != 0;
+    fill7(K.prev, nullptr, 0.0);
+    K.start = start_joints;
+    fill7(K.weights, weights_host, 1.0);
+    K.back = static_cast<uint8_t*>(workspace);
+    K.index = index; K.theta = theta; K.joints = joints; K.elbow = elbow; K.projected = projected;
+    K.step_cost = step_cost; K.cost = cost; K.n_solved = n_solved;
+    K.interval = interval; K.reachable = reachable; K.state = state;
+    K.spheres = spheres; K.capsules = capsules; K.n_spheres = n_spheres; K.n_capsules = n_capsules;
+    K.clearance = clearance; K.nearest = nearest; K.blocked = blocked;
+    K.min_clearance = min_clearance; K.influence = influence; K.clearance_gain = clearance_gain;
+    for (int l = 0; l < 3; l++) K.link_radius[l] = link_radius_host ? link_radius_host[l] : 0.0;
+    K.arms[0] = ctx->arms[RSIK_ARM_R]; K.arms[1] = ctx->arms[RSIK_ARM_L];
+    dim3 grid, block(rsik::kBlock);
+    if ((rc = launch_begin(ctx, n_pairs, &grid, who, rsik::kBlock / 64)) != RSIK_OK) return rc;
+    with_bool(tip_on_z(ctx, K.arms), [&](auto TIPZ) {
+        hipLaunchKernelGGL((rsik::solve_path_pair_kernel<TIPZ()>), grid, block, 0, ctx->stream, K); });
     return launch_end(ctx);
 }
 

@@ -874,6 +874,43 @@ class DualArmIK:
                 split[name] = {"r": x[:, 0::2], "l": x[:, 1::2]}
         return split
 
+    def path_pair_batch(self, poses_r: Any, poses_l: Any, start_r: Any = None, start_l: Any = None, spheres: Any = None,
+                        capsules: Any = None, link_radius: Any = None, min_clearance: float = -float("inf"), influence: float = 0.0,
+                        clearance_gain: float = 0.0, n_theta: int = 8, thetas: Any = None, policy: str = "fraction",
+                        weights: Optional[Sequence[float]] = None, skip_projected: bool = False, unwind: bool = False,
+                        want_elbow: bool = True, out: Optional[Dict[str, torch.Tensor]] = None,
+                        plan_only: bool = False) -> Dict[str, Any]:
+        """The elbow angles of both arms of n_pairs robots along two hand paths, chosen together in one launch so that the arms keep
+        out of each other (HipSolver.solve_path_pair, rsik_solve_path_pair): path_clear_batch in which every arm has, beside the
+        static spheres [S,4] and capsules [Cp,7] (none at all is allowed), the other arm's three links as obstacles, at the sample
+        that arm takes at the same waypoint.  A pair of samples nearer than min_clearance in either arm's view is excluded, one
+        nearer than influence is charged clearance_gain (influence - d)^2 per view; n_theta <= 16 samples per arm and waypoint.
+        poses_r, poses_l: [T,n_pairs,2,3] or SoA [6,T,n_pairs], per arm; start_r, start_l: [n_pairs,7] or None.  They are
+        interleaved (row 2 i the right arm of robot i, row 2 i + 1 its left arm).  With poses_l = None, poses_r and start_r are
+        taken as already interleaved arrays of 2 n_pairs rows.
+        Returns index, theta, joints, elbow, projected, step_cost, interval, reachable, state, clearance and nearest [T,n_pairs,2]
+        int32 (link, obstacle index: S + Cp + l is the partner's link l), each as {"r": ..., "l": ...}, two strided views of the
+        launch's interleaved tensor, which `out` takes as HipSolver.solve_path_pair does; and per robot cost [n_pairs], n_solved
+        [n_pairs] and blocked [T,n_pairs] (the pairs of samples the clearance excludes).  plan_only adds "launch"."""
+        dev = self._solver.device
+        if poses_l is None:
+            if start_l is not None:
+                raise ValueError("poses_l and start_l: both per arm, or both None for interleaved poses_r and start_r")
+            soa, start = _path_soa(poses_r, dev), start_r
+        else:
+            if (start_r is None) != (start_l is None):
+                raise ValueError("start_r and start_l: both or neither")
+            soa = _interleave(_path_soa(poses_r, dev), _path_soa(poses_l, dev), 2, dev)
+            start = None if start_r is None else _interleave(start_r, start_l, 0, dev)
+        thetas = _default_grid(thetas, n_theta, 0.5)
+        self._upload()
+        res = self._solver.solve_path_pair(soa, thetas, start, spheres=spheres, capsules=capsules, link_radius=link_radius,
+                                           min_clearance=min_clearance, influence=influence, clearance_gain=clearance_gain,
+                                           policy=policy, weights=weights, skip_projected=skip_projected, unwind=unwind,
+                                           want_elbow=want_elbow, out=out, plan_only=plan_only)
+        per_robot = ("cost", "n_solved", "blocked", "launch", "_keepalive")
+        return {name: x if name in per_robot else {"r": x[:, 0::2], "l": x[:, 1::2]} for name, x in res.items()}
+
     def clearance_batch(self, arm_ids: Any, joints: Any, spheres: Any = None, capsules: Any = None, link_radius: Any = None,
                         other_arm: Optional[Tuple[int, Any]] = None, want: Sequence[str] = ("clearance", "nearest"),
                         out: Optional[Dict[str, torch.Tensor]] = None, plan_only: bool = False) -> Dict[str, torch.Tensor]:
