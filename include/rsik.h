@@ -1238,6 +1238,85 @@ int rsik_track_pair(rsik_ctx *ctx, int64_t n_pairs, int64_t n_steps, const doubl
                     double *final_joints, double *final_err, double *min_clearance);
 
 /*
+ * rsik_clearance_edges — the clearance of a path ALONG the motion between its waypoints: rsik_solve_path_clear and rsik_solve_path_pair
+ * keep min_clearance at the waypoints only, and say nothing of the way from one winner to the next.  That motion is the one their
+ * transition cost assumes: joint by joint, the short way round (angle_diff).  One call takes a path's joints in place, samples every
+ * edge at n_sub + 1 sub-steps and returns, per edge, the least clearance, where it lies, the pair that gives it and a certified lower
+ * bound on the clearance of the whole continuous motion; per path, the minima of these.  What a caller otherwise composes from an
+ * interpolation of its own, rsik_clearance with n_rep = n_sub + 1 over (n_sub + 1) * n_steps * n rows, and two reductions.  Added
+ * within ABI version 8: two new symbols, no new option, nothing else changed.  The reference has nothing of the kind.
+ *
+ *   joints           [n_steps][n][7] device, waypoint-major: the `joints` output of rsik_solve_path, rsik_solve_path_clear or
+ *                    rsik_solve_path_pair (rows 2 i, 2 i + 1 are paths of their own here), with or without RSIK_PATH_UNWIND, or
+ *                    joints_steps of the track calls.  n >= 0, n_steps 1 ... 65536.
+ *   arm / arm_uniform   [n], one byte per path, or NULL and the one arm: as rsik_solve_path
+ *   start_joints     [n][7] device or NULL: the joints each path starts from
+ *   n_sub            S, 1 ... 256: the sub-steps of an edge
+ *   link_radius_host, n_spheres, spheres, n_capsules, capsules
+ *                    as rsik_solve_path_clear: 0 ... 256 spheres and 0 ... 64 capsules, at least one obstacle, 3 radii on the host or
+ *                    NULL for zeros.  An obstacle row with a NaN, an infinity or a negative radius is skipped.
+ *   min_clearance    m, finite, or -infinity for none: it feeds n_below and first_below, nothing else
+ *   workspace        device, aligned to 8 bytes, at least rsik_clearance_edges_workspace_bytes(n, n_steps) bytes: needed only when one
+ *                    of the five per-path outputs is asked for; otherwise it may be NULL
+ *
+ * Definition, independent of the kernel's layout:
+ *   Waypoints and edges.  A row of `joints` with a NaN or an infinity is NOT A WAYPOINT: this is how the path calls mark a skipped
+ *   one.  The edge INTO waypoint (t, i) starts at a, the last waypoint of path i before t, or start_joints[i] for the path's first
+ *   waypoint, and ends at b = row (t, i): step_cost's rule.  The first waypoint of a path without start_joints has the one-sample edge
+ *   {b}, numbered s = S.
+ *   Samples.  delta_k = angle_diff(b_k, a_k), the value RSIK_STAGE_ANGLE_DIFF returns.  Sample s has q_k(s) = a_k + delta_k * (s / S)
+ *   for s = 0 ... S - 1: s / S is one division, then a product, then a sum, unfused.  q(S) = b itself (a select: both ends of an edge
+ *   are the rows as given).  d(s) and its (link, obstacle) are, bit for bit, what rsik_clearance returns for q(s): the same arm, radii
+ *   and obstacles, the same order of the pairs, the first minimum, finite angles of any size.
+ * Per edge, [n_steps][n], any of them NULL:
+ *   edge_clearance   the minimum over s of d(s)
+ *   edge_sub         int32: the lowest s that attains it
+ *   edge_nearest     [n_steps][n][2] int32, aligned to 8 bytes: (link, obstacle index) of that sample
+ *   edge_bound       edge_clearance - 0.5 * (acc / S), with acc = sum over k of |delta_k| * R_k, k = 0 ... 6 in this order, unfused,
+ *                    R_0 = R_1 = u + f + |tip|, R_2 = R_3 = f + |tip|, R_4 = R_5 = R_6 = |tip|; u = RSIK_C_UPPER_ARM, f =
+ *                    RSIK_C_FOREARM, |tip| the length of RSIK_C_TIPL, of the path's arm.  acc = 0 for a one-sample edge.
+ *   Where row t is not a waypoint: NaN, -1, (-1, -1), NaN.  Where every obstacle is skipped: +infinity, the edge's first s, (-1, -1),
+ *   +infinity.
+ * Why edge_bound is a lower bound.  Joint k turns every point beyond it about an axis through its origin — joints 0, 1 at the
+ * shoulder, 2, 3 at the elbow, 4 - 6 at the wrist — and no point of the arm's axis (shoulder - elbow - wrist - goal origin) is
+ * further from that origin than R_k.  Between two neighbouring samples joint k turns by |delta_k| / S, so no point of the axis moves
+ * more than acc / S, and every configuration between them is within acc / (2 S) of the nearer sample.  The distance between a point
+ * set and the obstacles is 1-Lipschitz in that displacement.  Hence the clearance of the continuous motion is never below edge_bound,
+ * up to the rounding of d and of the bound's own few operations.  An edge_bound above 0 proves the edge free; one below 0 with an
+ * edge_clearance above 0 asks for a finer n_sub.
+ * Per path, [n], any of them NULL:
+ *   path_clearance   the minimum of edge_clearance over the path's edges
+ *   path_edge        [n][2] int32, aligned to 8 bytes: (t, s) of that minimum, the lowest t among equal values
+ *   path_bound       the minimum of edge_bound
+ *   n_below          int32: the edges with edge_clearance < min_clearance
+ *   first_below      int32: the lowest such t, or -1
+ *   A path without a waypoint: NaN, (-1, -1), NaN, 0, -1.
+ * A start_joints row that holds a NaN or an infinity loses its own path, as in rsik_solve_path: every edge output of the path is as
+ * for "not a waypoint", its path outputs as for a path without one.  It changes no other path.
+ *
+ * Guarantees: any output may be NULL, all nine NULL is RSIK_E_INVALID.  Any subset of the outputs gives the same bits, and two
+ * launches give the same bits.  A path's bits depend neither on n, nor on its place in the launch, nor on the other paths.
+ * edge_clearance and the bounds do not depend on the order of the obstacles; edge_nearest's obstacle index does.
+ *
+ * RSIK_E_INVALID, nothing written: n < 0; n_steps or n_sub outside its range; a count outside its range, or no obstacle; a link
+ * radius that is negative or not finite; a min_clearance that is a NaN or +infinity; then, for n > 0: joints == NULL or all nine
+ * outputs NULL; a NULL obstacle array with a count above 0; an edge_nearest or path_edge that is not aligned to 8 bytes; with a
+ * per-path output, a workspace that is NULL, too small or not aligned to 8 bytes.  The arm checks and their codes are rsik_jacobian's
+ * (RSIK_E_NOT_SET included).  rsik_clearance_edges_workspace_bytes refuses n < 0, n_steps outside its range, bytes == NULL and a
+ * product that does not fit; it grows with n and with n_steps.
+ * n == 0 launches nothing.  Enqueued on the context's stream — the per-edge kernel, then, where a per-path output is asked for, a
+ * second small one behind it —; allocates nothing and never waits for the device.
+ */
+int rsik_clearance_edges_workspace_bytes(int64_t n, int64_t n_steps, size_t *bytes);
+int rsik_clearance_edges(rsik_ctx *ctx, int64_t n, int64_t n_steps, const double *joints,
+                         const uint8_t *arm, int arm_uniform, const double *start_joints, int n_sub,
+                         const double *link_radius_host,
+                         int n_spheres, const double *spheres, int n_capsules, const double *capsules,
+                         double min_clearance, void *workspace, size_t workspace_bytes,
+                         double *edge_clearance, int32_t *edge_sub, int32_t *edge_nearest, double *edge_bound,
+                         double *path_clearance, int32_t *path_edge, double *path_bound, int32_t *n_below, int32_t *first_below);
+
+/*
  * Multi-GPU.  Poses are independent, so a job is sharded across the GPUs of a node — one process and one
  * rsik context per GPU — with no data-path collective; the only exchange is the all-gather of the final arrays
  * (joints [n,7], state [n]) over RCCL / xGMI.  The reference has nothing distributed (single-threaded Python).  Python

@@ -99,6 +99,9 @@ PROTOTYPES = {
                                   _vp, C.c_double, _dp, _dp, C.c_int, _vp, C.c_int, _vp, C.c_double, C.c_double,
                                   _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rsik_clearance": (C.c_int, [_vp, C.c_int64, C.c_int64, _vp, _vp, C.c_int, _dp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rsik_clearance_edges_workspace_bytes": (C.c_int, [C.c_int64, C.c_int64, C.POINTER(C.c_size_t)]),
+    "rsik_clearance_edges": (C.c_int, [_vp, C.c_int64, C.c_int64, _vp, _vp, C.c_int, _vp, C.c_int, _dp, C.c_int, _vp, C.c_int, _vp,
+                                       C.c_double, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rsik_theta_from_joints": (C.c_int, [_vp, C.c_int64, C.c_int, C.POINTER(_vp), _vp, C.c_int, _vp, _dp, _vp, _vp, _vp, _vp, _vp]),
     "rsik_theta_from_joints_state": (C.c_int, [_vp, C.c_int64, _vp, _vp, C.c_int, _vp, C.c_int, _dp, _vp, _vp]),
     "rsik_debug_math": (C.c_int, [_vp, C.c_int, C.c_int64, _vp, _vp, _vp, _vp]),

@@ -1416,6 +1416,85 @@ class HipSolver:
             + tuple(_ptr(res.get(name)) for name in self.CLEARANCE_OUTPUTS)
         return self._finish(res, "rsik_clearance", cargs, plan_only, (joints, arm, spheres, capsules, rad))
 
+    # ------------------------------------------------------------------ rsik_clearance_edges
+    CLEARANCE_EDGES_OUTPUTS = ("edge_clearance", "edge_sub", "edge_nearest", "edge_bound",
+                               "path_clearance", "path_edge", "path_bound", "n_below", "first_below")
+    CLEARANCE_EDGES_MAX_SUB = 256
+
+    def clearance_edges_workspace_bytes(self, n: int, n_steps: int) -> int:
+        """rsik_clearance_edges_workspace_bytes: the device workspace the per-path outputs of a clearance_edges of this shape need."""
+        b = C.c_size_t(0)
+        rc = self.lib.rsik_clearance_edges_workspace_bytes(int(n), int(n_steps), C.byref(b))
+        if rc != _abi.RSIK_OK:
+            raise _abi.RsikError(rc, "rsik_clearance_edges_workspace_bytes: n >= 0, n_steps 1 ... 65536")
+        return int(b.value)
+
+    def clearance_edges(
+        self,
+        joints: torch.Tensor,
+        start_joints: Optional[torch.Tensor] = None,
+        n_sub: int = 16,
+        *,
+        spheres: Optional[torch.Tensor] = None,
+        capsules: Optional[torch.Tensor] = None,
+        link_radius: Any = None,
+        arm: Optional[torch.Tensor] = None,
+        arm_uniform: int = 0,
+        min_clearance: float = -float("inf"),
+        want: Sequence[str] = CLEARANCE_EDGES_OUTPUTS,
+        out: Optional[Dict[str, torch.Tensor]] = None,
+        plan_only: bool = False,
+    ) -> Dict[str, torch.Tensor]:
+        """The clearance of n paths ALONG the motion between their waypoints, from one call (rsik_clearance_edges): solve_path_clear()
+        and solve_path_pair() keep min_clearance at the waypoints only; this verifies the way between them.
+        joints: [T, n, 7], waypoint-major, the `joints` of solve_path(), solve_path_clear() or solve_path_pair() (with or without
+        unwind) or joints_steps of the track calls, in place; a row with a NaN or an infinity is not a waypoint (a skipped one) and
+        the edge bridges it.  start_joints: [n, 7] or None.  n_sub: S, 1 ... 256 sub-steps per edge.  spheres [k, 4], k <= 256,
+        capsules [k, 7], k <= 64, link_radius: solve_path_clear()'s scene, at least one obstacle.  arm: [n], one byte per path.
+        The edge into waypoint (t, i) runs from the waypoint before it (or the start row) joint by joint the short way round:
+        q(s) = a + angle_diff(b, a) * (s / S), s = 0 ... S, q(S) = b; a first waypoint without a start row is the one sample s = S.
+        `want`: which of CLEARANCE_EDGES_OUTPUTS to compute, at least one; the bits of one do not depend on the others.  Returns
+        device tensors:
+        edge_clearance [T, n]: the least clearance()'s `clearance` over the samples; edge_sub [T, n] int32: the lowest s that attains
+        it; edge_nearest [T, n, 2] int32: that sample's (link, obstacle index);
+        edge_bound [T, n]: edge_clearance - sum_k |delta_k| R_k / (2 S), R_k the arm's reach beyond joint k — a certified lower bound
+        on the clearance of the whole continuous motion of the edge (include/rsik.h derives it): edge_bound > 0 proves the edge free;
+        NaN, -1, (-1, -1), NaN where row t is not a waypoint; +inf, the first s, (-1, -1), +inf where every obstacle is skipped;
+        path_clearance [n], path_edge [n, 2] int32 (t, s) of it, path_bound [n]: the minima over a path's edges; n_below [n] int32:
+        the edges with edge_clearance < min_clearance (m; -inf: none), first_below [n] int32: the first such t or -1.  A path
+        without a waypoint, or whose start row is not numbers: NaN, (-1, -1), NaN, 0, -1.
+        The workspace the per-path outputs need is allocated here, with torch; a plan keeps it and the obstacle tensors alive.
+        plan_only=True launches nothing and adds res["launch"], a zero-overhead re-launch callable (see plan())."""
+        if not isinstance(joints, torch.Tensor):
+            joints = torch.as_tensor(np.asarray(joints, dtype=np.float64))
+        if joints.dim() != 3 or joints.shape[-1] != 7:
+            raise ValueError("joints must have shape [T, n, 7]")
+        t, n = int(joints.shape[0]), int(joints.shape[1])
+        if not 1 <= t <= 65536:
+            raise ValueError("joints: between 1 and 65536 waypoints per path")
+        n_sub = int(n_sub)
+        if not 1 <= n_sub <= self.CLEARANCE_EDGES_MAX_SUB:
+            raise ValueError(f"n_sub must be 1 ... {self.CLEARANCE_EDGES_MAX_SUB}")
+        want = tuple(want)
+        if not want or any(name not in self.CLEARANCE_EDGES_OUTPUTS for name in want):
+            raise ValueError(f"want must name at least one of {self.CLEARANCE_EDGES_OUTPUTS}")
+        keep, scene_args = self._path_scene(spheres, capsules, link_radius, True)
+        joints = self._dev_f64(joints, (t, n, 7), "joints")
+        if start_joints is not None:
+            start_joints = self._dev_f64(start_joints, (n, 7), "start_joints")
+        arm = self._arm_ids(arm, n)
+        shapes = {"edge_clearance": ((t, n), _F64), "edge_sub": ((t, n), torch.int32), "edge_nearest": ((t, n, 2), torch.int32),
+                  "edge_bound": ((t, n), _F64), "path_clearance": ((n,), _F64), "path_edge": ((n, 2), torch.int32),
+                  "path_bound": ((n,), _F64), "n_below": ((n,), torch.int32), "first_below": ((n,), torch.int32)}
+        res = {name: self._out_buf(out, name, *shapes[name]) for name in self.CLEARANCE_EDGES_OUTPUTS if name in want}
+        workspace, ws_bytes = None, 0
+        if any(name in want for name in self.CLEARANCE_EDGES_OUTPUTS[4:]):
+            ws_bytes = self.clearance_edges_workspace_bytes(n, t)
+            workspace = torch.empty((max(ws_bytes, 8) // 8,), dtype=_F64, device=self.device)
+        cargs = (n, t, _ptr(joints), _ptr(arm), int(arm_uniform), _ptr(start_joints), n_sub) + scene_args \
+            + (float(min_clearance), _ptr(workspace), ws_bytes) + tuple(_ptr(res.get(name)) for name in self.CLEARANCE_EDGES_OUTPUTS)
+        return self._finish(res, "rsik_clearance_edges", cargs, plan_only, (joints, start_joints, arm, workspace) + keep)
+
     # ------------------------------------------------------------------ measurement hooks
     def clock_monitor(self, seconds: float, n_waves: int = 64, stream: Optional[torch.cuda.Stream] = None):
         """Starts rsik_debug_math op 8 on `stream` (a side stream, so that it runs BESIDE whatever the main stream is

@@ -46,6 +46,7 @@
 #include "rsik_kernel_track_avoid.hpp"
 #include "rsik_kernel_track_pair.hpp"
 #include "rsik_kernel_path_pair.hpp"
+#include "rsik_kernel_clearance_edges.hpp"
 
 // =====================================================================================
 // C ABI
@@ -1424,6 +1425,102 @@ int rsik_clearance(rsik_ctx* ctx, int64_t n, int64_t n_rep, const double* joints
         K.link_points = link_points ? link_points + first * 12 : nullptr;
         with_bool(arm != nullptr, [&](auto MIXED) { with_bool(gradient != nullptr || witness != nullptr, [&](auto WIT) {
             hipLaunchKernelGGL((rsik::clearance_kernel<MIXED(), WIT()>), grid, block, 0, ctx->stream, K); }); });
+    }
+    return launch_end(ctx);
+}
+
+// rsik_clearance_edges' workspace: what the per-path fold reads of every edge — its clearance, its bound (doubles) and its sub-step
+// (int32), [n_steps][n] each, the total a multiple of 8 bytes
+static bool clearance_edges_workspace_bytes(int64_t n, int64_t n_steps, size_t* bytes) {
+    if (n < 0 || n_steps < 1 || n_steps > 65536) return false;
+    const unsigned __int128 b = (unsigned __int128)n * (unsigned __int128)n_steps * 20u + 4u;
+    if (b > (unsigned __int128)(SIZE_MAX / 2)) return false;
+    *bytes = (size_t)b & ~(size_t)7;
+    return true;
+}
+int rsik_clearance_edges_workspace_bytes(int64_t n, int64_t n_steps, size_t* bytes) {
+    if (!bytes || !clearance_edges_workspace_bytes(n, n_steps, bytes)) return RSIK_E_INVALID;
+    return RSIK_OK;
+}
+
+// rsik_clearance_edges: the clearance along the motion between a path's waypoints (rsik_kernel_clearance_edges.hpp).  The scene's
+// limits and checks are rsik_solve_path_clear's, the arm checks rsik_jacobian's.
+int rsik_clearance_edges(rsik_ctx* ctx, int64_t n, int64_t n_steps, const double* joints, const uint8_t* arm, int arm_uniform,
+                         const double* start_joints, int n_sub,
+                         const double* link_radius_host, int n_spheres, const double* spheres, int n_capsules, const double* capsules,
+                         double min_clearance, void* workspace, size_t workspace_bytes,
+                         double* edge_clearance, int32_t* edge_sub, int32_t* edge_nearest, double* edge_bound,
+                         double* path_clearance, int32_t* path_edge, double* path_bound, int32_t* n_below, int32_t* first_below) {
+    if (!ctx) return RSIK_E_INVALID;
+    const char* who = "rsik_clearance_edges";
+    const std::string w(who);
+    if (n < 0) return fail(ctx, RSIK_E_INVALID, w + ": n < 0");
+    if (n_steps < 1 || n_steps > 65536) return fail(ctx, RSIK_E_INVALID, w + ": n_steps must be 1 ... 65536");
+    if (n_sub < 1 || n_sub > 256) return fail(ctx, RSIK_E_INVALID, w + ": n_sub must be 1 ... 256");
+    if (n_spheres < 0 || n_spheres > rsik::kAvoidMaxSpheres) return fail(ctx, RSIK_E_INVALID, w + ": n_spheres must be 0 ... 256");
+    if (n_capsules < 0 || n_capsules > rsik::kAvoidMaxCapsules) return fail(ctx, RSIK_E_INVALID, w + ": n_capsules must be 0 ... 64");
+    if (n_spheres + n_capsules < 1) return fail(ctx, RSIK_E_INVALID, w + ": at least one obstacle");
+    for (int l = 0; link_radius_host && l < 3; l++)
+        if (!(std::isfinite(link_radius_host[l]) && link_radius_host[l] >= 0.0))
+            return fail(ctx, RSIK_E_INVALID, w + ": every link radius must be finite and >= 0");
+    if (!(min_clearance < __builtin_inf()))  // (a NaN fails it too)
+        return fail(ctx, RSIK_E_INVALID, w + ": min_clearance must be finite or -infinity");
+    if (n == 0) return RSIK_OK;
+    const bool any_edge = edge_clearance || edge_sub || edge_nearest || edge_bound;
+    const bool any_path = path_clearance || path_edge || path_bound || n_below || first_below;
+    if (!joints || !(any_edge || any_path)) return fail(ctx, RSIK_E_INVALID, w + ": joints or all nine outputs are NULL");
+    if ((n_spheres > 0 && !spheres) || (n_capsules > 0 && !capsules))
+        return fail(ctx, RSIK_E_INVALID, w + ": spheres or capsules is NULL with a count above 0");
+    if ((((uintptr_t)edge_nearest | (uintptr_t)path_edge) & 7) != 0)
+        return fail(ctx, RSIK_E_INVALID, w + ": edge_nearest and path_edge must be aligned to 8 bytes");
+    size_t need = 0;
+    if (!clearance_edges_workspace_bytes(n, n_steps, &need)) return fail(ctx, RSIK_E_INVALID, w + ": n * n_steps too large");
+    if (any_path && (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 7) != 0))
+        return fail(ctx, RSIK_E_INVALID, w + ": a path output needs a workspace of rsik_clearance_edges_workspace_bytes, aligned to 8 bytes");
+    int rc = check_arms(ctx, arm, arm_uniform, who);
+    if (rc != RSIK_OK) return rc;
+    rsik::ClearanceEdgesArgs K;
+    std::memset(&K, 0, sizeof K);
+    const int64_t edges = n * n_steps;
+    K.n = n; K.n_steps = n_steps; K.joints = joints; K.arm = arm; K.start = start_joints;
+    K.spheres = spheres; K.capsules = capsules; K.n_spheres = n_spheres; K.n_capsules = n_capsules;
+    K.edge_clearance = edge_clearance; K.edge_sub = edge_sub; K.edge_nearest = edge_nearest; K.edge_bound = edge_bound;
+    if (any_path) {
+        K.ws_clearance = static_cast<double*>(workspace);
+        K.ws_bound = K.ws_clearance + edges;
+        K.ws_sub = reinterpret_cast<int32_t*>(K.ws_bound + edges);
+    }
+    K.path_clearance = path_clearance; K.path_edge = path_edge; K.path_bound = path_bound; K.n_below = n_below; K.first_below = first_below;
+    K.n_sub = n_sub; K.min_clearance = min_clearance;
+    for (int l = 0; l < 3; l++) K.link_radius[l] = link_radius_host ? link_radius_host[l] : 0.0;
+    bind_arms(ctx, arm, arm_uniform, K.arms);
+    for (int slot = 0; slot < 2; slot++) {  // how far one radian of a joint can move a point of the arm's axis (rsik.h)
+        const double* c = K.arms[slot].v;
+        const double tip = std::sqrt(c[RSIK_C_TIPL] * c[RSIK_C_TIPL] + c[RSIK_C_TIPL + 1] * c[RSIK_C_TIPL + 1] + c[RSIK_C_TIPL + 2] * c[RSIK_C_TIPL + 2]);
+        K.sweep[slot][0] = c[RSIK_C_UPPER_ARM] + c[RSIK_C_FOREARM] + tip;
+        K.sweep[slot][1] = c[RSIK_C_FOREARM] + tip;
+        K.sweep[slot][2] = tip;
+    }
+    // Lanes per edge: as many as keep the launch within what is resident at once (one round of workgroups, no tail), and no more
+    // than an edge has samples; one lane per edge beyond that, the workgroups striding over the edges.  The fold: as many lanes per
+    // path as it has waypoints, while the paths alone do not fill the device.
+    const int64_t resident = (int64_t)ctx->compute_units * rsik::kEdgeBlocksPerCu;
+    int lanes = 1;
+    while (lanes < 64 && lanes < n_sub + 1 && edges * lanes * 2 <= resident * rsik::kBlock) lanes *= 2;
+    K.lanes = lanes;
+    int fold_lanes = 1;
+    while (fold_lanes < 64 && fold_lanes < n_steps && n * fold_lanes < resident * rsik::kBlock) fold_lanes *= 2;
+    K.fold_lanes = fold_lanes;
+    const int64_t groups = rsik::kBlock / lanes;
+    const int64_t blocks = std::min<int64_t>((edges + groups - 1) / groups, resident);
+    dim3 grid, block(rsik::kBlock);
+    if ((rc = launch_begin(ctx, blocks * rsik::kBlock, &grid, who)) != RSIK_OK) return rc;
+    with_bool(arm != nullptr, [&](auto MIXED) {
+        hipLaunchKernelGGL((rsik::clearance_edges_kernel<MIXED()>), grid, block, 0, ctx->stream, K); });
+    if (any_path) {
+        if (n > INT64_MAX / 64) return fail(ctx, RSIK_E_INVALID, w + ": n too large for one launch");
+        if ((rc = launch_dims(ctx, n * fold_lanes, &grid, who)) != RSIK_OK) return rc;
+        hipLaunchKernelGGL(rsik::clearance_edges_fold_kernel, grid, block, 0, ctx->stream, K);
     }
     return launch_end(ctx);
 }

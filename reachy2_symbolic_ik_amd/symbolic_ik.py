@@ -540,6 +540,22 @@ class SymbolicIK:
         joints that is not numbers is NaN with nearest (-1, -1); an obstacle that is not numbers or has a negative radius is skipped."""
         return _clearance_batch(self, {"arm_uniform": self.arm_id}, joints, spheres, capsules, link_radius, want, out, plan_only)
 
+    def clearance_edges_batch(self, joints: Any, start_joints: Any = None, n_sub: int = 16, spheres: Any = None, capsules: Any = None,
+                              link_radius: Any = None, min_clearance: float = -float("inf"), want: Optional[Sequence[str]] = None,
+                              out: Optional[Dict[str, torch.Tensor]] = None, plan_only: bool = False) -> Dict[str, torch.Tensor]:
+        """The clearance of this arm ALONG the motion between the waypoints of n paths, in one call (HipSolver.clearance_edges,
+        rsik_clearance_edges): path_clear_batch keeps min_clearance at the waypoints only.  joints: [T,n,7] as path_batch and
+        path_clear_batch return them (in place; a NaN row is a skipped waypoint, bridged), start_joints [n,7] or None, n_sub: the
+        sub-steps S per edge, 1 ... 256; spheres, capsules, link_radius as path_clear_batch.  Every edge is sampled at
+        a + angle_diff(b, a) * (s / S), s = 0 ... S.  Returns the outputs named in want (None: all of
+        HipSolver.CLEARANCE_EDGES_OUTPUTS): edge_clearance [T,n] (the least clearance_batch `clearance` over the samples), edge_sub
+        [T,n] int32 (the s that attains it), edge_nearest [T,n,2] int32 (link, obstacle index), edge_bound [T,n] (a certified lower
+        bound on the clearance of the whole continuous motion: above 0 the edge is proven free), and per path path_clearance [n],
+        path_edge [n,2] int32 (t, s), path_bound [n], n_below [n] int32 (edges with edge_clearance < min_clearance) and first_below
+        [n] int32 (the first such t, or -1)."""
+        return _clearance_edges_batch(self, {"arm_uniform": self.arm_id}, joints, start_joints, n_sub, spheres, capsules, link_radius,
+                                      min_clearance, want, out, plan_only)
+
     def fk_residual_batch(self, poses: Any, joints: Any) -> torch.Tensor:
         """err [n,2] = (position error m, rotation error rad) of FK(joints) against the poses they were solved for."""
         self._upload()
@@ -699,6 +715,13 @@ def _clearance_batch(ik, arm, joints, spheres, capsules, link_radius, want, out,
     ik._upload()
     return ik._solver.clearance(joints, spheres=spheres, capsules=capsules, link_radius=link_radius, want=want, out=out,
                                 plan_only=plan_only, **arm)
+
+
+def _clearance_edges_batch(ik, arm, joints, start_joints, n_sub, spheres, capsules, link_radius, min_clearance, want, out, plan_only):
+    ik._upload()
+    return ik._solver.clearance_edges(joints, start_joints, n_sub, spheres=spheres, capsules=capsules, link_radius=link_radius,
+                                      min_clearance=min_clearance, want=ik._solver.CLEARANCE_EDGES_OUTPUTS if want is None else want,
+                                      out=out, plan_only=plan_only, **arm)
 
 
 def arm_capsules(link_points: torch.Tensor, link_radius: Any = None) -> torch.Tensor:
@@ -935,6 +958,19 @@ class DualArmIK:
                 given = capsules if isinstance(capsules, torch.Tensor) else torch.as_tensor(np.asarray(capsules, dtype=np.float64))
                 capsules = torch.cat([given.to(device=dev, dtype=torch.float64).reshape(-1, 7), extra], dim=0)
         return _clearance_batch(self, {"arm": arm_ids}, joints, spheres, capsules, link_radius, want, out, plan_only)
+
+    def clearance_edges_batch(self, arm_ids: Any, joints: Any, start_joints: Any = None, n_sub: int = 16, spheres: Any = None,
+                              capsules: Any = None, link_radius: Any = None, min_clearance: float = -float("inf"),
+                              want: Optional[Sequence[str]] = None, out: Optional[Dict[str, torch.Tensor]] = None,
+                              plan_only: bool = False) -> Dict[str, torch.Tensor]:
+        """SymbolicIK.clearance_edges_batch for paths of both arms (arm_ids [n] uint8, one byte per path): the clearance along the
+        motion between the waypoints of joints [T,n,7], sampled at n_sub + 1 sub-steps per edge against the static scene.  Returns
+        edge_clearance, edge_sub, edge_nearest, edge_bound [T,n,...] (edge_bound: the certified lower bound on the continuous
+        motion) and path_clearance, path_edge, path_bound, n_below, first_below [n,...], as named in want (None: all).  The joints
+        of path_pair_batch are 2 n_pairs paths of their own here (row 2 i right, 2 i + 1 left) against the static scene; the other
+        arm in motion is not among the obstacles."""
+        return _clearance_edges_batch(self, {"arm": arm_ids}, joints, start_joints, n_sub, spheres, capsules, link_radius,
+                                      min_clearance, want, out, plan_only)
 
     def theta_from_joints_batch(self, arm_ids: Any, poses: Any, current_joints: Any, preferred_theta: Optional[Sequence[float]] = None,
                                 out: Optional[Dict[str, torch.Tensor]] = None, plan_only: bool = False) -> Dict[str, torch.Tensor]:
